@@ -7,19 +7,27 @@ VAE decode (point map + confidence, ray, ray-moment, inverse depth). BASELINE.js
 Inputs are synthetic (seeded), weights random-init, everything resident in HBM before the timed region.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full                  # + the extra legs and figures below
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR      # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --height 576 --width 1024 --batch 4 --dtype f16          # BASELINE configs[4] on one GPU
 
 Compute mode (`--dtype`, default bf16x3m): the headline number is quoted in a mode that MEETS the 1e-3 point-map parity bar - bf16x3m =
 bf16 MFMA on a 3-term hi/lo split of f32-stored operands (bf16x3), with the GEMMs fed by a normalised branch activation in two f16
 passes and the three attention branches on f16 rows (geo4d_amd/precision.py; point map 1.8e-4 against the REFERENCE's own 50-step window at
-BASELINE size: tests/golden/fullsize_ddim50.pt). The all-three-pass bf16x3 mode (1.7e-5 on that fixture) and the plain-bf16 fast
-mode (2e-2: NOT the bar) are timed in the same run and reported under `strict_mode` / `fast_mode`. N > 1: window-data-parallel denoise, FRAME-SHARDED VAE decode
+BASELINE size: tests/golden/fullsize_ddim50.pt). With `--full`, the all-three-pass bf16x3 mode (1.7e-5 on that fixture) and the
+plain-bf16 fast mode (2e-2: NOT the bar) are timed in the same run and reported under `strict_mode` / `fast_mode`. N > 1: window-data-parallel denoise, FRAME-SHARDED VAE decode
 (every rank decodes its frame slice of all the round's windows) and an RCCL all-gather of the decoded maps that overlaps
 the next window's denoise.
 
-Prints ONE JSON line (rank 0). `roofline` is the dominant kernel (conv_gemm) from a live HIP-event timeline;
-`cpu_baseline` times the oracle (CPU port of the reference path) at the real 40x64 latent size on the host cores.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps windows and prints the headline (`value`, `ms_per_step`,
+`split_ms_per_step`). `--full` adds, after the timed steps: `roofline` (the dominant kernel, conv_gemm, and the attention from live
+HIP-event timelines), `shipped_setting`, `strict_mode`, `fast_mode`, `batched_windows`, the `clip_mode` leg and `cpu_baseline` (the oracle,
+a CPU port of the reference path, at the real 40x64 latent size on the host cores); each can be left out with its --no-* flag.
+
+`--dump-outputs DIR` writes what the timed path returned in its LAST timed step (rank 0): the denoised latents and the decoded
+[B, 11, T, H, W] maps, float32 - whole when an array fits its share of DUMP_BYTES, else a fixed seeded sample of its elements
+(`<name>_sample.npy`, see dump_outputs). Inputs and weights are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -70,6 +78,24 @@ def window_tflop(T, h, w, ddim_steps, batch):
     tok = (T * h * w) / (16 * 40 * 64)
     unet = (TFLOP_UNET_STEP - TFLOP_ATTN_SELF) * tok + TFLOP_ATTN_SELF * tok * (h * w) / (40 * 64)
     return batch * (unet * ddim_steps + TFLOP_DECODE_FRAME * T * (h * w) / (40 * 64))
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> tensor) as path/<name>.npy in float32. Each array gets an equal share of DUMP_BYTES: one that fits is written
+    whole, a larger one as path/<name>_sample.npy = the flattened array at sorted element indices drawn (with replacement) from
+    torch.Generator seeded 0 - the same indices for the same shape, so two runs / builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _cpu_baseline_worker(q, ushapes, vshapes, ucfg, ddconfig, adaptorconfig, T, hs, ws, cores):
@@ -402,6 +428,10 @@ def main():
                     "frame-shard the round's decode over all ranks (default)")
     ap.add_argument("--launch-check", action="store_true", help="no compute: bring the N-rank job up (RCCL on GPUs, gloo without), run "
                     "the barrier / max-over-ranks timing protocol on an empty step and print the JSON skeleton (tests/test_dist_cpu.py)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else this benchmark reports: the roofline timelines, "
+                    "shipped_setting, strict_mode, fast_mode, batched_windows, the clip leg and the CPU baseline (each can be left out with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (denoised latents, decoded maps or a fixed "
+                    "seeded sample of them; float32, <= 64 MB in all) as DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fast-mode", action="store_true", help="skip the plain-bf16 timing reported next to the headline")
@@ -412,7 +442,7 @@ def main():
     ap.add_argument("--clip-align-on-noise", action="store_true", help="--clip-frames: run the alignment on the decoded noise of the random-init network instead of "
                     "the synthetic scene (its logs / medians go non-finite)")
     ap.add_argument("--align-iters", type=int, default=500, help="--clip-frames: Adam iterations of the global alignment (postprocess.n_iter of the shipped config)")
-    ap.add_argument("--no-clip-leg", action="store_true", help="skip the end-to-end clip leg the default run appends under `clip_mode` (ONE 64-frame clip: 14 sliding "
+    ap.add_argument("--no-clip-leg", action="store_true", help="skip the end-to-end clip leg --full appends under `clip_mode` (ONE 64-frame clip: 14 sliding "
                     "windows + decode + cameras + multi-window alignment, strong-scaled over the ranks; ~45 s on one GPU)")
     ap.add_argument("--window-batch", type=int, default=4, help="clip modes: windows a rank denoises as ONE batch (pipeline.run_clip window_batch; the headline "
                     "metric stays one window per step - BASELINE configs[1] - and reports the batched rate beside it as `batched_windows`)")
@@ -426,6 +456,8 @@ def main():
         raise SystemExit(self_launch(args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:            # checked BEFORE the rendezvous: a wrong count would hang in it
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE', '1')} (the launcher's --nproc-per-node must equal --gpus)")
+    if args.dump_outputs and (args.launch_check or args.clip_frames):
+        raise SystemExit("bench.py: --dump-outputs writes the window path's outputs: not with --launch-check / --clip-frames")
     rank, world, local = gdist.init_from_env()
     if args.launch_check:
         return launch_check(args, rank, world, local)
@@ -456,6 +488,7 @@ def main():
         """`nb`: windows per step instead of --batch (the `batched_windows` leg: the same windows, `nb` at a time)."""
         split = [0.0, 0.0]
         pending = []
+        lat = None
         Bx = nb or B
         cond_x, fs_x = cond, fs
         if Bx != B:
@@ -464,6 +497,7 @@ def main():
             fs_x = torch.full((Bx,), 24, dtype=torch.long, device=dev)
 
         def one_window(seed, timed):
+            nonlocal lat
             x_T = torch.randn((Bx, 16, T, h, w), generator=torch.Generator().manual_seed(seed)).to(dev)
             if timed:
                 ev[0].record()
@@ -517,32 +551,17 @@ def main():
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             dt = tt.item()
         assert torch.isfinite(out).all()
-        return dt, split
+        return dt, split, {"latents": lat, "decoded": out}
 
     sampler = DDIMSampler(model, use_graph=not args.no_graph)
-    dt, split = run_mode(sampler, args.steps, args.warmup)
+    dt, split, outs = run_mode(sampler, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
+    del outs
 
     res = None
     if rank == 0:
         frames = T * B * args.steps * world
-        tflop_step = window_tflop(T, h, w, args.ddim_steps, B)
-        achieved = tflop_step * args.steps / dt                       # per-GPU algorithmic TFLOP/s, whole step
-        peak = MFMA_PEAK_TF[args.dtype]
-        passes = MFMA_PASSES[args.dtype]
-        x_T = torch.randn((B, 16, T, h, w), generator=torch.Generator().manual_seed(7)).to(dev)
-        n_gemm, tf_gemm, ms_gemm, tf_issued = gemm_timeline(model, x_T, cond, fs, dev)
-        n_att, tf_att, ms_att, tf_att_issued = attn_timeline(model, x_T, cond, fs, dev)
-        traffic, traffic_note, traffic_by_class = None, "no PMC summary committed for this dtype / size", None
-        # the NEWEST committed PMC summary of this mode (round-end passes at HEAD are named r<NN>_head_pmc_* or r<NN>_pmc_*)
-        cands = [os.path.join(ROOT, "profiles", f"r{r:02d}_{tag}pmc_{args.dtype}.json") for r in range(9, 1, -1) for tag in ("head_", "")]
-        pmc_path = next((q for q in cands if os.path.exists(q)), "")
-        if (args.height, args.width, T, B) == (320, 512, 16, 1) and pmc_path:
-            with open(pmc_path) as f:
-                pmc = json.load(f)["per_unet_forward"]
-            traffic = pmc["fetch_bytes_x2"] + pmc["write_bytes"]
-            traffic_by_class = pmc.get("by_class")
-            traffic_note = ("L2-miss (fabric-side) bytes of ONE U-Net forward, ALL its kernels: (2 x FETCH_SIZE + WRITE_SIZE) x 1024 from "
-                            f"separate rocprofv3 --pmc passes ({os.path.basename(pmc_path)}; Infinity-Cache hits included: upper bound on HBM bytes)")
         cfg_name = "BASELINE.json configs[1]" if (args.height, args.width, T, B) == (320, 512, 16, 1) else \
             ("BASELINE.json configs[4] on one GPU" if (args.height, args.width, B) == (576, 1024, 4) else "non-default size")
         res = {
@@ -569,74 +588,94 @@ def main():
                                               else torch.distributed.get_backend()) if world > 1 else None,
                        "hipgraph": not args.no_graph},
             "split_ms_per_step": {"ddim_denoise": split[0] / args.steps, "vae_decode_4_modalities": split[1] / args.steps},
-            "roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel (MFMA implicit GEMM: every conv / linear / batched GEMM of the path)",
-                         # achieved = ALGORITHMIC flops (each product once) / kernel time; peak = the dense MFMA peak of the operand type
-                         # (MI355X_MICROARCH.md: 2.5 PF bf16 / f16); frac = achieved / peak = useful work. frac_issued counts every MFMA
-                         # the mode issues (bf16x3: three per product) against the same peak = how busy the kernel keeps the matrix pipe.
-                         "achieved": tf_gemm / ms_gemm * 1e3, "peak": peak, "unit": "TFLOP/s",
-                         "frac": tf_gemm / ms_gemm * 1e3 / peak,                              # = frac_algorithmic (algorithmic flops / dense MFMA peak)
-                         "frac_algorithmic": tf_gemm / ms_gemm * 1e3 / peak,
-                         "frac_issued": tf_issued / ms_gemm * 1e3 / peak,              # MFMA instructions issued / dense peak (bf16x3: 3 per product; counted per launch)
-                         "mfma_issued_tflops": tf_issued / ms_gemm * 1e3, "mfma_dense_peak": peak, "mfma_passes_per_product": tf_issued / tf_gemm,
-                         "launches_per_unet_forward": n_gemm, "tflop_per_unet_forward": tf_gemm, "ms_per_unet_forward": ms_gemm,
-                         "avg_launch_us": 1e3 * ms_gemm / n_gemm,
-                         "traffic": traffic, "traffic_note": traffic_note,
-                         "traffic_by_kernel_class_gb": traffic_by_class,      # the same PMC passes split by kernel class (GB per U-Net forward)
-                         "note": "achieved = algorithmic flops (sum of 2*M*N*K over the conv_gemm launches of ONE eager U-Net forward, each product "
-                                 "counted once) / sum of their HIP-event durations on the launch stream (brackets include a split-K launch's reduce "
-                                 "kernel and ~2 us of dispatch gap each; the rocprofv3 kernel trace in profiles/ gives the pure kernel time); "
-                                 "peak = dense MFMA peak of the operand type; measured on this GPU type (profiles/r02_mfma_probe_and_kloop.md): "
-                                 "a pure MFMA loop on uniform random bf16 operands reaches 0.71 of that peak, 0.64 with the LDS fragment reads of the tile",
-                         "attention": {"kernel": "flash_attn_kernel (spatial self-attention, d_head 64: QK^T, online softmax, PV)",
-                                       "achieved": tf_att / ms_att * 1e3 if ms_att else None, "peak": peak, "unit": "TFLOP/s",
-                                       "frac_algorithmic": tf_att / ms_att * 1e3 / peak if ms_att else None,
-                                       "frac_issued": tf_att_issued / ms_att * 1e3 / peak if ms_att else None,
-                                       "mfma_passes_per_product": tf_att_issued / tf_att if tf_att else None,
-                                       "launches_per_unet_forward": n_att, "tflop_per_unet_forward": tf_att, "ms_per_unet_forward": ms_att,
-                                       "note": "north_star's >= 40 % target is on frac_issued of this kernel (bf16x3m since round 6: ONE f16 MFMA per product, so issued == algorithmic; "
-                                               "VERDICT r5's alternative bar for fewer passes: frac_algorithmic >= 0.16); HIP-event brackets on the launch stream, one eager forward"},
-                         "whole_step": {"achieved": achieved, "frac": achieved / peak, "frac_issued": (tf_issued / tf_gemm if tf_gemm else passes) * achieved / peak,
-                                        "note": f"{tflop_step:.1f} algorithmic TFLOP per step (SURVEY §8d: {TFLOP_UNET_STEP} x S + "
-                                                f"{TFLOP_DECODE_FRAME} x T at 16x40x64, scaled) / measured step time, per GPU, products counted once"}},
         }
-    if not args.no_shipped_setting and args.ddim_steps != 5:
+        if args.full:
+            # the dominant kernel and the attention, from live HIP-event timelines of eager U-Net forwards (outside the timed region)
+            tflop_step = window_tflop(T, h, w, args.ddim_steps, B)
+            achieved = tflop_step * args.steps / dt                       # per-GPU algorithmic TFLOP/s, whole step
+            peak = MFMA_PEAK_TF[args.dtype]
+            passes = MFMA_PASSES[args.dtype]
+            x_T = torch.randn((B, 16, T, h, w), generator=torch.Generator().manual_seed(7)).to(dev)
+            n_gemm, tf_gemm, ms_gemm, tf_issued = gemm_timeline(model, x_T, cond, fs, dev)
+            n_att, tf_att, ms_att, tf_att_issued = attn_timeline(model, x_T, cond, fs, dev)
+            traffic, traffic_note, traffic_by_class = None, "no PMC summary committed for this dtype / size", None
+            # the NEWEST committed PMC summary of this mode (round-end passes at HEAD are named r<NN>_head_pmc_* or r<NN>_pmc_*)
+            cands = [os.path.join(ROOT, "profiles", f"r{r:02d}_{tag}pmc_{args.dtype}.json") for r in range(9, 1, -1) for tag in ("head_", "")]
+            pmc_path = next((q for q in cands if os.path.exists(q)), "")
+            if (args.height, args.width, T, B) == (320, 512, 16, 1) and pmc_path:
+                with open(pmc_path) as f:
+                    pmc = json.load(f)["per_unet_forward"]
+                traffic = pmc["fetch_bytes_x2"] + pmc["write_bytes"]
+                traffic_by_class = pmc.get("by_class")
+                traffic_note = ("L2-miss (fabric-side) bytes of ONE U-Net forward, ALL its kernels: (2 x FETCH_SIZE + WRITE_SIZE) x 1024 from "
+                                f"separate rocprofv3 --pmc passes ({os.path.basename(pmc_path)}; Infinity-Cache hits included: upper bound on HBM bytes)")
+            res["roofline"] = {"bound": "mfma", "kernel": "conv_gemm_kernel (MFMA implicit GEMM: every conv / linear / batched GEMM of the path)",
+                               # achieved = ALGORITHMIC flops (each product once) / kernel time; peak = the dense MFMA peak of the operand type
+                               # (MI355X_MICROARCH.md: 2.5 PF bf16 / f16); frac = achieved / peak = useful work. frac_issued counts every MFMA
+                               # the mode issues (bf16x3: three per product) against the same peak = how busy the kernel keeps the matrix pipe.
+                               "achieved": tf_gemm / ms_gemm * 1e3, "peak": peak, "unit": "TFLOP/s",
+                               "frac": tf_gemm / ms_gemm * 1e3 / peak,                              # = frac_algorithmic (algorithmic flops / dense MFMA peak)
+                               "frac_algorithmic": tf_gemm / ms_gemm * 1e3 / peak,
+                               "frac_issued": tf_issued / ms_gemm * 1e3 / peak,              # MFMA instructions issued / dense peak (bf16x3: 3 per product; counted per launch)
+                               "mfma_issued_tflops": tf_issued / ms_gemm * 1e3, "mfma_dense_peak": peak, "mfma_passes_per_product": tf_issued / tf_gemm,
+                               "launches_per_unet_forward": n_gemm, "tflop_per_unet_forward": tf_gemm, "ms_per_unet_forward": ms_gemm,
+                               "avg_launch_us": 1e3 * ms_gemm / n_gemm,
+                               "traffic": traffic, "traffic_note": traffic_note,
+                               "traffic_by_kernel_class_gb": traffic_by_class,      # the same PMC passes split by kernel class (GB per U-Net forward)
+                               "note": "achieved = algorithmic flops (sum of 2*M*N*K over the conv_gemm launches of ONE eager U-Net forward, each product "
+                                       "counted once) / sum of their HIP-event durations on the launch stream (brackets include a split-K launch's reduce "
+                                       "kernel and ~2 us of dispatch gap each; the rocprofv3 kernel trace in profiles/ gives the pure kernel time); "
+                                       "peak = dense MFMA peak of the operand type; measured on this GPU type (profiles/r02_mfma_probe_and_kloop.md): "
+                                       "a pure MFMA loop on uniform random bf16 operands reaches 0.71 of that peak, 0.64 with the LDS fragment reads of the tile",
+                               "attention": {"kernel": "flash_attn_kernel (spatial self-attention, d_head 64: QK^T, online softmax, PV)",
+                                             "achieved": tf_att / ms_att * 1e3 if ms_att else None, "peak": peak, "unit": "TFLOP/s",
+                                             "frac_algorithmic": tf_att / ms_att * 1e3 / peak if ms_att else None,
+                                             "frac_issued": tf_att_issued / ms_att * 1e3 / peak if ms_att else None,
+                                             "mfma_passes_per_product": tf_att_issued / tf_att if tf_att else None,
+                                             "launches_per_unet_forward": n_att, "tflop_per_unet_forward": tf_att, "ms_per_unet_forward": ms_att,
+                                             "note": "north_star's >= 40 % target is on frac_issued of this kernel (bf16x3m since round 6: ONE f16 MFMA per product, so issued == algorithmic; "
+                                                     "VERDICT r5's alternative bar for fewer passes: frac_algorithmic >= 0.16); HIP-event brackets on the launch stream, one eager forward"},
+                               "whole_step": {"achieved": achieved, "frac": achieved / peak, "frac_issued": (tf_issued / tf_gemm if tf_gemm else passes) * achieved / peak,
+                                              "note": f"{tflop_step:.1f} algorithmic TFLOP per step (SURVEY §8d: {TFLOP_UNET_STEP} x S + "
+                                                      f"{TFLOP_DECODE_FRAME} x T at 16x40x64, scaled) / measured step time, per GPU, products counted once"}}
+    if args.full and not args.no_shipped_setting and args.ddim_steps != 5:
         # the reference ships --ddim_steps 5 (scripts/infer_geo4d.sh:22): the same captured step replayed 5 times per window, where the
         # 4-modality decode is the larger half of the window
         S0, args.ddim_steps = args.ddim_steps, 5
-        sdt, ssplit = run_mode(sampler, 2, 1)
+        sdt, ssplit, _ = run_mode(sampler, 2, 1)
         args.ddim_steps = S0
         if rank == 0:
             res["shipped_setting"] = {"ddim_steps": 5, "value": T * B * 2 * world / sdt, "unit": "frames/s", "ms_per_step": 1e3 * sdt / 2, "steps": 2,
                                       "split_ms_per_step": {"ddim_denoise": ssplit[0] / 2, "vae_decode_4_modalities": ssplit[1] / 2},
                                       "note": "scripts/infer_geo4d.sh:22 runs 5 DDIM steps: decode-bound"}
-    if not args.no_strict_mode and args.dtype == "bf16x3m":
+    if args.full and not args.no_strict_mode and args.dtype == "bf16x3m":
         # every product in three bf16 passes (round 2-4's headline mode: 2e-5 on the point map), same engine / weights / inputs, same process
         set_mode(model, pvae, "bf16x3")
         ssteps = max(1, min(args.steps, 3))
-        xdt, xsplit = run_mode(DDIMSampler(model, use_graph=not args.no_graph), ssteps, 1)
+        xdt, xsplit, _ = run_mode(DDIMSampler(model, use_graph=not args.no_graph), ssteps, 1)
         set_mode(model, pvae, args.dtype)
         if rank == 0:
             res["strict_mode"] = {"dtype": "bf16x3", "value": T * B * ssteps * world / xdt, "unit": "frames/s", "ms_per_step": 1e3 * xdt / ssteps, "steps": ssteps,
                                   "split_ms_per_step": {"ddim_denoise": xsplit[0] / ssteps, "vae_decode_4_modalities": xsplit[1] / ssteps},
                                   "parity": "point map 1.7e-5 vs the REFERENCE's 50-step window at this size (tests/golden/fullsize_ddim50.pt), 2.1e-5 on its 3-step window "
                                             "(fullsize_ddim.pt); the headline mode bf16x3m on the same two fixtures: 1.8e-4 / 3.9e-4 (tests/test_fullsize_gpu.py; bar 1e-3)"}
-    if not args.no_fast_mode and args.dtype in ("bf16x3", "bf16x3m"):
+    if args.full and not args.no_fast_mode and args.dtype in ("bf16x3", "bf16x3m"):
         # the plain-bf16 fast mode, same engine / weights / inputs, timed in the same process (all ranks take part)
         set_mode(model, pvae, "bf16")
         fsteps = max(1, min(args.steps, 3))
-        fdt, fsplit = run_mode(DDIMSampler(model, use_graph=not args.no_graph), fsteps, 1)
+        fdt, fsplit, _ = run_mode(DDIMSampler(model, use_graph=not args.no_graph), fsteps, 1)
         set_mode(model, pvae, args.dtype)
         if rank == 0:
             res["fast_mode"] = {"dtype": "bf16", "value": T * B * fsteps * world / fdt, "unit": "frames/s", "ms_per_step": 1e3 * fdt / fsteps,
                                 "steps": fsteps, "split_ms_per_step": {"ddim_denoise": fsplit[0] / fsteps, "vae_decode_4_modalities": fsplit[1] / fsteps},
                                 "parity": "point map ~2e-2 rel L2 vs the fp32 reference (tests/test_parity_gpu.py): NOT the 1e-3 bar, hence not the headline"}
-    if not args.no_batched_windows and B == 1 and args.window_batch > 1:
+    if args.full and not args.no_batched_windows and B == 1 and args.window_batch > 1:
         # Windows are independent (scripts/evaluation/test_geo4d.py:431-443), and at one window per step the U-Net's levels 1-3 cannot fill 256 CUs
         # (tiles < CUs). The headline above stays BASELINE configs[1] - ONE window per step; this leg times the same work `--window-batch` windows
         # at a time, which is how pipeline.run_clip(window_batch=...) runs a multi-window clip (and the clip leg below).
         bsteps = max(1, min(args.steps, 2))
         try:
-            bdt, bsplit = run_mode(DDIMSampler(model, use_graph=not args.no_graph), bsteps, 1, nb=args.window_batch)
+            bdt, bsplit, _ = run_mode(DDIMSampler(model, use_graph=not args.no_graph), bsteps, 1, nb=args.window_batch)
         except Exception as e:       # noqa: BLE001 - an extra leg must not cost the headline (every rank runs the same code: a failure is symmetric)
             bdt, bsplit = None, None
             if rank == 0:
@@ -648,7 +687,7 @@ def main():
                                       "split_ms_per_step": {"ddim_denoise": bsplit[0] / bsteps, "vae_decode_4_modalities": bsplit[1] / bsteps},
                                       "note": "same engine / weights / mode as the headline, the SAME per-window work, windows batched: not the headline "
                                               "(BASELINE configs[1] is a single window), reported because every multi-window clip (configs[2], [3]) runs this way"}
-    if not args.no_clip_leg and B == 1 and T == 16:
+    if args.full and not args.no_clip_leg and B == 1 and T == 16:
         # north_star's strong-scaling sentence in the SAME record: one clip, windows round-robin over the ranks, frame-sharded decode, all-gather,
         # sharded alignment (clip_mode above). A failure here must not cost the headline: it is reported under the key instead.
         import copy
@@ -666,7 +705,7 @@ def main():
                                                                            "denoised_frames_per_sec", "alignment_outputs_finite", "alignment_vs_scene_truth", "data")} | {
                 "windows": cm["config"]["windows"], "windows_per_rank_max": cm["config"]["windows_per_rank_max"], "parallelism": cm["config"]["parallelism"]}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(model, pvae, args.ddim_steps, T, h, w)
         print(json.dumps(res))
     if world > 1:

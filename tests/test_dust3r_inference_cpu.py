@@ -1,4 +1,4 @@
-"""The `dust3r/inference.py` call surface (reference: /root/reference/dust3r/inference.py:27-179,
+"""The `dust3r/inference.py` call surface (reference: dust3r/inference.py:27-179,
 dust3r/utils/device.py:10-75) on the host, with a stub pairwise model: batching, collation, the batch-size-1 fallback for images of
 different sizes, symmetrised batches. No GPU, no reference import (the behaviours are stated here as plain expectations)."""
 import numpy as np
@@ -70,53 +70,17 @@ def test_symmetrized_batch_and_loss_hook():
     assert di.loss_of_one_batch((v1, v2), StubModel(), None, "cpu", ret="pred2")["pts3d_in_other_view"].shape[0] == 2
 
 
-def _reference_get_pred_pts3d():
-    """The reference's own function (build container only: /root/reference is absent on the GPU box), or None."""
-    import importlib.util
+def _reference_pts3d_cases():
+    """The reference's own get_pred_pts3d (dust3r/inference.py:110-132) on the six cases of the test below: inputs and outputs stored by
+    `python tests/golden/generate.py dust3r_pts3d`."""
     import os
-    import sys
-    import types
-    root = "/root/reference"
-    if not os.path.isdir(root):
-        return None
-    saved = {k: sys.modules.get(k) for k in ("dust3r", "dust3r.utils", "dust3r.utils.device", "dust3r.utils.misc", "dust3r.utils.geometry",
-                                            "dust3r.viz", "dust3r.utils.image", "tqdm")}
-    try:
-        for name in ("dust3r", "dust3r.utils"):
-            m = types.ModuleType(name)
-            m.__path__ = [os.path.join(root, *name.split("."))]
-            sys.modules[name] = m
-        viz, img = types.ModuleType("dust3r.viz"), types.ModuleType("dust3r.utils.image")       # plotting / image helpers: not on this path
-        viz.SceneViz = viz.auto_cam_size = img.rgb = None
-        sys.modules["dust3r.viz"], sys.modules["dust3r.utils.image"] = viz, img
-        misc = types.ModuleType("dust3r.utils.misc")          # the real one drags cv2 / evo in at module level; these two are not called here
-        misc.invalid_to_nans = misc.invalid_to_zeros = None
-        sys.modules["dust3r.utils.misc"] = misc
-        if saved["tqdm"] is None:
-            try:
-                import tqdm  # noqa: F401
-            except ImportError:
-                t = types.ModuleType("tqdm")
-                t.tqdm = lambda x, **k: x
-                sys.modules["tqdm"] = t
-        spec = importlib.util.spec_from_file_location("dust3r.inference", os.path.join(root, "dust3r", "inference.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod.get_pred_pts3d
-    except Exception:
-        return None
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    return torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dust3r_pts3d.pt"), weights_only=False)
 
 
 def test_get_pred_pts3d_all_branches_match_the_reference():
     """`use_pose` goes through camera_pose (it used to return the untransformed points) and the
-    depth + pseudo_focal branch exists. Expectations are closed-form; where /root/reference is importable the reference's own
-    get_pred_pts3d (dust3r/inference.py:110-132) is run beside ours on the same inputs."""
+    depth + pseudo_focal branch exists. Expectations are closed-form, and the reference's own get_pred_pts3d (dust3r/inference.py:110-132)
+    on the same inputs is checked beside them (tests/golden/dust3r_pts3d.pt)."""
     g = torch.Generator().manual_seed(5)
     B, H, W = 2, 5, 7
     pts = torch.randn((B, H, W, 3), generator=g)
@@ -133,8 +97,11 @@ def test_get_pred_pts3d_all_branches_match_the_reference():
              ({"camera_intrinsics": K}, {"depth": depth, "pseudo_focal": focal2, "camera_pose": pose}, True),
              ({"camera_intrinsics": K}, {"depth": depth, "pseudo_focal": focal2[:, :1]}, False),
              ({}, {"pts3d_in_other_view": pts, "camera_pose": pose}, True)]
-    ref = _reference_get_pred_pts3d()
-    for gt, pred, use_pose in cases:
+    ref = _reference_pts3d_cases()
+    assert len(ref) == len(cases)
+    for (gt, pred, use_pose), rc in zip(cases, ref):
+        assert rc["use_pose"] == use_pose and rc["gt"].keys() == gt.keys() and rc["pred"].keys() == pred.keys()
+        assert all(torch.equal(rc["gt"][k], gt[k]) for k in gt) and all(torch.equal(rc["pred"][k], pred[k]) for k in pred)   # same inputs
         got = di.get_pred_pts3d(gt, pred, use_pose=use_pose)
         if "pts3d_in_other_view" in pred:
             want = pts
@@ -152,8 +119,7 @@ def test_get_pred_pts3d_all_branches_match_the_reference():
             if use_pose:
                 want = torch.einsum("bij,bhwj->bhwi", pose[:, :3, :3], want) + pose[:, None, None, :3, 3]
         assert torch.allclose(got, want, atol=1e-5), (list(pred), use_pose)
-        if ref is not None:
-            assert torch.allclose(got, ref(gt, pred, use_pose=use_pose), atol=1e-6), (list(pred), use_pose)
+        assert torch.allclose(got, rc["out"], atol=1e-6), (list(pred), use_pose)
     import pytest
     with pytest.raises(AssertionError):
         di.get_pred_pts3d({}, {"pts3d": pts}, use_pose=True)           # camera_pose missing: the reference asserts

@@ -39,7 +39,7 @@ case $JOB in
     ( time timeout 1200 python -m pytest tests/test_fullsize_gpu.py tests/test_parity_gpu.py -m gpu -q -x -s ) > $O/pytest_full.log 2>&1; echo "pytest rc=$?" >> $O/pytest_full.log
     grep -E "^\[|passed|failed|rc=|Error|assert" $O/pytest_full.log | cut -c1-300 | tail -14
     for i in 1 2; do
-      timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$i.json 2> $O/bench_$i.err
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$i.json 2> $O/bench_$i.err
       python - <<PY
 import json
 try:
@@ -67,8 +67,8 @@ PY
     }
     for i in 1 2; do
       ( cd gpurun_ab_r5 && timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_r5_$i.json 2> $O/bench_r5_$i.err ); bl $O/bench_r5_$i.json "r5 tree run $i:"
-      GEO4D_TWO_PASS=conv3x3,vae3x3,tconv,ln,ff timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_noattn_$i.json 2> $O/bench_noattn_$i.err; bl $O/bench_noattn_$i.json "r6 f16 rows, no attn class run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_attn_$i.json 2> $O/bench_attn_$i.err; bl $O/bench_attn_$i.json "r6 + attn class run $i:"
+      GEO4D_TWO_PASS=conv3x3,vae3x3,tconv,ln,ff timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_noattn_$i.json 2> $O/bench_noattn_$i.err; bl $O/bench_noattn_$i.json "r6 f16 rows, no attn class run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_attn_$i.json 2> $O/bench_attn_$i.err; bl $O/bench_attn_$i.json "r6 + attn class run $i:"
     done
     ;;
   r6c)         # split-K without a reduce launch (wave tickets): bit-equal to the reduce kernel? faster? (same-box A/B by environment switch)
@@ -85,11 +85,11 @@ except Exception as e:
 PY
     }
     for i in 1 2; do
-      GEO4D_SPLITK_FUSED=0 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_reduce_$i.json 2> $O/bench_reduce_$i.err; bl $O/bench_reduce_$i.json "reduce kernel run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_fused_$i.json 2> $O/bench_fused_$i.err; bl $O/bench_fused_$i.json "fused split-K run $i:"
+      GEO4D_SPLITK_FUSED=0 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_reduce_$i.json 2> $O/bench_reduce_$i.err; bl $O/bench_reduce_$i.json "reduce kernel run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_fused_$i.json 2> $O/bench_fused_$i.err; bl $O/bench_fused_$i.json "fused split-K run $i:"
     done
     cd /tmp
-    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
+    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
     find /tmp/prof/kt -name "*kernel_stats.csv" -exec cp {} $O/kt_kernel_stats.csv \;
     KT=$(find /tmp/prof/kt -name "*kernel_trace.csv" | head -1)
     [ -n "$KT" ] && python $R/tools/prof_phases.py $KT 40 > $O/phases.md 2>&1
@@ -108,8 +108,8 @@ except Exception as e:
 PY
     }
     for i in 1 2; do
-      GEO4D_SPLITK_FUSED=0 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_reduce_$i.json 2> $O/bench_reduce_$i.err; bl $O/bench_reduce_$i.json "reduce kernel run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_fused_$i.json 2> $O/bench_fused_$i.err; bl $O/bench_fused_$i.json "fused split-K run $i:"
+      GEO4D_SPLITK_FUSED=0 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_reduce_$i.json 2> $O/bench_reduce_$i.err; bl $O/bench_reduce_$i.json "reduce kernel run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_fused_$i.json 2> $O/bench_fused_$i.err; bl $O/bench_fused_$i.json "fused split-K run $i:"
     done
     ;;
   r6e)         # classes cattn / tattn (cross- and temporal-attention chains on f16 rows): parity + frames/s per class, same box; the 50-step reference fixture
@@ -128,7 +128,7 @@ PY
     done
     for i in 1 2; do
       for cls in $BASE $BASE,cattn $BASE,tattn $BASE,cattn,tattn; do
-        GEO4D_TWO_PASS=$cls timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_${cls}_$i.json 2> $O/bench_${cls}_$i.err; bl $O/bench_${cls}_$i.json "$cls run $i:"
+        GEO4D_TWO_PASS=$cls timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_${cls}_$i.json 2> $O/bench_${cls}_$i.err; bl $O/bench_${cls}_$i.json "$cls run $i:"
       done
     done
     ( time GEO4D_TWO_PASS=$BASE,cattn,tattn timeout 1500 python -m pytest tests/test_fullsize_gpu.py tests/test_parity_gpu.py -m gpu -q -s -k "full_size or window_end_to_end or ddim_sampler" ) > $O/pytest_full.log 2>&1; echo "pytest rc=$?" >> $O/pytest_full.log
@@ -151,7 +151,7 @@ PY
     done
     for i in 1 2; do
       for cls in $BASE $BASE,vaeup; do
-        GEO4D_TWO_PASS=$cls timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_${cls}_$i.json 2> $O/bench_${cls}_$i.err; bl $O/bench_${cls}_$i.json "$cls run $i:"
+        GEO4D_TWO_PASS=$cls timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_${cls}_$i.json 2> $O/bench_${cls}_$i.err; bl $O/bench_${cls}_$i.json "$cls run $i:"
       done
     done
     ;;
@@ -166,15 +166,15 @@ except Exception as e:
 PY
     }
     cp geo4d_amd/tuning/gfx950.json $O/gfx950_before.json
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_old_1.json 2> $O/bench_old_1.err; bl $O/bench_old_1.json "old table run 1:"
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_old_1.json 2> $O/bench_old_1.err; bl $O/bench_old_1.json "old table run 1:"
     timeout 1500 python tools/tune_gemm.py $O/gfx950.json --keep --drop-prefix=4/ bf16x3m > $O/tune.log 2>&1; show $O/tune.log | tail -3
     if [ -s $O/gfx950.json ]; then
       cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_new_1.json 2> $O/bench_new_1.err; bl $O/bench_new_1.json "new table run 1:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_new_1.json 2> $O/bench_new_1.err; bl $O/bench_new_1.json "new table run 1:"
       cp $O/gfx950_before.json geo4d_amd/tuning/gfx950.json
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_old_2.json 2> $O/bench_old_2.err; bl $O/bench_old_2.json "old table run 2:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_old_2.json 2> $O/bench_old_2.err; bl $O/bench_old_2.json "old table run 2:"
       cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_new_2.json 2> $O/bench_new_2.err; bl $O/bench_new_2.json "new table run 2:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_new_2.json 2> $O/bench_new_2.err; bl $O/bench_new_2.json "new table run 2:"
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -4 $O/smoke.log
     fi
     ;;
@@ -192,8 +192,8 @@ except Exception as e:
 PY
     }
     for i in 1 2; do
-      GEO4D_SPLITK_COLSUM=0 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "split-K colsum off run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "split-K colsum on run $i:"
+      GEO4D_SPLITK_COLSUM=0 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "split-K colsum off run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "split-K colsum on run $i:"
     done
     ;;
   r6i)         # the f16-row epilogue on every two-pass tile (160x320 for N = 640 / 960 / 1920 ...): tests, re-tune the "o" launches, A/B old vs new table
@@ -214,9 +214,9 @@ PY
     if [ -s $O/gfx950.json ]; then
       for i in 1 2; do
         cp $O/gfx950_before.json geo4d_amd/tuning/gfx950.json
-        timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_old_$i.json 2> $O/bench_old_$i.err; bl $O/bench_old_$i.json "old table run $i:"
+        timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_old_$i.json 2> $O/bench_old_$i.err; bl $O/bench_old_$i.json "old table run $i:"
         cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-        timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_new_$i.json 2> $O/bench_new_$i.err; bl $O/bench_new_$i.json "new table run $i:"
+        timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_new_$i.json 2> $O/bench_new_$i.err; bl $O/bench_new_$i.json "new table run $i:"
       done
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke
     fi
@@ -234,8 +234,8 @@ except Exception as e:
 PY
     }
     for i in 1 2; do
-      GEO4D_X3_PRESPLIT_UP=0 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "presplit-up off run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "presplit-up on run $i:"
+      GEO4D_X3_PRESPLIT_UP=0 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "presplit-up off run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "presplit-up on run $i:"
     done
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke
     ;;
@@ -255,9 +255,9 @@ PY
     if [ -s $O/gfx950.json ]; then
       for i in 1 2; do
         cp $O/gfx950_before.json geo4d_amd/tuning/gfx950.json
-        timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_old_$i.json 2> $O/bench_old_$i.err; bl $O/bench_old_$i.json "old table run $i:"
+        timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_old_$i.json 2> $O/bench_old_$i.err; bl $O/bench_old_$i.json "old table run $i:"
         cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-        timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_new_$i.json 2> $O/bench_new_$i.err; bl $O/bench_new_$i.json "new table run $i:"
+        timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows > $O/bench_new_$i.json 2> $O/bench_new_$i.err; bl $O/bench_new_$i.json "new table run $i:"
       done
     fi
     ;;
@@ -275,8 +275,8 @@ except Exception as e:
 PY
     }
     for i in 1 2; do
-      GEO4D_FUSED_CONCAT=0 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "concat copies run $i:"
-      timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "producers write the halves run $i:"
+      GEO4D_FUSED_CONCAT=0 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_off_$i.json 2> $O/bench_off_$i.err; bl $O/bench_off_$i.json "concat copies run $i:"
+      timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-batched-windows --no-shipped-setting > $O/bench_on_$i.json 2> $O/bench_on_$i.err; bl $O/bench_on_$i.json "producers write the halves run $i:"
     done
     ;;
   r5a)         # first call of round 5: the two-pass f16 GEMM / bf16x3m mode - correct? how much faster per conv? accurate at size over 50 steps? end to end?
@@ -291,7 +291,7 @@ PY
     grep -E "^\[|passed|failed|rc=|Error|assert" $O/pytest_fullsize.log | cut -c1-400 | tail -14
     for i in 1 2; do
       for m in bf16x3 bf16x3m; do
-        timeout 400 python bench.py --steps 3 --warmup 1 --dtype $m --no-cpu-baseline --no-fast-mode > $O/bench_${m}_$i.json 2> $O/bench_${m}_$i.err
+        timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $m --no-cpu-baseline --no-fast-mode > $O/bench_${m}_$i.json 2> $O/bench_${m}_$i.err
         python - <<PY
 import json
 try:
@@ -303,7 +303,7 @@ PY
       done
     done
     cd /tmp
-    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-shipped-setting > $O/kt.log 2>&1
+    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-shipped-setting > $O/kt.log 2>&1
     find /tmp/prof/kt -name "*kernel_stats.csv" -exec cp {} $O/kt_kernel_stats.csv \;
     KT=$(find /tmp/prof/kt -name "*kernel_trace.csv" | head -1)
     [ -n "$KT" ] && python $R/tools/prof_phases.py $KT 16 > $O/phases_bf16x3m.md 2>&1
@@ -312,10 +312,10 @@ PY
   r5final)     # the round's last call: HEAD as the driver will run it (suite, smoke, default line) + the trace / PMC evidence of that very tree
     ( time timeout 1500 python -m pytest tests -m gpu -q -x -s ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; grep -E "passed|failed|rc=|^FAILED|^ERROR" $O/pytest.log | tail -5
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -5 $O/smoke.log
-    ( time timeout 900 python bench.py --steps 5 --warmup 2 ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err
+    ( time timeout 900 python bench.py --steps 5 --warmup 2 --full ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err
     python -c "import json; d=json.loads([l for l in open('$O/bench.json') if l.startswith('{')][-1]); print('default line:', d['dtype'], round(d['value'],3), d['split_ms_per_step'], 'strict', round(d['strict_mode']['value'],3), 'fast', round(d['fast_mode']['value'],3), 'shipped', round(d['shipped_setting']['value'],2), 'clip s', round(d['clip_mode']['ms_per_step']/1e3,2), 'frac', round(d['roofline']['frac'],4), 'issued', round(d['roofline']['frac_issued'],3), 'attn issued', round(d['roofline']['attention']['frac_issued'],3))"
     cd /tmp
-    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
+    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
     find /tmp/prof/kt -name "*kernel_stats.csv" -exec cp {} $O/kt_kernel_stats.csv \;
     KT=$(find /tmp/prof/kt -name "*kernel_trace.csv" | head -1)
     [ -n "$KT" ] && python $R/tools/prof_phases.py $KT 30 > $O/phases.md 2>&1
@@ -336,7 +336,7 @@ PY
     cd $R/gpurun_ab_r4 && ( time make -j64 > $O/build_r4.log 2>&1 ) 2>&1 | grep real
     for i in 1 2; do
       cd $R/gpurun_ab_r4 && timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/ab_r4_$i.json 2> $O/ab_r4_$i.err
-      cd $R && timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/ab_r5_$i.json 2> $O/ab_r5_$i.err
+      cd $R && timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/ab_r5_$i.json 2> $O/ab_r5_$i.err
     done
     cd $R && python - <<PY
 import json
@@ -350,18 +350,18 @@ PY
   r5z)         # last call of the round: HEAD as the driver will run it - the whole suite, smoke, a default bench line
     ( time timeout 1500 python -m pytest tests -m gpu -q -x ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; grep -E "passed|failed|rc=|^FAILED|^ERROR" $O/pytest.log | tail -5
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -5 $O/smoke.log
-    ( time timeout 900 python bench.py --steps 5 --warmup 2 ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err
+    ( time timeout 900 python bench.py --steps 5 --warmup 2 --full ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err
     python -c "import json; d=json.loads([l for l in open('$O/bench.json') if l.startswith('{')][-1]); print('default line:', d['dtype'], round(d['value'],3), d['split_ms_per_step'], 'strict', round(d['strict_mode']['value'],3), 'fast', round(d['fast_mode']['value'],3), 'shipped', round(d['shipped_setting']['value'],2), 'clip s', round(d['clip_mode']['ms_per_step']/1e3,2), 'frac', round(d['roofline']['frac'],4), 'issued', round(d['roofline']['frac_issued'],3), 'attn issued', round(d['roofline']['attention']['frac_issued'],3))"
     ;;
   r5n)         # the other BASELINE configs on one GPU at HEAD (bf16x3m): configs[2] at the Sintel size, the 128-frame clip of configs[3], configs[4]'s 576x1024 batch; + one more default line (another box's headline)
     timeout 600 python bench.py --clip-frames 64 --height 256 --width 576 > $O/bench_clip64_sintel.json 2> $O/bench_clip64_sintel.err; cut -c1-900 $O/bench_clip64_sintel.json | python -c "import sys,json; d=json.loads(sys.stdin.read()+'' if False else open('$O/bench_clip64_sintel.json').read()); print('configs[2] 64x256x576:', round(d['value'],3), d['unit'], d['phase_seconds'], d['alignment_vs_scene_truth'])"
     timeout 600 python bench.py --clip-frames 128 > $O/bench_clip128.json 2> $O/bench_clip128.err; python -c "import json; d=json.load(open('$O/bench_clip128.json')); print('configs[3]-size 128x320x512:', round(d['value'],3), d['unit'], d['phase_seconds'])"
     timeout 600 python bench.py --height 576 --width 1024 --batch 4 --dtype f16 --steps 1 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/bench_configs4.json 2> $O/bench_configs4.err; python -c "import json; d=json.load(open('$O/bench_configs4.json')); print('configs[4] 4x16x576x1024 f16:', round(d['value'],3), d['unit'], round(d['ms_per_step']), 'ms per 4-clip step')"
-    ( time timeout 900 python bench.py --steps 5 --warmup 2 ) > $O/bench_default.json 2> $O/bench_default.err; python -c "import json; d=json.loads([l for l in open('$O/bench_default.json') if l.startswith('{')][-1]); print('default line:', round(d['value'],3), d['split_ms_per_step'], 'strict', round(d['strict_mode']['value'],3), 'fast', round(d['fast_mode']['value'],3), 'shipped', round(d['shipped_setting']['value'],2), 'clip s', round(d['clip_mode']['ms_per_step']/1e3,2), 'traffic GB', round((d['roofline']['traffic'] or 0)/1e9,1), d['roofline']['traffic_by_kernel_class_gb'])"
+    ( time timeout 900 python bench.py --steps 5 --warmup 2 --full ) > $O/bench_default.json 2> $O/bench_default.err; python -c "import json; d=json.loads([l for l in open('$O/bench_default.json') if l.startswith('{')][-1]); print('default line:', round(d['value'],3), d['split_ms_per_step'], 'strict', round(d['strict_mode']['value'],3), 'fast', round(d['fast_mode']['value'],3), 'shipped', round(d['shipped_setting']['value'],2), 'clip s', round(d['clip_mode']['ms_per_step']/1e3,2), 'traffic GB', round((d['roofline']['traffic'] or 0)/1e9,1), d['roofline']['traffic_by_kernel_class_gb'])"
     ;;
   r5m)         # r5l's A/B again with the switch actually reaching the library (bench only + the column-fastest PMC passes)
     run_bench() {   # name, extra env
-      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-shipped-setting > $O/bench_$1.json 2> $O/bench_$1.err
+      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg --no-shipped-setting > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -387,7 +387,7 @@ PY
   r5l)         # grouped tile order (GROUP_M = 4) against the column-fastest order of rounds 1-4 (GEO4D_DEBUG_ABLATE=17), same library, same box: bits? frames/s? L2-miss traffic?
     ( timeout 600 python -m pytest tests/test_f16x2_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_presplit_gpu.py -m gpu -q ) > $O/pytest.log 2>&1; tail -3 $O/pytest.log; grep -E "^FAILED|^ERROR" $O/pytest.log | head
     run_bench() {   # name, extra env
-      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -416,7 +416,7 @@ PY
     ;;
   r5k)         # same-box A/B of A64: the pre-A64 library + its table (build_b/, built in the container from commit 0f96093) against HEAD, interleaved
     run_bench() {   # name, extra env
-      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $2 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype bf16x3m --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -441,7 +441,7 @@ PY
     cp geo4d_amd/tuning/gfx950.json $O/gfx950_before.json
     timeout 900 python tools/tune_gemm.py $O/gfx950.json --keep --drop-prefix=4/ bf16x3m > $O/tune.log 2>&1; show $O/tune.log | tail -3
     run_bench() {   # name, dtype, extra env
-      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -472,7 +472,7 @@ PY
     cp geo4d_amd/tuning/gfx950.json $O/gfx950_before.json
     timeout 900 python tools/tune_gemm.py $O/gfx950.json --keep --drop-prefix=4/ bf16x3m > $O/tune.log 2>&1; show $O/tune.log | tail -3
     run_bench() {   # name, dtype, extra env
-      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -492,7 +492,7 @@ PY
     ( timeout 600 python -m pytest tests/test_gn_small_gpu.py tests/test_kernels_gpu.py tests/test_bf16x3_gpu.py tests/test_parity_gpu.py -m gpu -q ) > $O/pytest.log 2>&1; tail -4 $O/pytest.log; grep -E "^FAILED|^ERROR" $O/pytest.log | head
     timeout 200 python tools/norm_bench.py --dtype f32 > $O/norm.log 2>&1; show $O/norm.log | tail -24
     run_bench() {   # name, dtype, extra env
-      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $2 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -510,7 +510,7 @@ PY
   r5g)         # where does a bf16x3m step go now? (kernel trace of the bench split into phases) + the two-pass test file
     ( timeout 300 python -m pytest tests/test_f16x2_gpu.py -m gpu -q ) > $O/pytest_x2.log 2>&1; tail -3 $O/pytest_x2.log
     cd /tmp
-    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
+    timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg > $O/kt.log 2>&1
     find /tmp/prof/kt -name "*kernel_stats.csv" -exec cp {} $O/kt_kernel_stats.csv \;
     KT=$(find /tmp/prof/kt -name "*kernel_trace.csv" | head -1)
     [ -n "$KT" ] && python $R/tools/prof_phases.py $KT 40 > $O/phases.md 2>&1
@@ -525,7 +525,7 @@ PY
     ( time timeout 1500 python -m pytest tests -m gpu -q -x --durations=12 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|^FAILED|assert" $O/pytest.log | tail -12; grep -E "^[0-9.]+s " $O/pytest.log | head -12
     timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -5 $O/smoke.log
-    ( time timeout 900 python bench.py --steps 3 --warmup 1 ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+    ( time timeout 900 python bench.py --steps 3 --warmup 1 --full ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
     python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench.json") if l.startswith("{")][-1])
@@ -544,7 +544,7 @@ PY
     ( time timeout 900 python -m pytest tests/test_fullsize_gpu.py tests/test_parity_gpu.py -m gpu -q -x -s -k "vs_reference or 50_step or multi_step or window_end_to_end" ) > $O/pytest_fullsize.log 2>&1; echo "pytest rc=$?" >> $O/pytest_fullsize.log
     grep -E "\[full|\[3-step|\[50-step|rel|passed|failed|rc=|Error|assert" $O/pytest_fullsize.log | cut -c1-700 | tail -16
     run_bench() {   # name, dtype, extra env
-      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --dtype $2 --no-cpu-baseline --no-fast-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $2 --no-cpu-baseline --no-fast-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -568,7 +568,7 @@ PY
     ( time timeout 900 python -m pytest tests/test_fullsize_gpu.py -m gpu -q -x -s -k "vs_reference or 50_step or multi_step" ) > $O/pytest_fullsize.log 2>&1; echo "pytest rc=$?" >> $O/pytest_fullsize.log
     grep -E "\[full|\[3-step|\[50-step|passed|failed|rc=|Error|assert" $O/pytest_fullsize.log | cut -c1-700 | tail -14
     run_bench() {   # name, dtype, extra env
-      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --dtype $2 --no-cpu-baseline --no-fast-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
+      env $3 timeout 400 python bench.py --steps 3 --warmup 1 --full --dtype $2 --no-cpu-baseline --no-fast-mode --no-clip-leg > $O/bench_$1.json 2> $O/bench_$1.err
       python - <<PY
 import json
 try:
@@ -589,12 +589,12 @@ PY
     timeout 1200 python tools/gemm_bench.py --dtype f16x2 --iters 10 --explore-all > $O/census_x2_all.log 2>&1; show $O/census_x2_all.log | grep -v "^    table" | tail -64
     ;;
   r4a)         # first call of round 4: where do the linears stand (all generations, vendor), is the table mis-tuned, what does a re-tune buy
-    timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/bench_old_table.json 2> $O/bench_old.err; cut -c1-400 $O/bench_old_table.json
+    timeout 400 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-fast-mode > $O/bench_old_table.json 2> $O/bench_old.err; cut -c1-400 $O/bench_old_table.json
     TAG=$TAG bash $0 census bf16x3
     TAG=$TAG bash $0 census bf16
     TAG=$TAG bash $0 retune bf16x3 bf16
     cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_new_table.json 2> $O/bench_new.err; cut -c1-400 $O/bench_new_table.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_new_table.json 2> $O/bench_new.err; cut -c1-400 $O/bench_new_table.json
     timeout 300 python tools/attn_bench.py bf16 bf16x3 > $O/attn.log 2>&1; show $O/attn.log | grep "v1\|v3" | grep "2560\|forward"
     timeout 200 python tools/norm_bench.py --dtype f32 > $O/norm.log 2>&1; show $O/norm.log | tail -20
     ;;
@@ -605,12 +605,12 @@ PY
     timeout 200 python tools/norm_bench.py --dtype f32 > $O/norm.log 2>&1; show $O/norm.log | grep unet
     TAG=$TAG bash $0 retune bf16x3
     cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-600 $O/bench.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-600 $O/bench.json
     ;;
   r4c)         # re-entry call: the groundwork commit on the GPU (tests of the touched kernels), census with every candidate + vendor bound, attention / norm benches, bench line
     ( time timeout 700 python -m pytest tests/test_presplit_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_kernels_gpu.py tests/test_bf16x3_gpu.py -m gpu -q -x --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -8
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-900 $O/bench.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-900 $O/bench.json
     TAG=$TAG bash $0 census bf16x3
     timeout 300 python tools/attn_bench.py bf16 bf16x3 > $O/attn.log 2>&1; show $O/attn.log | grep "2560\|forward"
     timeout 200 python tools/norm_bench.py --dtype f32 > $O/norm.log 2>&1; show $O/norm.log | grep "unet\|L[012]"
@@ -619,36 +619,36 @@ PY
     ( time timeout 600 python -m pytest tests/test_presplit_gpu.py tests/test_kernels_gpu.py tests/test_bf16x3_gpu.py -m gpu -q -x -k "attention or presplit or split" --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error|variant" $O/pytest.log | tail -12
     timeout 300 python tools/attn_bench.py bf16 bf16x3 > $O/attn.log 2>&1; show $O/attn.log | grep "2560\|forward\| 640"
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-1200 $O/bench.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-1200 $O/bench.json
     ;;
   r4e)         # after the o_split fixes + variant 4 as the attention default: the touched tests, then the bench line
     ( time timeout 900 python -m pytest tests/test_presplit_gpu.py tests/test_kernels_gpu.py tests/test_bf16x3_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py -m gpu -q -x --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error|variant" $O/pytest.log | tail -12
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-1500 $O/bench.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-1500 $O/bench.json
     ;;
   r4f)         # paired 128-byte epilogue stores (second / third generation): bit-identical? fixed cost per launch? census + bench
     ( time timeout 900 python -m pytest tests/test_presplit_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_bf16x3_gpu.py -m gpu -q -x --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -6
     timeout 300 python tools/gemm_kscan.py > $O/kscan.log 2>&1; show $O/kscan.log 230
-    timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
+    timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
     ;;
   r4g)         # the table re-measured with the round-4 epilogue (fixed cost per tile 30 -> ~5 us on the phased tiles), then the bench line on it
     TAG=$TAG bash $0 retune bf16x3 bf16
     cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
     grep -c "" $O/gfx950.json.log; awk '{print $3}' $O/gfx950.json.log | sort | uniq -c | sort -rn | head -12
-    timeout 500 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
+    timeout 500 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
     ;;
   r4h)         # 16-bit-row fast paths: the GEMM tests of every generation / dtype, bf16 table re-measured, bench line
     ( time timeout 900 python -m pytest tests/test_presplit_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_bf16x3_gpu.py tests/test_kernels_gpu.py -m gpu -q -x --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -6
     TAG=$TAG bash $0 retune bf16
     cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-    timeout 500 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
+    timeout 500 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
     ;;
   r4i)         # per-row bias in the fast epilogue (V^T projections): tests, bench; the configs[2] clip line (64 frames -> 14 windows + alignment) on one GPU
     ( time timeout 900 python -m pytest tests/test_presplit_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_bf16x3_gpu.py tests/test_kernels_gpu.py -m gpu -q -x --durations=5 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -6
-    timeout 500 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
+    timeout 500 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
     timeout 600 python bench.py --clip-frames 64 --no-cpu-baseline > $O/clip64.json 2> $O/clip64.err; tail -2 $O/clip64.err; cut -c1-2000 $O/clip64.json
     ;;
   r4j)         # row-bias table + per-row bias in the fast epilogue: tests, table re-measured (both modes), bench, the 64-frame clip line
@@ -656,14 +656,14 @@ PY
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -6
     TAG=$TAG bash $0 retune bf16x3 bf16
     cp $O/gfx950.json geo4d_amd/tuning/gfx950.json
-    timeout 500 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
+    timeout 500 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-420 $O/bench.json
     timeout 600 python bench.py --clip-frames 64 --no-cpu-baseline > $O/clip64.json 2> $O/clip64.err; tail -2 $O/clip64.err; cut -c1-2400 $O/clip64.json
     ;;
   r4k)         # GroupNorm statistics from the fast epilogue (GEO4D_GN_FUSED=1): correct? faster? (A/B on one box, default stays off)
     ( time timeout 600 python -m pytest tests/test_bf16x3_gpu.py tests/test_kernels_gpu.py tests/test_gemm_v2_gpu.py tests/test_gemm_v3_gpu.py tests/test_presplit_gpu.py -m gpu -q -x -k "statistics or groupnorm or gemm or conv or linear or epilogue" --durations=3 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
     grep -E "passed|failed|rc=|Error|error" $O/pytest.log | tail -6
     for f in 0 1 0 1; do
-      GEO4D_GN_FUSED=$f timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode > $O/bench_fused$f.json 2> $O/bench_fused$f.err
+      GEO4D_GN_FUSED=$f timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode > $O/bench_fused$f.json 2> $O/bench_fused$f.err
       python -c "import json; d=json.load(open('$O/bench_fused$f.json')); print('GN_FUSED=$f', round(d['value'],3), {k:round(v) for k,v in d['split_ms_per_step'].items()})" || tail -3 $O/bench_fused$f.err
     done
     ;;

@@ -13,12 +13,12 @@ export TMPDIR=/tmp
 ( time timeout 1200 python -m pytest tests -m gpu -q -s --durations=10 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 grep -E "passed|failed|rc=|^FAILED|^ERROR" $O/pytest.log | tail -6
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -5 $O/smoke.log
-( time timeout 900 python bench.py --steps 5 --warmup 2 ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cut -c1-400 $O/bench.json
+( time timeout 900 python bench.py --steps 5 --warmup 2 --full ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cut -c1-400 $O/bench.json
 # same-box A/B against the round-5 end state (gpurun_ab_r5/ = `git archive 1f11639`, library built in the container: it travels with the snapshot)
 if [ -f $R/gpurun_ab_r5/geo4d_amd/csrc/libgeo4d_hip.so ]; then
   for i in 1 2; do
     cd $R/gpurun_ab_r5 && timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/ab_r5_$i.json 2> $O/ab_r5_$i.err
-    cd $R && timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/ab_r6_$i.json 2> $O/ab_r6_$i.err
+    cd $R && timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-mode --no-strict-mode --no-clip-leg > $O/ab_r6_$i.json 2> $O/ab_r6_$i.err
   done
   cd $R && python - <<PY
 import json
@@ -30,7 +30,7 @@ for n in ("ab_r5_1", "ab_r6_1", "ab_r5_2", "ab_r6_2"):
 PY
 fi
 cd /tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --dtype $MODE --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg --no-batched-windows > $O/kt.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof/kt -o kt -- python $R/bench.py --steps 1 --warmup 1 --full --dtype $MODE --no-cpu-baseline --no-fast-mode --no-strict-mode --no-shipped-setting --no-clip-leg --no-batched-windows > $O/kt.log 2>&1
 find /tmp/prof/kt -name "*kernel_stats.csv" -exec cp {} $O/kt_kernel_stats.csv \;
 KT=$(find /tmp/prof/kt -name "*kernel_trace.csv" | head -1)
 [ -n "$KT" ] && python $R/tools/prof_phases.py $KT 30 > $O/phases.md 2>&1
