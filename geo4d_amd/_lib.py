@@ -148,6 +148,13 @@ SIGNATURES = {
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_lad_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_float, C.c_float,
                                   C.c_void_p, C.c_void_p]),
+    "geo4d_bicubic_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "geo4d_masked_select_workspace": (C.c_size_t, [C.c_long]),
+    "geo4d_masked_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_depth_metrics_workspace": (C.c_size_t, [C.c_long]),
+    "geo4d_depth_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_last_error": (C.c_char_p, []),
     "geo4d_align_refresh": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),
     "geo4d_align_small_grads": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),

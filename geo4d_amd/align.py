@@ -85,9 +85,9 @@ def rotmat_to_quat(R):
     return (q / q.norm()).float()
 
 
-def rigid_points_registration(x, y, weights):
+def rigid_points_registration(x, y, weights, fp64=False):
     """(s, R, T) minimising sum w |s R x + T - y|^2 (init_im_poses.py:797-800 -> roma.rigid_points_registration(compute_scaling=True)):
-    weighted Umeyama, sums in fp64."""
+    weighted Umeyama, sums in fp64; the result is cast to fp32 unless fp64 (geo4d_amd.evaluation's sim(3) trajectory alignment)."""
     x, y, w = x.reshape(-1, 3).double(), y.reshape(-1, 3).double(), weights.reshape(-1).double()
     w = w / w.sum()
     xm, ym = (w[:, None] * x).sum(0), (w[:, None] * y).sum(0)
@@ -102,7 +102,8 @@ def rigid_points_registration(x, y, weights):
     D = torch.diag(torch.stack([torch.ones(()).double(), torch.ones(()).double(), d]))
     R = (U @ D @ Vt).to(x.device)
     s = (S * torch.diagonal(D)).sum().to(x.device) / (w * (xc * xc).sum(-1)).sum()
-    return s.float(), R.float(), (ym - s * (R @ xm)).float()
+    T = ym - s * (R @ xm)
+    return (s, R, T) if fp64 else (s.float(), R.float(), T.float())
 
 
 def estimate_focal_weiszfeld(rays, pp=None, iters=10):
@@ -131,11 +132,18 @@ def align_origin_and_rpe(est, ref):
     est, ref [S, 4, 4] float64 ndarrays -> (P [4, 4], rmse in degrees). Pinned on closed-form cases (tests/test_align_closed_form_cpu.py)."""
     Pm = ref[0] @ np.linalg.inv(est[0])
     al = Pm[None] @ est
-    ang = []
-    for k in range(len(est) - 1):
-        E = np.linalg.inv(np.linalg.inv(ref[k]) @ ref[k + 1]) @ (np.linalg.inv(al[k]) @ al[k + 1])
-        ang.append(np.degrees(np.arccos(np.clip((np.trace(E[:3, :3]) - 1) / 2, -1.0, 1.0))))
+    ang = [rotation_angle_deg(E) for E in relative_pose_errors(al, ref)]
     return Pm, float(np.sqrt(np.mean(np.square(ang))))
+
+
+def relative_pose_errors(est, ref):
+    """evo's RPE error matrices for delta = 1 frame, all pairs: E_k = (Q_k^-1 Q_{k+1})^-1 (P_k^-1 P_{k+1}), P = est, Q = ref [S, 4, 4]."""
+    return [np.linalg.inv(np.linalg.inv(ref[k]) @ ref[k + 1]) @ (np.linalg.inv(est[k]) @ est[k + 1]) for k in range(len(est) - 1)]
+
+
+def rotation_angle_deg(E):
+    """Rotation angle of the 3 x 3 block of E in degrees (evo's rotation_angle_deg pose relation)."""
+    return np.degrees(np.arccos(np.clip((np.trace(E[:3, :3]) - 1) / 2, -1.0, 1.0)))
 
 
 def lr_at(t, schedule, lr_base, lr_min):

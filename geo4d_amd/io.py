@@ -9,6 +9,10 @@ Writers follow ``dust3r/cloud_opt/base_opt_group.py:390-464`` and ``dust3r/utils
 format is text (TUM trajectories ``t x y z qw qx qy qz``, ``pred_focal.txt`` / ``pred_intrinsics.txt`` with ``%.6f``,
 ``frame_%04d.npy``, ``conf_%d.npy``) so that ``viser/visualizer.py`` and the evaluation scripts read them unchanged; the colour
 depth previews use matplotlib's 'inferno' map over the 2-98 percentile range of inverse depth like ``vis_sequence_depth``.
+
+Ground-truth readers for the evaluation (geo4d_amd/evaluation.py) follow ``lvdm/data/eval_dataset_geo4d.py`` (Sintel ``.dpt``, Bonn and
+KITTI 16-bit PNGs) and ``dust3r/utils/vo_eval.py`` (Sintel ``.cam`` sequences and TUM text trajectories, returned as the TUM-style
+``(poses x y z qw qx qy qz, timestamps)`` pairs that ``eval_metrics`` takes).
 """
 import os
 
@@ -106,6 +110,97 @@ def load_video_batch(filepath_list, frame_stride, video_size=(256, 256), video_f
 
 
 # ---- writing ------------------------------------------------------------------------------------------------------------------
+# ---- ground truth for evaluation (lvdm/data/eval_dataset_geo4d.py:36-69, dust3r/utils/vo_eval.py:18-140) ---------------------------
+SINTEL_TAG = 202021.25
+
+
+def depth_read_sintel(filename):
+    """Sintel .dpt: float32 tag, int32 width, int32 height, then height x width float32 depths."""
+    with open(filename, "rb") as f:
+        check = np.fromfile(f, dtype=np.float32, count=1)[0]
+        assert check == SINTEL_TAG, f"depth_read_sintel: wrong tag {check} in {filename} (should be {SINTEL_TAG}); big-endian file?"
+        width = np.fromfile(f, dtype=np.int32, count=1)[0]
+        height = np.fromfile(f, dtype=np.int32, count=1)[0]
+        assert width > 0 and height > 0 and 1 < width * height < 100000000, f"depth_read_sintel: bad size {width} x {height}"
+        return np.fromfile(f, dtype=np.float32, count=-1).reshape((height, width))
+
+
+def _read_png16(filename):
+    from PIL import Image
+    png = np.array(Image.open(filename), dtype=np.int64)
+    assert png.max() > 255, f"{filename}: not a 16-bit depth map"
+    return png
+
+
+def depth_read_bonn(filename):
+    """Bonn RGB-D 16-bit PNG: depth = value / 5000 (float64), missing (0) -> -1."""
+    png = _read_png16(filename)
+    depth = png.astype(np.float64) / 5000.0
+    depth[png == 0] = -1.0
+    return depth
+
+
+def depth_read_kitti(filename):
+    """KITTI 16-bit PNG: depth = value / 256 (float64), missing (0) -> -1."""
+    png = _read_png16(filename)
+    depth = png.astype(np.float64) / 256.0
+    depth[png == 0] = -1.0
+    return depth
+
+
+def sintel_cam_read(filename):
+    """Sintel .cam -> (M [3, 3] intrinsics, N [3, 4] world-to-camera extrinsics), float64."""
+    with open(filename, "rb") as f:
+        check = np.fromfile(f, dtype=np.float32, count=1)[0]
+        assert check == SINTEL_TAG, f"sintel_cam_read: wrong tag {check} in {filename} (should be {SINTEL_TAG}); big-endian file?"
+        M = np.fromfile(f, dtype=np.float64, count=9).reshape((3, 3))
+        N = np.fromfile(f, dtype=np.float64, count=12).reshape((3, 4))
+    return M, N
+
+
+def load_sintel_traj(cam_dir):
+    """Every .cam of a Sintel sequence directory (sorted by name) -> (poses [N, 7] camera-to-world x y z qw qx qy qz with the positions
+    centred on their mean, timestamps [N, 1] = the number after the last '_' of each file name)."""
+    from scipy.spatial.transform import Rotation
+    files = [os.path.join(cam_dir, x) for x in sorted(os.listdir(cam_dir)) if x.endswith(".cam")]
+    stamps = [float(os.path.basename(x)[:-4].split("_")[-1]) for x in files]
+    poses = []
+    for fn in files:
+        c2w = np.linalg.inv(np.concatenate([sintel_cam_read(fn)[1], [[0, 0, 0, 1]]], 0))
+        x, y, z, w = Rotation.from_matrix(c2w[:3, :3]).as_quat()
+        poses.append(np.concatenate([c2w[:3, -1], [w, x, y, z]]))
+    poses = np.stack(poses, 0)
+    poses[:, :3] -= poses[:, :3].mean(0, keepdims=True)
+    return poses, np.stack(stamps, 0)[:, None]
+
+
+def load_tum_traj(path):
+    """TUM trajectory text (`timestamp x y z qx qy qz qw` per line, '#' comments) -> (poses [N, 7] x y z qw qx qy qz, timestamps [N])."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line and not line.startswith("#"):
+                rows.append([float(v) for v in line.replace(",", " ").split()])
+    mat = np.asarray(rows, dtype=np.float64)
+    assert mat.ndim == 2 and mat.shape[1] == 8, f"{path}: not a TUM trajectory (8 columns)"
+    return np.column_stack((mat[:, 1:4], np.roll(mat[:, 4:], 1, axis=1))), mat[:, 0]
+
+
+def load_traj(path, traj_format="sintel", skip=0, stride=1, num_frames=None):
+    """vo_eval.py load_traj for the 'sintel' (a directory of .cam files) and 'tum' / 'tartanair' (a TUM text file) formats."""
+    if traj_format == "sintel":
+        poses, stamps = load_sintel_traj(path)
+    elif traj_format in ("tum", "tartanair"):
+        poses, stamps = load_tum_traj(path)
+    else:
+        raise NotImplementedError(f"load_traj: format {traj_format!r}")
+    poses, stamps = poses[skip::stride], stamps[skip::stride]
+    if num_frames is not None:
+        poses, stamps = poses[:num_frames], stamps[:num_frames]
+    return poses, stamps
+
+
 def c2w_to_tumpose(c2w):
     """base_opt_group.py:29-44: camera-to-world 4x4 -> (x y z qw qx qy qz)."""
     from scipy.spatial.transform import Rotation

@@ -819,3 +819,69 @@ def plucker_cameras(raymap, crossmap):
     _lib.check(lib.geo4d_plucker_cameras(raymap.data_ptr(), crossmap.data_ptr(), raymap.stride(1), raymap.stride(2), T, H, W,
                                          ws.data_ptr(), need, out.data_ptr(), _stream()), "geo4d_plucker_cameras")
     return out
+
+
+def bicubic_resize(x, size, out=None):
+    """x fp32 [T, h, w] -> [T, OH, OW] = F.interpolate(x[None], size, mode="bicubic", align_corners=False)[0] (torchvision Resize(BICUBIC)
+    on a float tensor under the reference's pinned torch 2.0 stack: no antialias, no output clamp)."""
+    lib = _lib.load()
+    _dev(x, "x")
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous(), (x.dtype, x.shape)
+    T, h, w = x.shape
+    OH, OW = int(size[0]), int(size[1])
+    out = torch.empty((T, OH, OW), device=x.device, dtype=torch.float32) if out is None else out
+    assert out.shape == (T, OH, OW) and out.dtype == torch.float32 and out.is_contiguous()
+    _lib.check(lib.geo4d_bicubic_resize(x.data_ptr(), out.data_ptr(), T, h, w, OH, OW, _stream()), "geo4d_bicubic_resize")
+    return out
+
+
+def _mask_ptr(mask, n, device):
+    if mask is None:
+        return None, None
+    assert mask.numel() == n and mask.device == device, "mask must match the depth maps"
+    m = mask.reshape(-1).to(torch.bool).contiguous()
+    return m, m.data_ptr()
+
+
+def masked_select(pred, gt, *, max_depth=None, mask=None, pre_clip_min=None, pre_clip_max=None):
+    """(clamp(pred, pre_clip_min, pre_clip_max)[v], gt[v], count) with v = (gt > 0) & (gt < max_depth) & mask in index order
+    (= torch boolean indexing). The two outputs are n-element buffers of which the first `count` (a device int64 [1]) are written."""
+    lib = _lib.load()
+    _dev(pred, "pred"); _dev(gt, "gt")
+    assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and pred.is_contiguous() and gt.is_contiguous()
+    n = gt.numel()
+    assert pred.numel() == n and n > 0
+    m, mp = _mask_ptr(mask, n, gt.device)
+    pv, gv = torch.empty(n, device=gt.device, dtype=torch.float32), torch.empty(n, device=gt.device, dtype=torch.float32)
+    count = torch.empty(1, device=gt.device, dtype=torch.int64)
+    need = lib.geo4d_masked_select_workspace(n)
+    ws = torch.empty((need + 3) // 4, device=gt.device, dtype=torch.int32)
+    inf = float("inf")
+    _lib.check(lib.geo4d_masked_select(pred.data_ptr(), gt.data_ptr(), n, inf if max_depth is None else float(max_depth), mp,
+                                       -inf if pre_clip_min is None else float(pre_clip_min), inf if pre_clip_max is None else float(pre_clip_max),
+                                       pv.data_ptr(), gv.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _stream()), "geo4d_masked_select")
+    return pv, gv, count
+
+
+def depth_metrics(pred, gt, st, *, max_depth=None, custom_mask=None, pre_clip_min=None, pre_clip_max=None, post_clip_min=None,
+                  post_clip_max=None, aligned=False):
+    """One pass of depth_evaluation's metrics (depth_eval.py:283-335) with (s, t) = st (fp32 device [2]): returns (sums fp64 [8] = sum |a-g|/g,
+    sum (a-g)^2/g, sum (a-g)^2, sum (log a' - log g)^2, #delta < 1.25, < 1.25^2, < 1.25^3, #pixels; error map [n]; s * pred + t [n] or None)."""
+    lib = _lib.load()
+    _dev(pred, "pred"); _dev(gt, "gt"); _dev(st, "st")
+    assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and pred.is_contiguous() and gt.is_contiguous()
+    assert st.dtype == torch.float32 and st.numel() == 2 and st.is_contiguous()
+    n = gt.numel()
+    assert pred.numel() == n and n > 0
+    m, mp = _mask_ptr(custom_mask, n, gt.device)
+    sums = torch.empty(8, device=gt.device, dtype=torch.float64)
+    err = torch.empty(n, device=gt.device, dtype=torch.float32)
+    al = torch.empty(n, device=gt.device, dtype=torch.float32) if aligned else None
+    need = lib.geo4d_depth_metrics_workspace(n)
+    ws = torch.empty((need + 7) // 8, device=gt.device, dtype=torch.float64)
+    inf = float("inf")
+    clip = lambda v, d: d if v is None else float(v)
+    _lib.check(lib.geo4d_depth_metrics(pred.data_ptr(), gt.data_ptr(), n, clip(max_depth, inf), mp, st.data_ptr(), clip(pre_clip_min, -inf),
+                                       clip(pre_clip_max, inf), clip(post_clip_min, -inf), clip(post_clip_max, inf), sums.data_ptr(),
+                                       err.data_ptr(), _ptr(al), ws.data_ptr(), need, _stream()), "geo4d_depth_metrics")
+    return sums, err, al

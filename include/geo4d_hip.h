@@ -324,6 +324,29 @@ int geo4d_lad_fit(const float* q, const float* target, int G, long n, const unsi
 int geo4d_lad_delta(const float* q, const float* target, const float* conf, const float* st, int G, long n, float conf_thr,
                     float conf_clamp, float q_thr, unsigned* counts, void* stream);
 
+/* Video-depth evaluation against ground truth (dust3r/depth_eval.py depth_evaluation :147-355 as scripts/evaluation/infer_geo4d.py:514-545
+ * calls it; geo4d_amd/evaluation.py). All arrays fp32 on the device, n elements of the flattened [T][H][W] sequence, n < 2^32.
+ *   geo4d_bicubic_resize: y [T][OH][OW] = torch.nn.functional.interpolate(x [T][h][w], (OH, OW), "bicubic", align_corners=False) — what
+ *     torchvision.transforms.Resize(BICUBIC) does to a float tensor under the reference's torch 2.0 / torchvision 0.15 (antialias off):
+ *     a = -0.75, border-clamped taps, no output clamp.
+ *   geo4d_masked_select: (pred_out, gt_out)[0, *count) = (clamp(pred, pre_min, pre_max), gt)[valid], valid = gt > 0 && gt < max_depth
+ *     (max_depth = +INFINITY: no upper bound) && (mask == NULL || mask[i]), in index order (= torch boolean indexing); *count is a device
+ *     int64. pred_out / gt_out hold n floats. workspace: geo4d_masked_select_workspace(n) bytes, 4-byte aligned.
+ *   geo4d_depth_metrics: one pass over the full-size pred / gt with st = (s, t) read from the device. Metric pixels: gt > 0 && gt < max_depth
+ *     && (custom_mask == NULL || custom_mask[i]); a = clamp(s * clamp(pred, pre_min, pre_max) + t, post_min, post_max); sums [8] fp64 =
+ *     {sum |a-g|/g, sum (a-g)^2/g, sum (a-g)^2, sum (log a' - log g)^2, #(delta < 1.25), #(< 1.25^2), #(< 1.25^3), #pixels} with
+ *     a' = max(a, 1e-5) and delta = max(a'/g, g/a') (:283-317). err_map [n] = |s pred + t - g| / g where gt > 0 && gt < max_depth, else 0;
+ *     aligned [n] (may be NULL) = s pred + t (:320-335). Unused clips are -INFINITY / +INFINITY. workspace:
+ *     geo4d_depth_metrics_workspace(n) bytes, 8-byte aligned. Deterministic (fixed-order reductions, no atomics). */
+int geo4d_bicubic_resize(const float* x, float* y, int T, int h, int w, int OH, int OW, void* stream);
+size_t geo4d_masked_select_workspace(long n);
+int geo4d_masked_select(const float* pred, const float* gt, long n, float max_depth, const unsigned char* mask, float pre_min, float pre_max,
+                        float* pred_out, float* gt_out, long* count, void* workspace, size_t workspace_bytes, void* stream);
+size_t geo4d_depth_metrics_workspace(long n);
+int geo4d_depth_metrics(const float* pred, const float* gt, long n, float max_depth, const unsigned char* custom_mask, const float* st,
+                        float pre_min, float pre_max, float post_min, float post_max, double* sums, float* err_map, float* aligned,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 const char* geo4d_last_error(void);
 int geo4d_abi_version(void);
 /* sizeof of the parameter structs as the LIBRARY was compiled (which: 0 conv_gemm, 1 groupnorm, 2 attention, 3 align, 4 align_small; else 0):
