@@ -13,7 +13,7 @@ import torch  # noqa: F401  -- MUST precede loading the .so: PyTorch ships its o
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GEO4D_HIP_LIB: load another build of the SAME library (A/B builds of a kernel: tools/gpu_r2k.sh); the ABI handshake below still applies
 LIB_PATH = os.environ.get("GEO4D_HIP_LIB") or os.path.join(_HERE, "csrc", "libgeo4d_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 F32, BF16, F16, BF16X3, F16X2 = 0, 1, 2, 3, 4
 
@@ -155,6 +155,12 @@ SIGNATURES = {
     "geo4d_depth_metrics_workspace": (C.c_size_t, [C.c_long]),
     "geo4d_depth_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_scene_clean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, C.c_void_p]),
+    "geo4d_scene_points_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "geo4d_scene_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_scene_mesh_faces_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "geo4d_scene_mesh_faces": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_last_error": (C.c_char_p, []),
     "geo4d_align_refresh": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),
     "geo4d_align_small_grads": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),

@@ -146,6 +146,19 @@ def rotation_angle_deg(E):
     return np.degrees(np.arccos(np.clip((np.trace(E[:3, :3]) - 1) / 2, -1.0, 1.0)))
 
 
+def conf_trf(mode):
+    """get_conf_trf (dust3r/cloud_opt/commons.py:70-81)."""
+    if mode == "log":
+        return torch.log
+    if mode == "sqrt":
+        return torch.sqrt
+    if mode == "m1":
+        return lambda x: x - 1
+    if mode in ("id", "none"):
+        return lambda x: x
+    raise ValueError(f"bad mode for {mode=}")
+
+
 def lr_at(t, schedule, lr_base, lr_min):
     """commons.py:102-110."""
     if schedule == "cosine":
@@ -225,6 +238,12 @@ class GroupAligner:
             self.P["s_depth"], self.P["t_depth"] = torch.ones(G, 1, device=self.dev), z(G, 1)
         if self.traj is not None:
             self.P["traj_align_poses"] = torch.cat([z(G, 3), torch.ones(G, 1, device=self.dev), z(G, 4)], 1)
+        # scene state the export reads (geo4d_amd/scene_export.py): Geo4D builds its scene with conf='id' and the class defaults
+        # min_conf_thr = 3, thr_for_init_conf = False (base_opt_group.py:104-170); the confidence maps are built on first use
+        self.conf_mode, self.min_conf_thr, self.thr_for_init_conf = "id", 3, False
+        self.imgs = None                         # [n, H, W, 3] RGB in [0, 1] (post_optimization(imgs=...))
+        self._conf_maps = None                   # (im_conf, init_conf_maps)
+        self._all_depthmaps = True               # False while a sharded alignment holds only this rank's images' final depth maps
 
     def _late_keys(self):
         """Parameters that receive gradients only once their term is on (torch.optim.Adam skips them until then)."""
@@ -272,6 +291,81 @@ class GroupAligner:
         d = self.P["im_depthmaps"].exp().unsqueeze(-1)
         cam = torch.cat([d * (grid - self._pp) / f, d], -1)
         return (cam @ R.transpose(1, 2) + t[:, None]).reshape(self.n, self.H, self.W, 3)
+
+    # ---- scene state of the export (base_opt_group.py:160-170, 237-242, 327-331, 353-359, 371-381; optimizer_group.py:213-219) ----
+    def _slot_max_conf(self):
+        """[n, H, W]: per image the maximum of its windows' confidences over every slot that holds it, from zeros, slots in window order
+        (_compute_single_img_conf_group); the un-sharded slot CSR, so every rank builds the same maps."""
+        ptr = self._img_slot_ptr.tolist()
+        idx = self._img_slot_idx.long()
+        out = torch.zeros(self.n, self.H * self.W, device=self.dev)
+        for k in range(max(b - a for a, b in zip(ptr, ptr[1:]))):
+            imgs = [i for i in range(self.n) if ptr[i + 1] - ptr[i] > k]
+            rows = torch.tensor(imgs, dtype=torch.long, device=self.dev)
+            slots = idx[torch.tensor([ptr[i] + k for i in imgs], dtype=torch.long, device=self.dev)]
+            out[rows] = torch.maximum(out[rows], self.conf[slots])
+        return out.reshape(self.n, self.H, self.W)
+
+    def _conf_state(self):
+        if self._conf_maps is None:
+            im_conf = self._slot_max_conf()
+            self._conf_maps = (im_conf, im_conf.clone())
+        return self._conf_maps
+
+    @property
+    def im_conf(self):
+        """[n, H, W] fp32 per-image confidence; clean_pointcloud rewrites it in place."""
+        return self._conf_state()[0]
+
+    @property
+    def init_conf_maps(self):
+        """[n, H, W] fp32 copy of the initial im_conf that clean_pointcloud never touches."""
+        return self._conf_state()[1]
+
+    def get_conf(self, mode=None):
+        return conf_trf(self.conf_mode if mode is None else mode)(self.im_conf)
+
+    def get_init_conf(self, mode=None):
+        return conf_trf(self.conf_mode if mode is None else mode)(self.init_conf_maps)
+
+    def get_masks(self):
+        """[n, H, W] bool: conf > min_conf_thr on init_conf_maps (thr_for_init_conf) or on im_conf. With thr_for_init_conf the masks
+        do not see clean_pointcloud, as in the reference."""
+        return (self.init_conf_maps if self.thr_for_init_conf else self.im_conf) > self.min_conf_thr
+
+    def get_intrinsics(self):
+        """[n, 3, 3]: the focals on the diagonal, principal point (W/2, H/2)."""
+        K = torch.zeros((self.n, 3, 3), device=self.dev)
+        f = self.get_focals().detach().flatten()
+        K[:, 0, 0] = K[:, 1, 1] = f
+        K[:, :2, 2] = self._pp
+        K[:, 2, 2] = 1
+        return K
+
+    def gather_depthmaps(self):
+        """Sharded alignment: every image's depth map from the rank that owns it (a collective: call it on every rank). A no-op without a shard."""
+        if self.shard is not None:
+            self.P["im_depthmaps"].copy_(self.shard.gather_depthmaps(self.P["im_depthmaps"]))
+        self._all_depthmaps = True
+        return self
+
+    def require_all_depthmaps(self, what):
+        if not self._all_depthmaps:
+            raise RuntimeError(f"{what} needs every image's depth map, but this rank of a sharded alignment holds only the images it owns: "
+                               "call scene.gather_depthmaps() on every rank first")
+
+    @torch.no_grad()
+    def clean_pointcloud(self, tol=0.001, bad_conf=0):
+        """clean_depth of get_3D_model_from_scene (base_opt_group.py:371-381, 630-665) on the HIP device: lowers im_conf, in place, where a
+        pixel lies in front of another image's depth and is less confident. Returns self."""
+        from . import scene_export
+        scene_export.check_tol(tol)
+        self.require_all_depthmaps("clean_pointcloud")
+        cams = torch.linalg.inv(self.get_im_poses_matrix())
+        new = scene_export.clean_pointcloud(self.im_conf, self.get_intrinsics(), cams, self.get_depthmaps(), self.get_pts3d(), tol=tol,
+                                            bad_conf=bad_conf)
+        self.im_conf.copy_(new)
+        return self
 
     # ---- one loss / gradient evaluation ---------------------------------------------------------------------------------------
     def _small(self):
@@ -500,6 +594,7 @@ class GroupAligner:
         eps = 1e-8
         if self.shard is not None and self.shard.active:
             use_graph = False                                  # the per-iteration all-reduce runs on RCCL's stream: eager launches
+            self._all_depthmaps = False
         steps = torch.arange(1, niter + 1, dtype=torch.float64)
         lrs = torch.tensor([lr_at(it / niter, schedule, lr, lr_min) for it in range(niter)], dtype=torch.float64)
         table = torch.stack([lrs, 1 - b1 ** steps, (1 - b2 ** steps).sqrt()], 1).float().to(self.dev)            # [niter, 3]
@@ -565,8 +660,7 @@ class GroupAligner:
                 run_phase(start, niter)
         else:                                               # terms already started (a second call continues with them on)
             run_phase(0, niter)
-        if self.shard is not None:                             # every image's depth map from the rank that owns it
-            self.P["im_depthmaps"].copy_(self.shard.gather_depthmaps(self.P["im_depthmaps"]))
+        self.gather_depthmaps()                                # every image's depth map from the rank that owns it
         hist = losses.tolist() if history else None
         return float(losses[-1]) if niter else float("inf"), hist
 
@@ -737,7 +831,7 @@ GroupAligner._init_pnp = _init_pnp
 
 def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03, align=True, intrinsics=None,
                       use_raymap=True, use_inverse_depthmap=True, use_traj=True, pointmap_vae_used=True, depth_traj_start_iter=150,
-                      sharded=None, pose_init="traj"):
+                      sharded=None, pose_init="traj", imgs=None):
     """The consumer of the gathered clip: ``post_optimization`` of scripts/evaluation/test_geo4d.py:30-51 with the pred_list its
     window loop builds (:446-501). ``slices`` / ``maps [n_windows, 11, T, H, W]`` / ``traj [n_windows, T, 4, 4]`` are what
     ``pipeline.run_clip(..., with_cameras=True)`` returns; ``args`` = the config's ``postprocess`` tree (a dict or any object with
@@ -745,7 +839,9 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     the shipped values). ``sharded``: None = shard the optimisation over the ranks of the default process group when there is one
     (align_dist.AlignShard: every rank evaluates its block of windows, one all-reduce per iteration), False = replicate it.
     Returns the optimised ``GroupAligner`` (``get_depthmaps`` / ``get_im_poses_matrix`` / ``get_focals``).
-    ``intrinsics [n_images, 3, 3]`` presets the focals and freezes them (scene.preset_focal(..., requires_grad=False) in the script)."""
+    ``intrinsics [n_images, 3, 3]`` presets the focals and freezes them (scene.preset_focal(..., requires_grad=False) in the script).
+    ``imgs``: the clip's frames in [-1, 1] (``[1, 3, T, H, W]`` as run_clip takes them, ``[3, T, H, W]`` or ``[T, 3, H, W]``) or uint8,
+    kept as ``scene.imgs`` [n, H, W, 3] in [0, 1] (dust3r.utils.image.rgb) for the export (geo4d_amd/scene_export.py)."""
     from .pipeline import postprocess_window
     get = (lambda k, d: args.get(k, d)) if isinstance(args, dict) else (lambda k, d: getattr(args, k, d))
     if args is None:
@@ -772,6 +868,24 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     scene.init_from_group(traj, focal=focal, raymaps=torch.stack([p["raymap"] for p in post]) if use_raymap else None, pose_init=pose_init)
     if intrinsics is not None:
         scene.frozen.add("im_focals")
+    if imgs is not None:
+        scene.imgs = rgb_frames(imgs, scene.n, scene.H, scene.W).to(scene.dev)
     if align:
         scene.compute_global_alignment(niter=get("n_iter", 500), schedule=get("pose_schedule", "linear"), lr=lr)
     return scene
+
+
+def rgb_frames(frames, n, H, W):
+    """dust3r.utils.image.rgb on a clip -> [n, H, W, 3] fp32 in [0, 1]: floats x * 0.5 + 0.5 clipped, uint8 x / 255. Layouts: [1, 3, T, H, W]
+    and [3, T, H, W] (load_video_batch / run_clip), [T, 3, H, W] (rgb's own), [T, H, W, 3]."""
+    x = torch.as_tensor(frames)
+    if x.dim() == 5 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() == 4 and x.shape[1] == 3 and x.shape[-1] != 3:
+        x = x.permute(0, 2, 3, 1)
+    elif x.dim() == 4 and x.shape[0] == 3 and x.shape[-1] != 3:
+        x = x.permute(1, 2, 3, 0)
+    if tuple(x.shape) != (n, H, W, 3):
+        raise ValueError(f"imgs: expected {n} frames of {H} x {W} RGB, got shape {tuple(torch.as_tensor(frames).shape)}")
+    x = x.float() / 255 if x.dtype == torch.uint8 else (x.float() * 0.5 + 0.5).clip(0, 1)
+    return x.contiguous()

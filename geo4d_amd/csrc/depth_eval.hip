@@ -12,6 +12,7 @@
 // into FMAs is switched off for this file so each product and sum rounds where torch's does.
 #include <cmath>
 #include "common.h"
+#include "compact.h"
 #include "geo4d_hip.h"
 
 #pragma clang fp contract(off)
@@ -92,34 +93,6 @@ __global__ __launch_bounds__(256) void select_count_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_count[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// exclusive scan of block_count in place (one workgroup of 1024 lanes walking the array), total -> *count
-__global__ __launch_bounds__(1024) void select_scan_kernel(unsigned* __restrict__ block_count, long nblocks, long* __restrict__ count) {
-    __shared__ unsigned wsum[16];
-    __shared__ unsigned long long carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (long b0 = 0; b0 < nblocks; b0 += 1024) {
-        const long b = b0 + tid;
-        const unsigned v = b < nblocks ? block_count[b] : 0u;
-        unsigned incl = v;                                          // inclusive scan inside the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned before = 0;
-        for (int k = 0; k < wave; ++k) before += wsum[k];
-        const unsigned long long carry = carry_s;
-        if (b < nblocks) block_count[b] = (unsigned)(carry + before + incl - v);
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) *count = (long)carry_s;
 }
 
 __global__ __launch_bounds__(256) void select_scatter_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -261,7 +234,7 @@ extern "C" int geo4d_masked_select(const float* pred, const float* gt, long n, f
     unsigned* blk = (unsigned*)workspace;
     hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, gt, mask, n, max_depth, bounded, blk);
     GEO4D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(1024), 0, s, blk, nblocks, count);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, blk, nblocks, count);
     GEO4D_CHECK_LAUNCH();
     hipLaunchKernelGGL(select_scatter_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, pred, gt, mask, n, max_depth, bounded, pre_min, pre_max, blk,
                        pred_out, gt_out);

@@ -274,7 +274,8 @@ OPENGL = np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]], dt
 
 
 def _glb_bytes(meshes, transform):
-    """Binary glTF 2.0 with one node per primitive. meshes: list of dict(mode, positions f32 [n, 3], colors u8 [n, 4] or None).
+    """Binary glTF 2.0 with one node per primitive. meshes: list of dict(mode, positions f32 [n, 3], colors u8 [n, 4] or None,
+    indices [f, 3] or None: uint32 vertex ids of an indexed primitive).
     `transform` (4x4) is applied to every node, as trimesh.Scene.apply_transform does."""
     import json
     import struct
@@ -298,7 +299,10 @@ def _glb_bytes(meshes, transform):
         attrs = {"POSITION": add(pos, 34962, 5126, "VEC3", minmax=True)}
         if m.get("colors") is not None:
             attrs["COLOR_0"] = add(np.ascontiguousarray(m["colors"], dtype=np.uint8), 34962, 5121, "VEC4", normalized=True)
-        gl_meshes.append({"primitives": [{"attributes": attrs, "mode": m["mode"]}]})
+        prim = {"attributes": attrs, "mode": m["mode"]}
+        if m.get("indices") is not None:
+            prim["indices"] = add(np.ascontiguousarray(m["indices"], dtype=np.uint32).reshape(-1), 34963, 5125, "SCALAR")
+        gl_meshes.append({"primitives": [prim]})
         nodes.append({"mesh": len(gl_meshes) - 1, "matrix": [float(v) for v in np.asarray(transform, np.float64).T.reshape(-1)]})   # column-major
     doc = {"asset": {"version": "2.0", "generator": "geo4d_amd.io"}, "scene": 0, "scenes": [{"nodes": list(range(len(nodes)))}],
            "nodes": nodes, "meshes": gl_meshes, "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(buf)}]}
@@ -329,7 +333,8 @@ def save_glb(path, imgs, pts3d, masks, focals, cams2world, cam_size=0.05, show_c
     """convert_scene_output_to_glb(as_pointcloud=True) without trimesh: the masked points of every image with their colours as ONE
     POINTS primitive, one LINES primitive per camera (pyramid edges, viridis-like colour ramp unless `cam_color` [n][3] in 0-255), and
     the reference's scene transform inv(cams2world[0] @ OPENGL @ rot_y(180 deg)) on every node.
-    imgs [n, H, W, 3] in [0, 1]; pts3d [n, H, W, 3]; masks [n, H, W] bool; focals [n]; cams2world [n, 4, 4]. Returns `path`."""
+    imgs [n, H, W, 3] in [0, 1]; pts3d [n, H, W, 3]; masks [n, H, W] bool; focals [n]; cams2world [n, 4, 4]. Returns `path`.
+    geo4d_amd.scene_export.get_3D_model_from_scene writes the same file from points compacted on the device."""
     to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
     imgs, pts3d, masks, focals, cams2world = (to_np(v) for v in (imgs, pts3d, masks, focals, cams2world))
     assert len(pts3d) == len(masks) <= len(imgs) <= len(cams2world) == len(np.reshape(focals, -1))
@@ -337,10 +342,29 @@ def save_glb(path, imgs, pts3d, masks, focals, cams2world, cam_size=0.05, show_c
     pts = np.concatenate([p[m] for p, m in zip(pts3d, masks)]).reshape(-1, 3)
     col = np.concatenate([im[m] for im, m in zip(imgs, masks)]).reshape(-1, 3)
     col = np.concatenate([np.clip(col * 255.0 + 0.5, 0, 255).astype(np.uint8), np.full((len(col), 1), 255, np.uint8)], 1)
-    meshes = [dict(mode=0, positions=pts, colors=col)]
+    H, W = imgs.shape[1:3]
+    return write_scene_glb(path, [dict(mode=0, positions=pts, colors=col)], focals, cams2world, (W, H), cam_size=cam_size, show_cam=show_cam,
+                           cam_color=cam_color)
+
+
+def mesh_geometry(positions, colors, faces):
+    """The indexed TRIANGLES primitive of the mesh export (convert_scene_output_to_glb with as_pointcloud=False): POSITION = every pixel
+    of every image as cat_meshes keeps them (f32 [n H W, 3]), COLOR_0 = each vertex's own pixel colour (RGBA u8 [n H W, 4]), uint32
+    indices = the kept faces [f, 3]. The reference hands trimesh per-FACE colours (the quad's top-left pixel for its first two faces,
+    the bottom-right one for the other two); glTF can attach colours to faces only by un-merging the vertices, so this writer keeps
+    one vertex per pixel and colours by vertex instead, and does not reproduce trimesh's exact file layout."""
+    return dict(mode=4, positions=positions, colors=colors, indices=faces)
+
+
+def write_scene_glb(path, geometry, focals, cams2world, imsize, cam_size=0.05, show_cam=True, cam_color=None):
+    """Writes `geometry` (a list of _glb_bytes mesh dicts: the point cloud or the mesh, already compacted) + one LINES primitive per
+    camera (see save_glb) under the reference's scene transform. imsize = (W, H). Returns `path`."""
+    to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    focals, cams2world = to_np(focals), to_np(cams2world)
+    meshes = list(geometry)
     n = len(cams2world)
     if show_cam:
-        H, W = imgs.shape[1:3]
+        W, H = imsize
         for i in range(n):
             if cam_color is not None:
                 c = np.asarray(cam_color[i] if isinstance(cam_color, list) else cam_color, np.float64)

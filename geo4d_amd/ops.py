@@ -885,3 +885,63 @@ def depth_metrics(pred, gt, st, *, max_depth=None, custom_mask=None, pre_clip_mi
                                        clip(pre_clip_max, inf), clip(post_clip_min, -inf), clip(post_clip_max, inf), sums.data_ptr(),
                                        err.data_ptr(), _ptr(al), ws.data_ptr(), need, _stream()), "geo4d_depth_metrics")
     return sums, err, al
+
+
+def scene_clean(conf, pts3d, depth, mats, tol=0.001, bad_conf=0.0):
+    """clean_pointcloud (base_opt_group.py:630-665) in place on conf fp32 [n, H, W]: pts3d [n, H, W, 3] world points, depth [n, H, W],
+    mats [n, 21] = rows 0..2 of each world-to-camera matrix then its intrinsics, row-major. Returns conf."""
+    lib = _lib.load()
+    for t, what in ((conf, "conf"), (pts3d, "pts3d"), (depth, "depth"), (mats, "mats")):
+        _dev(t, what)
+        assert t.dtype == torch.float32 and t.is_contiguous(), (what, t.dtype, t.shape)
+    n, H, W = conf.shape
+    assert pts3d.shape == (n, H, W, 3) and depth.shape == (n, H, W) and mats.shape == (n, 21), (pts3d.shape, depth.shape, mats.shape)
+    _lib.check(lib.geo4d_scene_clean(conf.data_ptr(), pts3d.data_ptr(), depth.data_ptr(), mats.data_ptr(), n, H, W, float(tol), float(bad_conf),
+                                     _stream()), "geo4d_scene_clean")
+    return conf
+
+
+def _scene_mask(mask, shape, device):
+    if mask is None:
+        return None
+    assert tuple(mask.shape) == tuple(shape) and mask.device == device, (mask.shape, shape)
+    return mask.to(torch.bool).contiguous()
+
+
+def scene_points(pts3d, rgb=None, mask=None):
+    """(pts [n H W, 3] fp32, rgba [n H W, 4] uint8 or None, count device int64 [1]): pts3d[mask] and the matching colours of rgb
+    [n, H, W, 3] in [0, 1], image-major raster order (= torch boolean indexing); the first `count` rows are written. mask None = all."""
+    lib = _lib.load()
+    _dev(pts3d, "pts3d")
+    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous()
+    n, H, W, _ = pts3d.shape
+    if rgb is not None:
+        _dev(rgb, "rgb")
+        assert rgb.dtype == torch.float32 and rgb.shape == pts3d.shape and rgb.is_contiguous(), (rgb.dtype, rgb.shape)
+    m = _scene_mask(mask, (n, H, W), pts3d.device)
+    pts = torch.empty((n * H * W, 3), device=pts3d.device, dtype=torch.float32)
+    rgba = None if rgb is None else torch.empty((n * H * W, 4), device=pts3d.device, dtype=torch.uint8)
+    count = torch.empty(1, device=pts3d.device, dtype=torch.int64)
+    need = lib.geo4d_scene_points_workspace(n, H, W)
+    ws = torch.empty((need + 3) // 4, device=pts3d.device, dtype=torch.int32)
+    _lib.check(lib.geo4d_scene_points(pts3d.data_ptr(), _ptr(rgb), _ptr(m), n, H, W, pts.data_ptr(), _ptr(rgba), count.data_ptr(),
+                                      ws.data_ptr(), need, _stream()), "geo4d_scene_points")
+    return pts, rgba, count
+
+
+def scene_mesh_faces(mask, n, H, W, device):
+    """(faces [4 n (H-1)(W-1), 3] int32, count device int64 [1]): pts3d_to_trimesh + cat_meshes's faces (dust3r/viz.py:40-90) for a
+    valid-vertex mask [n, H, W] (None = every vertex valid); the first `count` rows are written."""
+    lib = _lib.load()
+    if mask is not None:
+        _dev(mask, "mask")
+    m = _scene_mask(mask, (n, H, W), device)
+    faces = torch.empty((4 * n * max(H - 1, 0) * max(W - 1, 0), 3), device=device, dtype=torch.int32)
+    count = torch.zeros(1, device=device, dtype=torch.int64)
+    if H < 2 or W < 2:                                      # no quads
+        return faces, count
+    need = lib.geo4d_scene_mesh_faces_workspace(n, H, W)
+    ws = torch.empty((need + 3) // 4, device=device, dtype=torch.int32)
+    _lib.check(lib.geo4d_scene_mesh_faces(_ptr(m), n, H, W, faces.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _stream()),
+               "geo4d_scene_mesh_faces")
+    return faces, count

@@ -1,0 +1,119 @@
+"""Scene export: from an aligned ``GroupAligner`` to what a user opens (the end of scripts/evaluation/test_geo4d.py:513-534).
+
+``get_3D_model_from_scene`` is ``dust3r/demo.py:56-86`` on a ``GroupAligner``: optional ``clean_depth`` (``clean_pointcloud``, the
+n (n - 1) H W projections of csrc/scene_export.hip, one launch per source image), the confidence masks, and the glb of
+``convert_scene_output_to_glb`` (dust3r/utils/viz_demo.py:13-58): the point cloud (``as_pointcloud``) or the mesh of
+``pts3d_to_trimesh`` + ``cat_meshes`` (dust3r/viz.py:40-90), plus the camera glyphs. Masking and compaction run on the device; only the
+kept points / faces go to the host. ``save_scene`` writes the script's whole results folder.
+"""
+import os
+
+import torch
+
+from . import io, ops
+
+
+def check_tol(tol):
+    """clean_pointcloud's `assert 0 <= tol < 1`, as an error."""
+    if not (0 <= tol < 1):
+        raise ValueError(f"clean_pointcloud: tol must satisfy 0 <= tol < 1, got {tol}")
+
+
+def _stack(x):
+    return torch.stack(list(x)) if isinstance(x, (list, tuple)) else x
+
+
+@torch.no_grad()
+def clean_pointcloud(im_confs, K, cams, depthmaps, all_pts3d, tol=0.001, bad_conf=0):
+    """base_opt_group.py:630-665 with the same arguments (tensors [n, ...] or lists of per-image tensors, on the HIP device): for every
+    ordered pair (i, j) in the reference's loop order, pixels of i that project in front of j's depth and are less confident than j's
+    pixel there get min(conf, bad_conf). cams = world-to-camera 4x4, K = 3x3 intrinsics. Returns the cleaned confidences [n, H, W]
+    (a new tensor; the inputs are left as they are)."""
+    check_tol(tol)
+    conf = _stack(im_confs)
+    n, H, W = conf.shape
+    cams, K = _stack(cams), _stack(K)
+    if not (conf.is_cuda and cams.is_cuda and K.is_cuda):
+        from . import _lib
+        raise _lib.Geo4DNativeError("clean_pointcloud runs only on a HIP device (there is no CPU fallback)")
+    assert len(cams) == len(K) == n, (cams.shape, K.shape, conf.shape)
+    mats = torch.cat([cams[:, :3, :].reshape(n, 12), K.reshape(n, 9)], 1).float().contiguous()
+    out = conf.float().clone().contiguous()
+    ops.scene_clean(out, _stack(all_pts3d).reshape(n, H, W, 3).float().contiguous(), _stack(depthmaps).reshape(n, H, W).float().contiguous(),
+                    mats, tol=tol, bad_conf=bad_conf)
+    return out
+
+
+def camera_colors(n):
+    """The demo's camera edge colours: viridis(i / n) scaled to 0-255 (demo.py:80-81)."""
+    import matplotlib
+    cmap = matplotlib.colormaps["viridis"]
+    return [tuple(255 * c for c in cmap(i / n)[:3]) for i in range(n)]
+
+
+def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
+                            transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True):
+    """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
+
+    Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
+    to geo4d_amd.io.save_glb on the same points, colours and masks; the mesh is one indexed TRIANGLES primitive with per-vertex colours
+    (io.mesh_geometry says why it is not trimesh's per-face layout). `mask_sky=True` raises NotImplementedError: segment_sky needs
+    OpenCV, which this engine does not use. `transparent_cams` is accepted and changes nothing: the camera glyphs here are untextured
+    wireframes, there is no image on them to make transparent."""
+    if scene is None:
+        return None
+    if mask_sky:
+        raise NotImplementedError("get_3D_model_from_scene(mask_sky=True): segment_sky needs OpenCV (cv2), which is not available")
+    if clean_depth:
+        scene = scene.clean_pointcloud()
+    if scene.imgs is None:
+        raise ValueError("get_3D_model_from_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs "
+                         "[n, H, W, 3] in [0, 1]")
+    scene.require_all_depthmaps("get_3D_model_from_scene")
+    with torch.no_grad():
+        imgs = scene.imgs.to(scene.dev).float().contiguous()
+        focals = scene.get_focals().detach()
+        cams2world = scene.get_im_poses_matrix().detach()
+        pts3d = scene.get_pts3d().contiguous()
+        scene.min_conf_thr = min_conf_thr
+        scene.thr_for_init_conf = thr_for_init_conf
+        msk = scene.get_masks() if is_msk else None
+        n, H, W, _ = pts3d.shape
+        if as_pointcloud:
+            pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
+            c = int(count.item())
+            geometry = [dict(mode=0, positions=pts[:c].cpu().numpy(), colors=rgba[:c].cpu().numpy())]
+        else:
+            pts, rgba, _ = ops.scene_points(pts3d, imgs, None)          # every vertex, as cat_meshes keeps them
+            faces, count = ops.scene_mesh_faces(msk, n, H, W, pts3d.device)
+            c = int(count.item())
+            geometry = [io.mesh_geometry(pts.cpu().numpy(), rgba.cpu().numpy(), faces[:c].cpu().numpy())] if c else []
+    outfile = os.path.join(outdir, (save_name or "scene") + ".glb")
+    if not silent:
+        print("(exporting 3D scene to", outfile, ")")
+    return io.write_scene_glb(outfile, geometry, focals, cams2world, (W, H), cam_size=cam_size, show_cam=show_cam,
+                              cam_color=camera_colors(n))
+
+
+def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, **glb_kw):
+    """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
+    cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
+    previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
+    Returns the directory."""
+    from .align import rgb_frames
+    d = os.path.join(outdir, seq)
+    os.makedirs(d, exist_ok=True)
+    if imgs is not None:
+        scene.imgs = rgb_frames(imgs, scene.n, scene.H, scene.W).to(scene.dev)
+    kw = dict(silent=True, as_pointcloud=True, mask_sky=False, clean_depth=False, transparent_cams=False, cam_size=0.01, is_msk=False)
+    kw.update(glb_kw)
+    get_3D_model_from_scene(d, kw.pop("silent"), scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
+    with torch.no_grad():
+        io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
+        io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())
+        io.save_intrinsics(os.path.join(d, "pred_intrinsics.txt"), scene.get_intrinsics())
+        io.save_depth_maps(d, scene.get_depthmaps())
+        io.save_conf_maps(d, scene.get_conf(), "conf")
+        io.save_conf_maps(d, scene.get_init_conf(), "init_conf")
+        io.save_rgb_imgs(d, scene.imgs.detach().cpu().numpy())
+    return d

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GEO4D_ABI_VERSION 8
+#define GEO4D_ABI_VERSION 9
 
 /* Implicit-GEMM convolution / linear / batched GEMM:  out = epilogue(alpha * gather(A) . W^T)
  * replaces F.linear (attention.py:52-56,420,437), F.conv2d 3x3/1x1 stride 1|2 (openaimodel3d.py:154,179,65-67;
@@ -346,6 +346,29 @@ size_t geo4d_depth_metrics_workspace(long n);
 int geo4d_depth_metrics(const float* pred, const float* gt, long n, float max_depth, const unsigned char* custom_mask, const float* st,
                         float pre_min, float pre_max, float post_min, float post_max, double* sums, float* err_map, float* aligned,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Scene export (dust3r/demo.py get_3D_model_from_scene :56-86 on an aligned scene; geo4d_amd/scene_export.py). n images of H x W,
+ * n * H * W < 2^31; every array on the device, image-major [n][H][W](...).
+ *   geo4d_scene_clean: clean_pointcloud (dust3r/cloud_opt/base_opt_group.py:630-665) IN PLACE on conf [n][H][W] fp32. pts3d [n][H][W][3]
+ *     world points, depth [n][H][W], mats [n][21] = rows 0..2 of the 4x4 world-to-camera matrix (12) then the 3x3 intrinsics (9),
+ *     row-major. For i = 0 .. n-1 in order, for j != i ascending: pixel p of i goes to camera j, (u, v) = rint((K p)[:2] / (K p)[2]);
+ *     where z > 0, 0 <= u < W, 0 <= v < H, z < (1 - tol) depth[j][v][u] and conf[i][p] < conf[j][v][u], conf[i][p] = min(conf[i][p],
+ *     bad_conf). Rows j < i are read already cleaned, rows j > i as given (the reference's loop order). 0 <= tol < 1. n launches.
+ *   geo4d_scene_points: (pts_out [*count][3], rgba_out [*count][4] u8) = (pts3d, rgb)[mask] in image-major raster order (mask NULL:
+ *     every pixel); RGBA = clip(c * 255 + 0.5, 0, 255) truncated, alpha 255. rgb [n][H][W][3] fp32 and rgba_out are both set or both
+ *     NULL; rgba_out 4-byte aligned. *count is a device int64; the outputs hold n H W rows. workspace: geo4d_scene_points_workspace bytes.
+ *   geo4d_scene_mesh_faces: faces [*count][3] int32 = pts3d_to_trimesh + cat_meshes (dust3r/viz.py:40-90): per image i the blocks
+ *     (tl, tr, bl), (bl, tr, tl), (tr, bl, br), (br, bl, tr) over the (H-1) x (W-1) quads in raster order, kept when all three vertices
+ *     are valid in mask [n][H][W] (NULL: all), vertex ids + i H W. faces holds 4 n (H-1)(W-1) rows; H, W >= 2.
+ *     workspace: geo4d_scene_mesh_faces_workspace bytes, 4-byte aligned. */
+int geo4d_scene_clean(float* conf, const float* pts3d, const float* depth, const float* mats, int n, int H, int W, double tol, float bad_conf,
+                      void* stream);
+size_t geo4d_scene_points_workspace(int n, int H, int W);
+int geo4d_scene_points(const float* pts3d, const float* rgb, const unsigned char* mask, int n, int H, int W, float* pts_out,
+                       unsigned char* rgba_out, long* count, void* workspace, size_t workspace_bytes, void* stream);
+size_t geo4d_scene_mesh_faces_workspace(int n, int H, int W);
+int geo4d_scene_mesh_faces(const unsigned char* mask, int n, int H, int W, int* faces, long* count, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 const char* geo4d_last_error(void);
 int geo4d_abi_version(void);
