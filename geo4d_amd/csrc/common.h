@@ -244,7 +244,8 @@ __device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r 
 
 // ---- misc ---------------------------------------------------------------------------------
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
-// erf by Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, i.e. fp32 round-off class): 5 fma + v_rcp + v_exp instead of
+// erf by Abramowitz-Stegun 7.1.26 (the formula's |abs error| <= 1.5e-7; evaluated in fp32 over the 1-ulp v_rcp / v_exp: 4.6e-7 measured
+// on [-8, 8], tests/test_entrypoints_gpu.py - fp32 round-off class): 5 fma + v_rcp + v_exp instead of
 // libm's branchy ~25-instruction erff — the GEGLU epilogue runs it on every element of the widest tensors of the U-Net.
 __device__ __forceinline__ float erf_as(float x) {
     const float ax = fabsf(x);
