@@ -14,8 +14,13 @@
 // Activations are channels-last tokens [F, H*W, C]; weights are packed [N][taps*Cin] (K-major, tap-major).
 // out[m][n] = epilogue(alpha * sum_k A_gather[m][k] * W[n][k])
 //
-// Structure (kernel template in gemm_kernel.h; 4, 5, 8 or 10 waves, tile BM x BN x 128 B of K per stage; tiles 128x128, 128x64,
-// 64x128, 64x64, 128x32, 256x128, 256x256, 160x320, 160x160 picked per problem by the host's measured table):
+// Host side: this file validates the descriptor, gemm_plan.h resolves it - ONE tile table (every hint of the three kernel generations:
+// gemm_kernel.h, gemm_kernel_v2.h, gemm_kernel_v3.h) and ONE function, resolve(), that applies defaults, redirects, fall-backs, split-K,
+// the operand-layout variant and the gn_colsum granularity - and the generation's translation unit launches the plan's tile.
+// geo4d_conv_gemm_colsum_rows answers from the same plan.
+//
+// Structure of the first-generation kernel (template in gemm_kernel.h; 4, 5, 8 or 10 waves, tile BM x BN x 128 B of K per stage; tiles
+// 128x128, 128x64, 64x128, 64x64, 128x32, 256x128, 256x256, 160x320, 160x160 picked per problem by the host's measured table):
 //   * gather table: the source pixel of every (tile row, tap) is resolved ONCE per workgroup into LDS
 //     (-1 = zero padding), so the K loop does one ds_read + one 64-bit mad per 16-byte chunk instead of
 //     re-deriving (frame, y, x), bounds and upsample/stride arithmetic every stage;
@@ -38,42 +43,38 @@
 #include "gemm_kernel.h"
 
 namespace geo4d_gemm {
-extern template int launch_typed<float>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_typed<bf16_t>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_typed<f16_t>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_typed<bf16x3_t>(const geo4d_conv_gemm_t&, hipStream_t);
+// one translation unit per generation and element type (parallel build): gemm_*.hip, gemm_v2_*.hip, gemm_v3_*.hip
+extern template int launch_typed<float>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_typed<bf16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_typed<f16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_typed<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v2_typed<bf16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v2_typed<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v2_typed<f16x2p_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v3_typed<bf16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v3_typed<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v3_typed<f16x2p_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+
+// the second / third generation's launcher of the plan's tile (resolve() refuses those hints for the other element types)
+template <typename T>
+static int launch_v23(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t s) {
+    return generation(plan.hint) == 2 ? launch_v2_typed<T>(p, plan, s) : launch_v3_typed<T>(p, plan, s);
+}
 }  // namespace geo4d_gemm
-namespace geo4d_gemm {
-template <typename T> int colsum_rows_v23(const geo4d_conv_gemm_t& p);      // gemm_kernel_v3.h, instantiated in gemm_v3_bf16x3.hip / gemm_v3_bf16.hip
-extern template int colsum_rows_v23<bf16x3_t>(const geo4d_conv_gemm_t&);
-extern template int colsum_rows_v23<bf16_t>(const geo4d_conv_gemm_t&);
-extern template int colsum_rows_v23<f16x2p_t>(const geo4d_conv_gemm_t&);
-// f16x2 (dtype 4) exists on the second / third generation only
-extern template int launch_v2_typed<f16x2p_t>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_v3_typed<f16x2p_t>(const geo4d_conv_gemm_t&, hipStream_t);
-}  // namespace geo4d_gemm
-using geo4d_gemm::BKC;
-using geo4d_gemm::MAXTAP;
-using geo4d_gemm::launch_typed;
+using namespace geo4d_gemm;
 
 extern "C" int geo4d_conv_gemm(const geo4d_conv_gemm_t* pp, void* stream) {
     if (!pp) return GEO4D_EINVAL;
-    geo4d_conv_gemm_t p = *pp;
+    const geo4d_conv_gemm_t& p = *pp;
     const int esz = (p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3 || p.dtype == GEO4D_F16X2) ? 4 : 2;
-    const int epc = 16 / esz;
-    const int bk = BKC * epc;
+    const int bk = KSLAB_BYTES / esz;
     if (p.dtype < 0 || p.dtype > 4 || p.out_dtype < 0 || p.out_dtype > 2) { geo4d_set_error("conv_gemm: bad dtype"); return GEO4D_EINVAL; }
     if (p.dtype != GEO4D_BF16X3 && p.dtype != GEO4D_F16X2 && (p.a_split || p.w_split)) { geo4d_set_error("conv_gemm: a_split / w_split are bf16x3 / f16x2 (dtype 3 / 4) options"); return GEO4D_EINVAL; }
-    if (p.dtype == GEO4D_F16X2) {
-        // two-pass f16: plain f16 activation rows x a pre-split f16 weight, f32 rows (or, o_split = 2, plain f16 rows) out, second / third
-        // generation tiles (0 = a default per shape)
-        if (p.a_split != 2 || !p.w_split || (p.o_split != 0 && p.o_split != 2) || p.out_nchw || p.out_dtype != GEO4D_F32 || (p.tile_hint != 0 && p.tile_hint < 22)) {
-            geo4d_set_error("conv_gemm: f16x2 (dtype 4) needs a_split = 2 (plain f16 activation rows) and w_split, a row-major output (f32 rows, or o_split = 2: plain f16 rows), and tile hint 0 or >= 22");
-            return GEO4D_EINVAL;
-        }
-        // (GEGLU lives on the tiles whose wave tiles are a multiple of 64 columns wide)
-        if (p.tile_hint == 0) p.tile_hint = p.M >= 4096 ? (p.act == 2 ? 71 : 72) : 25;
-        if (p.split_k == 0) p.split_k = 1;
+    // two-pass f16: plain f16 activation rows x a pre-split f16 weight, f32 rows (or, o_split = 2, plain f16 rows) out, second / third
+    // generation tiles (0 = a default per shape)
+    if (p.dtype == GEO4D_F16X2 && (p.a_split != 2 || !p.w_split || (p.o_split != 0 && p.o_split != 2) || p.out_nchw || p.out_dtype != GEO4D_F32 || (p.tile_hint != 0 && generation(p.tile_hint) == 1))) {
+        geo4d_set_error("conv_gemm: f16x2 (dtype 4) needs a_split = 2 (plain f16 activation rows) and w_split, a row-major output (f32 rows, or o_split = 2: plain f16 rows), and tile hint 0 or >= 22");
+        return GEO4D_EINVAL;
     }
     if (p.o_split) {
         const int nst = p.act == 2 ? p.N / 2 : p.N;
@@ -104,42 +105,28 @@ extern "C" int geo4d_conv_gemm(const geo4d_conv_gemm_t* pp, void* stream) {
             return GEO4D_EINVAL;
         }
     }
-    if (p.gn_colsum && p.tile_hint < 21) {      // (first generation: one entry per 32 rows; the second / third generation launchers check their own form)
-        const int oesz = p.out_dtype == GEO4D_F32 ? 4 : 2;
-        if ((p.M % 32) || (p.N % 8) || p.out_nchw || p.act == 2 || p.batch != 1 || p.split_k != 1 || ((p.ldo * oesz) % 16) || ((uintptr_t)p.O % 16) ||
-            ((uintptr_t)p.gn_colsum % 16) || (p.R && (((p.ldr * oesz) % 16) || ((uintptr_t)p.R % 16)))) {
-            geo4d_set_error("conv_gemm: gn_colsum needs M % 32 == 0, N % 8 == 0, a row-major 16-byte aligned output, batch 1, split_k = 1, no GEGLU");
-            return GEO4D_EINVAL;
-        }
-    }
     if (p.rowbias && p.rowbias_div <= 0) { geo4d_set_error("conv_gemm: rowbias_div"); return GEO4D_EINVAL; }
     if (p.batch > 65535) { geo4d_set_error("conv_gemm: batch too large"); return GEO4D_EINVAL; }
     if (!p.zeros || ((uintptr_t)p.zeros % 16)) { geo4d_set_error("conv_gemm: `zeros` must point at 16 zero bytes (16-byte aligned) in device memory"); return GEO4D_EINVAL; }
     if (p.workspace && ((uintptr_t)p.workspace % 16)) { geo4d_set_error("conv_gemm: workspace alignment"); return GEO4D_EINVAL; }
+    const Plan plan = resolve(p);
+    if (plan.error) { geo4d_set_error(plan.error); return GEO4D_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
+    const bool gen1 = generation(plan.hint) == 1;
     switch (p.dtype) {
-        case GEO4D_F32: return launch_typed<float>(p, s);
-        case GEO4D_BF16: return launch_typed<bf16_t>(p, s);
-        case GEO4D_BF16X3: return launch_typed<bf16x3_t>(p, s);
-        case GEO4D_F16X2: return p.tile_hint >= 71 ? geo4d_gemm::launch_v3_typed<f16x2p_t>(p, s) : geo4d_gemm::launch_v2_typed<f16x2p_t>(p, s);
-        default: return launch_typed<f16_t>(p, s);
+        case GEO4D_F32: return launch_typed<float>(p, plan, s);
+        case GEO4D_BF16: return gen1 ? launch_typed<bf16_t>(p, plan, s) : launch_v23<bf16_t>(p, plan, s);
+        case GEO4D_BF16X3: return gen1 ? launch_typed<bf16x3_t>(p, plan, s) : launch_v23<bf16x3_t>(p, plan, s);
+        case GEO4D_F16X2: return launch_v23<f16x2p_t>(p, plan, s);
+        default: return launch_typed<f16_t>(p, plan, s);
     }
 }
 
 // Rows of the output that ONE gn_colsum entry of the launch `*pp` describes covers (tile_hint / split_k as they will be launched;
 // the gn_colsum field itself is ignored): 32 for the first-generation tiles, the wave tile's rows for the second / third generation,
-// 0 = this launch cannot emit the sums (the caller then leaves gn_colsum null and the GroupNorm runs its own statistics pass).
+// 0 = this launch cannot emit the sums or would be refused (the caller then leaves gn_colsum null and the GroupNorm runs its own
+// statistics pass). The answer is the launch's own plan.
 extern "C" int geo4d_conv_gemm_colsum_rows(const geo4d_conv_gemm_t* pp) {
-    if (!pp) return 0;
-    const geo4d_conv_gemm_t& p = *pp;
-    if (p.tile_hint < 21) {
-        const int oesz = p.out_dtype == GEO4D_F32 ? 4 : 2;
-        const bool ok = !(p.M % 32) && !(p.N % 8) && !p.out_nchw && p.act != 2 && p.batch == 1 && p.split_k <= 1 && !p.o_split && !((p.ldo * oesz) % 16) &&
-                        !((uintptr_t)p.O % 16) && (!p.R || (!((p.ldr * oesz) % 16) && !((uintptr_t)p.R % 16)));
-        return ok ? 32 : 0;
-    }
-    if (p.dtype == GEO4D_BF16X3) return geo4d_gemm::colsum_rows_v23<bf16x3_t>(p);
-    if (p.dtype == GEO4D_BF16) return geo4d_gemm::colsum_rows_v23<bf16_t>(p);
-    if (p.dtype == GEO4D_F16X2) return geo4d_gemm::colsum_rows_v23<f16x2p_t>(p);
-    return 0;
+    if (!pp || pp->Hout <= 0 || pp->Wout <= 0) return 0;      // (the plan divides by a frame's rows)
+    return resolve(*pp).colsum_rows;
 }

@@ -2,5 +2,5 @@
 #include "gemm_kernel.h"
 
 namespace geo4d_gemm {
-template int launch_typed<float>(const geo4d_conv_gemm_t&, hipStream_t);
+template int launch_typed<float>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
 }  // namespace geo4d_gemm

@@ -1,10 +1,11 @@
 // geo4d_amd/csrc/gemm_kernel.h — the implicit-GEMM kernel template + tile dispatch (see gemm.hip for the design notes).
 // Included by gemm.hip (C ABI + validation) and by gemm_{bf16,f16,f32}.hip, each of which instantiates launch_typed<T>
-// for ONE element type so the three sets of kernels compile in parallel.
+// for ONE element type so the three sets of kernels compile in parallel. Which tile a launch becomes is decided in gemm_plan.h.
 #pragma once
 #include <type_traits>
 #include "common.h"
 #include "geo4d_hip.h"
+#include "gemm_plan.h"
 
 namespace geo4d_gemm {
 
@@ -12,6 +13,7 @@ namespace geo4d_gemm {
 constexpr int PITCH = 128;  // LDS row pitch in bytes: 8 x 16-byte slots, XOR-swizzled
 constexpr int BKC = 8;      // 16-byte chunks per row per stage
 constexpr int MAXTAP = 9;
+static_assert(BKC * 16 == KSLAB_BYTES, "gemm_plan.h counts K slabs of BKC 16-byte chunks");
 
 __device__ __forceinline__ void store_out(void* O, long idx, float v, int dt) {
     if (dt == GEO4D_F32) ((float*)O)[idx] = v;
@@ -529,7 +531,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const geo4d_conv_gem
 // launch of the second / third generation): a workgroup owns RB rows x (256 / RB) groups of 8 columns, thread (r, cg) finishes 8 outputs of row r
 // exactly like splitk_reduce_kernel (same summation order, same epilogue order: same bits), then the RB rows of every column are added in a
 // fixed tree (xor shuffles inside the wave, the 4 waves through LDS in wave order) into gn_colsum[M / RB][N][2] = (sum, sum of squares).
-// batch 1, M % RB == 0, N % (8 * 256 / RB) == 0, f32 rows (splitk_colsum_rows below).
+// batch 1, M % RB == 0, N % (8 * 256 / RB) == 0, f32 rows (splitk_colsum_rows, gemm_plan.h).
 template <typename T, int RB>
 __global__ __launch_bounds__(256) void splitk_reduce_colsum_kernel(const geo4d_conv_gemm_t p, int splits) {
     constexpr int CG = 256 / RB;                 // 8-column groups per workgroup
@@ -581,27 +583,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_colsum_kernel(const geo4d_c
         dst[0] = s0; dst[1] = s1;
     }
 }
-// rows per gn_colsum entry a split-K launch of the second / third generation emits through splitk_reduce_colsum_kernel (0 = it cannot): 32, or 8
-// where a frame's rows are a multiple of 8 but not of 32 (the 5 x 8 level: per-frame GroupNorms need blocks that do not straddle frames)
-inline int splitk_colsum_rows(const geo4d_conv_gemm_t& p, int sp) {
-    if (sp <= 1 || p.batch != 1 || p.act != 0 || p.o_split || p.out_nchw || p.out_dtype != GEO4D_F32 || p.bias_per_row || (p.ldo & 3) || ((uintptr_t)p.O % 16) ||
-        (p.R && ((uintptr_t)p.R % 4))) return 0;
-    const int hw = p.Hout * p.Wout;
-    if (hw % 32 == 0 && p.M % 32 == 0 && p.N % 64 == 0) return 32;
-    if (hw % 8 == 0 && p.M % 8 == 0 && p.N % 256 == 0) return 8;
-    return 0;
-}
-// the reduce launch of a split-K GEMM (every generation's launcher ends here): with gn_colsum, the column-sum form
+// the reduce launch of a split-K GEMM (every generation's launcher ends here): with gn_colsum, the column-sum form at the plan's granularity
 template <typename T>
-int launch_splitk_reduce(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    if (p.gn_colsum) {
-        const int rows = splitk_colsum_rows(p, splits);
-        if (rows == 32) hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 32>), dim3((unsigned)((p.M / 32) * (p.N / 64))), dim3(256), 0, stream, p, splits);
-        else if (rows == 8) hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 8>), dim3((unsigned)((p.M / 8) * (p.N / 256))), dim3(256), 0, stream, p, splits);
-        else { geo4d_set_error("conv_gemm: gn_colsum on a split-K launch needs batch 1, f32 rows, no activation, frame rows % 8 == 0 (geo4d_conv_gemm_colsum_rows)"); return GEO4D_EINVAL; }
+int launch_splitk_reduce(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    if (p.gn_colsum && plan.colsum_rows == 32) {
+        hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 32>), dim3((unsigned)((p.M / 32) * (p.N / 64))), dim3(256), 0, stream, p, plan.splits);
+    } else if (p.gn_colsum) {
+        hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 8>), dim3((unsigned)((p.M / 8) * (p.N / 256))), dim3(256), 0, stream, p, plan.splits);
     } else {
         const long tot = (long)p.batch * p.M * (p.N / 8);
-        hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, p, splits);
+        hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, p, plan.splits);
     }
     GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
@@ -627,112 +618,50 @@ int launch_kernel(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int ST>
-int launch_cfg(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    if (p.act == 2 && ((BN / WN / 32) & 1)) {
-        geo4d_set_error("conv_gemm: GEGLU needs wave tiles that are a multiple of 64 columns wide (this tile has an odd number of 32-column blocks)");
-        return GEO4D_EINVAL;
-    }
+int launch_cfg(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
     int rc;
     if constexpr (IsX3<T>::value) {
-        if (p.w_split && !p.a_split) rc = launch_kernel<T, BM, BN, WM, WN, ST, 1>(p, splits, stream);
-        else if (p.w_split && p.a_split) rc = launch_kernel<T, BM, BN, WM, WN, ST, 2>(p, splits, stream);
-        else rc = launch_kernel<T, BM, BN, WM, WN, ST, 0>(p, splits, stream);
+        if (plan.hot == 1) rc = launch_kernel<T, BM, BN, WM, WN, ST, 1>(p, plan.splits, stream);
+        else if (plan.hot == 2) rc = launch_kernel<T, BM, BN, WM, WN, ST, 2>(p, plan.splits, stream);
+        else rc = launch_kernel<T, BM, BN, WM, WN, ST, 0>(p, plan.splits, stream);
     } else {
-        rc = launch_kernel<T, BM, BN, WM, WN, ST, 0>(p, splits, stream);
+        rc = launch_kernel<T, BM, BN, WM, WN, ST, 0>(p, plan.splits, stream);
     }
-    if (rc != GEO4D_OK) return rc;
-    if (splits > 1) {
-        const long total = (long)p.batch * p.M * (p.N / 8);
-        hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, splits);
-        GEO4D_CHECK_LAUNCH();
-    }
+    if (rc != GEO4D_OK || plan.splits == 1) return rc;
+    const long total = (long)p.batch * p.M * (p.N / 8);      // (no gn_colsum from a split first-generation launch: the plain reduce)
+    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, plan.splits);
+    GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
 }
 
-// tile hints 22..28 (gemm_kernel_v2.h: 16x16x32 MFMA, register epilogue, persistent workgroups) are instantiated in their own
-// translation units (gemm_v2_*.hip) so that the two kernel generations compile in parallel
-template <typename T> int launch_v2_typed(const geo4d_conv_gemm_t& p, hipStream_t stream);
-// tile hints 71..74 (gemm_kernel_v3.h: the same with a phased, counted-wait K loop): gemm_v3_*.hip
-template <typename T> int launch_v3_typed(const geo4d_conv_gemm_t& p, hipStream_t stream);
-
-// Tile choice: score = MFMA efficiency of the tile shape x useful fraction x how full the last wave of
-// workgroups is (2 workgroups fit per CU by LDS => 512 slots on 256 CUs). Split-K multiplies the workgroup count
-// when M x N alone cannot fill the chip and K is deep enough to amortise the extra fp32 slab traffic.
-struct TileCfg { int bm, bn; float eff; };
+// the plan's tile on the first generation (hints 1..17). The later generations are instantiated in their own translation units so that
+// the generations compile in parallel: hints 22..28 (gemm_kernel_v2.h: 16x16x32 MFMA, register epilogue, persistent workgroups) in
+// gemm_v2_*.hip, hints 71..74 (gemm_kernel_v3.h: the same with a phased, counted-wait K loop) in gemm_v3_*.hip
+template <typename T> int launch_v2_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);
+template <typename T> int launch_v3_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);
 
 template <typename T>
-int launch_typed(const geo4d_conv_gemm_t& p, hipStream_t stream) {
-    static constexpr TileCfg cfgs[] = {{128, 128, 1.00f}, {128, 64, 0.85f}, {64, 128, 0.80f}, {64, 64, 0.62f}, {128, 32, 0.50f}};
-    if (p.tile_hint >= 71) return launch_v3_typed<T>(p, stream);
-    if (p.tile_hint >= 21) return launch_v2_typed<T>(p, stream);
-    if (p.o_split) {     // the pre-split output format lives in the register epilogue of the second-generation kernel only
-        geo4d_conv_gemm_t q = p;
-        // (GEGLU needs wave tiles that are a multiple of 64 columns wide: 22, 25, 27 of the second generation)
-        const bool gg = p.act == 2;
-        q.tile_hint = (p.tile_hint == 13 || p.tile_hint == 11) ? 22 : p.tile_hint == 16 ? (gg ? 22 : 23) : p.tile_hint == 3 ? 27 : p.tile_hint == 4 ? (gg ? 27 : 28) : 25;
-        return launch_v2_typed<T>(q, stream);
-    }
-    if (p.tile_hint >= 11) {
-        // explicit big-tile / deep-ring configurations, chosen by the host tuning table only. What they trade:
+int launch_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    switch (plan.hint) {
+        case 1: return launch_cfg<T, 128, 128, 2, 2, 2>(p, plan, stream);
+        case 2: return launch_cfg<T, 128, 64, 4, 1, 2>(p, plan, stream);
+        case 3: return launch_cfg<T, 64, 128, 2, 2, 2>(p, plan, stream);
+        case 4: return launch_cfg<T, 64, 64, 2, 2, 2>(p, plan, stream);
+        case 5: return launch_cfg<T, 128, 32, 4, 1, 2>(p, plan, stream);
+        // explicit big-tile configurations, chosen by the host tuning table only. What they trade:
         // a CU can hold at most ~128 KB of LDS-DMA destinations, and a stage lands ~1 us after it is issued, so the
         // flops a CU can retire per microsecond are (bytes in flight) x (flops per byte of the tile shape).
         //   11: 256x128, 8 waves     13: 256x256, 8 waves (128 flop/B)
         //   16: 160x320, 10 waves (M = 40960, N = 320: 256 tiles = one per CU, each input row and each weight read once per tile)
         // Measured (profiles/r01_gemm_tiles.md): deeper rings (former hints 12, 14) never beat their 2-stage twins - the fill rate
         // per CU does not grow with more DMAs in flight - while the fatter tiles (11, 13) do: fewer L2->LDS bytes per flop.
-        int sp = 1;
-        if (p.split_k > 1) {
-            if (!p.workspace || p.act == 2 || p.out_nchw || (p.N % 8) || (size_t)p.split_k * p.batch * p.M * p.N * 4 > p.workspace_bytes ||
-                p.K / (BKC * Elem<T>::EPC) / p.split_k < 1) {
-                geo4d_set_error("conv_gemm: split_k not applicable (workspace too small / epilogue not splittable)");
-                return GEO4D_EINVAL;
-            }
-            sp = p.split_k;
-        }
-        switch (p.tile_hint) {
-            case 11: return launch_cfg<T, 256, 128, 4, 2, 2>(p, sp, stream);
-            case 13: return launch_cfg<T, 256, 256, 4, 2, 2>(p, sp, stream);
-            case 16: return launch_cfg<T, 160, 320, 5, 2, 2>(p, sp, stream);   // 10 waves: all 320 columns of the level-0 layers in ONE tile
-            case 17: return launch_cfg<T, 160, 160, 5, 1, 2>(p, sp, stream);   // 5 waves: M = 10240, N = 640 -> 256 tiles
-        }
-        geo4d_set_error("conv_gemm: unknown tile_hint");
-        return GEO4D_EINVAL;
+        case 11: return launch_cfg<T, 256, 128, 4, 2, 2>(p, plan, stream);
+        case 13: return launch_cfg<T, 256, 256, 4, 2, 2>(p, plan, stream);
+        case 16: return launch_cfg<T, 160, 320, 5, 2, 2>(p, plan, stream);   // 10 waves: all 320 columns of the level-0 layers in ONE tile
+        case 17: return launch_cfg<T, 160, 160, 5, 1, 2>(p, plan, stream);   // 5 waves: M = 10240, N = 640 -> 256 tiles
     }
-    const int bk = BKC * Elem<T>::EPC;
-    const int nslab = p.K / bk;
-    const bool can_split = p.workspace && p.act != 2 && !p.out_nchw && (p.N % 8) == 0 && p.split_k != 1;
-    int best = -1, best_split = 1;
-    float best_score = -1.f;
-    const int hint_tile = p.tile_hint;
-    for (int i = 0; i < 5; ++i) {
-        const TileCfg& c = cfgs[i];
-        if (p.act == 2 && i >= 3) continue;  // GEGLU needs 64-wide wave tiles (NB == 2)
-        if (hint_tile && i != hint_tile - 1) continue;
-        const double tm = (p.M + c.bm - 1) / c.bm, tn = (p.N + c.bn - 1) / c.bn;
-        const double tiles = tm * tn * p.batch;
-        const double useful = ((double)p.M * p.N * p.batch) / (tiles * c.bm * c.bn);
-        for (int s = 1; s <= 16; s *= 2) {
-            if (s > 1 && (!can_split || nslab / s < 8)) break;
-            if (p.split_k > 1 && s != p.split_k) continue;
-            if (s > 1 && (size_t)s * p.batch * p.M * p.N * 4 > p.workspace_bytes) break;
-            const double wgs = tiles * s;
-            const double waves = (double)(long)((wgs + 511) / 512);
-            const double fill = wgs / (waves * 512);
-            const double split_cost = s > 1 ? 0.92 : 1.0;      // slab write + reduce kernel
-            const float score = (float)(c.eff * useful * (0.30 + 0.70 * fill) * split_cost);
-            if (score > best_score) { best_score = score; best = i; best_split = s; }
-        }
-    }
-    switch (best) {
-        case 0: return launch_cfg<T, 128, 128, 2, 2, 2>(p, best_split, stream);
-        case 1: return launch_cfg<T, 128, 64, 4, 1, 2>(p, best_split, stream);
-        case 2: return launch_cfg<T, 64, 128, 2, 2, 2>(p, best_split, stream);
-        case 3: return launch_cfg<T, 64, 64, 2, 2, 2>(p, best_split, stream);
-        case 4: return launch_cfg<T, 128, 32, 4, 1, 2>(p, best_split, stream);
-    }
-    geo4d_set_error("conv_gemm: no tile configuration (split_k / tile_hint not applicable to this problem?)");
+    geo4d_set_error("conv_gemm: unknown tile_hint");
     return GEO4D_EINVAL;
 }
-
 
 }  // namespace geo4d_gemm

@@ -99,16 +99,7 @@ constexpr int PITCH_A64 = 64;
 // gn_colsum from the fast path (round 4): per WAVE-TILE row range (MB x 16 rows) and output column, (sum, sum of squares) of the values
 // this launch stores - the consumer GroupNorm's statistics pass, skipped (norm.hip gn_finalize_cols, rows per entry = the wave tile's
 // rows). Available where the plain f32-row fast path runs (no activation, no split-K, no pre-split output) and M is a multiple of the
-// wave tile's rows; geo4d_conv_gemm_colsum_rows() tells the host which rows a launch will use (0 = not available).
-inline bool colsum_fast_ok(const geo4d_conv_gemm_t& p, int sp) {
-    return sp == 1 && p.act == 0 && !p.o_split && !p.out_nchw && p.batch == 1 && p.out_dtype == GEO4D_F32 && (p.N & 3) == 0 && (p.ldo & 3) == 0 &&
-           ((uintptr_t)p.O % 16) == 0 && (!p.R || ((p.ldr & 3) == 0 && ((uintptr_t)p.R % 16) == 0));
-}
-// The two-pass f16 type has no 256x256 instantiation (that tile spills a few registers around its K loop, and the long-K convolutions
-// the type exists for run on the phased tiles): hint 22 means the 160x320 tile there - same bits, every tile sums in the same order.
-// (GEGLU needs wave tiles a multiple of 64 columns wide, which 160x320 is not: 128x128 there.)
-template <typename T> inline int v2_effective_hint(int hint, int act = 0, int o_split = 0) { return (IsTwoPass<T>::value && hint == 22) ? (act == 2 ? 25 : 23) : hint; }
-inline int v2_wave_rows(int hint) { return hint == 22 ? 64 : hint == 23 ? 80 : hint == 25 ? 64 : (hint == 27 || hint == 28) ? 32 : 0; }
+// wave tile's rows; geo4d_conv_gemm_colsum_rows() tells the host which rows a launch will use (0 = not available; colsum_fast_ok, gemm_plan.h).
 __device__ __forceinline__ float row16_sum(float v) {      // sum over the 16 lanes lr of a 16-lane row, fixed order (DPP: xor 1, xor 2, half mirror, mirror)
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
@@ -719,13 +710,20 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
     }
 }
 
-// resident workgroups per launch = CUs x workgroups that fit a CU (queried once per kernel instantiation)
-template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>
-int launch_v2_kernel(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    constexpr int smem = v2_smem_bytes<BM, BN>();
+// ---- the launcher of the persistent generations (this one and gemm_kernel_v3.h), parameterised by the generation's kernel template and
+// LDS size. Resident workgroups per launch = CUs x workgroups that fit a CU (queried once per kernel instantiation).
+struct GenV2 {
+    template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT>
+    static auto kernel() { return conv_gemm_v2_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>; }
+    template <int BM, int BN> static constexpr int smem() { return v2_smem_bytes<BM, BN>(); }
+};
+
+template <typename G, typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>
+int launch_persistent(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    constexpr int smem = G::template smem<BM, BN>();
     static_assert(smem <= 160 * 1024, "LDS");
     static int resident = 0;
-    auto kern = conv_gemm_v2_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>;
+    auto kern = G::template kernel<T, BM, BN, WM, WN, HOT, OSPLIT>();
     if (!resident) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
             geo4d_set_error("hipFuncSetAttribute(max dynamic LDS) failed");
@@ -734,112 +732,59 @@ int launch_v2_kernel(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream)
         int dev = 0, cus = 0, occ = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, WM * WN * 64, smem) != hipSuccess || cus <= 0 || occ <= 0) {
-            geo4d_set_error("conv_gemm v2: occupancy query failed");
+            geo4d_set_error("conv_gemm: occupancy query failed");
             return GEO4D_EIO;
         }
         resident = cus * occ;
     }
     const int tiles_mn = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    const long total = (long)tiles_mn * p.batch * splits;
+    const long total = (long)tiles_mn * p.batch * plan.splits;
     // debug_ablate = 2 (tests only): 3 workgroups whatever the problem, so that small shapes walk the persistent tile loop
     const long cap = p.debug_ablate == 2 ? 3 : resident;
     const unsigned grid = (unsigned)(total < cap ? total : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, splits, tiles_mn);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn);
     GEO4D_CHECK_LAUNCH();
-    if (splits > 1) return launch_splitk_reduce<T>(p, splits, stream);
+    if (plan.splits > 1) return launch_splitk_reduce<T>(p, plan, stream);
     return GEO4D_OK;
 }
 
-// o_split (bf16x3, pre-split x pre-split operands only): the output in the producers' pre-split format - needs whole 8-column groups
-// and 16-byte aligned rows, has no split-K (the reduce kernel writes plain f32) and no residual-free restrictions otherwise
-inline bool o_split_ok(const geo4d_conv_gemm_t& p, int splits) {
-    const long nout = p.act == 2 ? (p.N >> 1) : p.N;
-    return splits == 1 && p.w_split && p.a_split && (nout & 7) == 0 && (p.ldo & 7) == 0 && ((uintptr_t)p.O % 32) == 0 &&
-           (p.batch == 1 || (p.o_bs & 7) == 0) && (!p.R || ((p.ldr & 3) == 0 && ((uintptr_t)p.R % 16) == 0 && (p.batch == 1 || (p.r_bs & 3) == 0)));
-}
-
-// o_split = 2 (the two-pass f16 type): plain f16 rows out - column bias + alpha (+ GEGLU) only, whole 8-column groups, 16-byte aligned rows
-inline bool o_f16_ok(const geo4d_conv_gemm_t& p, int splits) {
-    const long nout = p.act == 2 ? (p.N >> 1) : p.N;
-    return splits == 1 && p.w_split && p.a_split == 2 && (p.act == 0 || p.act == 2) && !p.R && !p.rowbias && !p.bias_per_row && (nout & 7) == 0 && (p.ldo & 7) == 0 &&
-           ((uintptr_t)p.O % 16) == 0 && (p.batch == 1 || (p.o_bs & 7) == 0);
-}
-
-template <typename T, int BM, int BN, int WM, int WN>
-int launch_v2_cfg(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    if (p.act == 2 && ((BN / WN / 16) % 4)) {
-        geo4d_set_error("conv_gemm v2: GEGLU needs wave tiles that are a multiple of 64 columns wide");
-        return GEO4D_EINVAL;
-    }
-    if (p.o_split && !IsX3<T>::value) { geo4d_set_error("conv_gemm: o_split is a bf16x3 option"); return GEO4D_EINVAL; }
-    if constexpr (IsTwoPass<T>::value) {       // f16x2: pre-split x pre-split; plain f32 rows out, or (o_split = 2) the f16 pre-split format
-        if (p.a_split != 2 || !p.w_split || (p.o_split && p.o_split != 2)) { geo4d_set_error("conv_gemm: f16x2 (dtype 4) takes plain f16 activation rows (a_split = 2) and a pre-split f16 weight; o_split 0 or 2 (plain f16 rows out)"); return GEO4D_EINVAL; }
-        if (p.o_split) {
-            // (the f16-row epilogue: every tile for plain rows - q | k, q | k | v, cross-attention q -, the GEGLU form on the tiles whose wave
-            // tiles are a multiple of 64 columns wide: checked at the top of this function)
-            if (o_f16_ok(p, splits)) return launch_v2_kernel<T, BM, BN, WM, WN, 2, true>(p, splits, stream);
-            geo4d_set_error("conv_gemm: o_split = 2 (plain f16 rows out) needs no split-K / residual / row biases / SiLU / GELU, stored columns % 8 == 0 and 16-byte aligned output rows");
-            return GEO4D_EINVAL;
-        }
-        return launch_v2_kernel<T, BM, BN, WM, WN, 2>(p, splits, stream);
-    } else {
+// the plan's operand-layout / output-format variant of one tile; only the variants an element type has are instantiated:
+// bf16 the generic one, bf16x3 all of them, the two-pass f16 type pre-split x pre-split with either output
+template <typename G, typename T, int BM, int BN, int WM, int WN>
+int launch_persistent_cfg(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
     if constexpr (IsX3<T>::value) {
-        if (p.o_split) {
-            if (o_split_ok(p, splits)) return launch_v2_kernel<T, BM, BN, WM, WN, 2, true>(p, splits, stream);
-            geo4d_set_error("conv_gemm: o_split needs pre-split x pre-split operands, no split-K, N % 8 == 0 and 32-byte aligned output rows");
-            return GEO4D_EINVAL;
+        if (plan.osplit) return launch_persistent<G, T, BM, BN, WM, WN, 2, true>(p, plan, stream);
+        if (plan.hot == 2) return launch_persistent<G, T, BM, BN, WM, WN, 2>(p, plan, stream);
+        if constexpr (!IsTwoPass<T>::value) {
+            if (plan.hot == 1) return launch_persistent<G, T, BM, BN, WM, WN, 1>(p, plan, stream);
         }
-        if (p.w_split && !p.a_split) return launch_v2_kernel<T, BM, BN, WM, WN, 1>(p, splits, stream);
-        if (p.w_split && p.a_split) return launch_v2_kernel<T, BM, BN, WM, WN, 2>(p, splits, stream);
     }
-    return launch_v2_kernel<T, BM, BN, WM, WN, 0>(p, splits, stream);
-    }
+    if constexpr (!IsTwoPass<T>::value) return launch_persistent<G, T, BM, BN, WM, WN, 0>(p, plan, stream);
+    return GEO4D_EINVAL;      // (unreachable: resolve() gives the two-pass type hot = 2)
 }
 
 // tile hints of the second generation (16x16x32 MFMA, register epilogue, persistent workgroups). Round 4 kept the five the measured
 // table selects (profiles/r04_gemm_census_bf16x3.log); 21 / 24 / 26 / 29 and the three-A-buffer twins 31..39 are gone:
 //   22: 256x256, 8 waves (64x128 wave tiles)    23: 160x320, 8 waves (80x80)    25: 128x128, 4 waves (64x64)
 //   27: 64x128, 4 waves (32x64)                 28: 64x64, 4 waves (32x32)
+// The two-pass f16 type has no 256x256 instantiation (that tile spills a few registers around its K loop, and the long-K convolutions
+// the type exists for run on the phased tiles): resolve() sends hint 22 to 160x320 there (GEGLU: 128x128) - same bits, every tile
+// sums in the same order.
 template <typename T>
-int launch_v2_typed(const geo4d_conv_gemm_t& p_in, hipStream_t stream) {
-    geo4d_conv_gemm_t p = p_in;
-    p.tile_hint = v2_effective_hint<T>(p_in.tile_hint, p_in.act, p_in.o_split);
-    if constexpr (std::is_same<T, float>::value || std::is_same<T, f16_t>::value) {
-        geo4d_set_error("conv_gemm: tile hints 22..28 serve bf16 / bf16x3 (the exact-f32 and the f16 modes stay on hints 0..17)");
-        return GEO4D_EINVAL;
-    } else {
-        if (p.out_nchw) {
-            geo4d_set_error("conv_gemm: tile hints 22..28 have no NCTHW epilogue");
-            return GEO4D_EINVAL;
-        }
-        int sp = 1;
-        if (p.split_k > 1) {
-            if (!p.workspace || p.act == 2 || (p.N % 8) || (size_t)p.split_k * p.batch * p.M * p.N * 4 > p.workspace_bytes ||
-                p.K / (BKC * Elem<T>::EPC) / p.split_k < 1) {
-                geo4d_set_error("conv_gemm: split_k not applicable (workspace too small / epilogue not splittable)");
-                return GEO4D_EINVAL;
-            }
-            sp = p.split_k;
-        }
-        if (p.gn_colsum && sp > 1) {      // split-K: the sums come from the reduce launch (gemm_kernel.h splitk_reduce_colsum_kernel)
-            if (!splitk_colsum_rows(p, sp)) { geo4d_set_error("conv_gemm: this split-K launch cannot emit gn_colsum (geo4d_conv_gemm_colsum_rows)"); return GEO4D_EINVAL; }
-        } else
-        if (p.gn_colsum && (!colsum_fast_ok(p, sp) || v2_wave_rows(p.tile_hint) == 0 || p.M % v2_wave_rows(p.tile_hint) || ((uintptr_t)p.gn_colsum % 16))) {
-            geo4d_set_error("conv_gemm: gn_colsum on tile hints 22..28 needs the plain f32-row epilogue (no activation / split-K / o_split / batch) and M % wave-tile rows == 0 (geo4d_conv_gemm_colsum_rows)");
-            return GEO4D_EINVAL;
-        }
-        switch (p.tile_hint) {
+int launch_v2_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    if constexpr (std::is_same<T, bf16_t>::value || IsX3<T>::value) {
+        switch (plan.hint) {
             case 22:
-                if constexpr (IsTwoPass<T>::value) return GEO4D_EINVAL;      // (unreachable: v2_effective_hint)
-                else return launch_v2_cfg<T, 256, 256, 4, 2>(p, sp, stream);
-            case 23: return launch_v2_cfg<T, 160, 320, 2, 4>(p, sp, stream);
-            case 25: return launch_v2_cfg<T, 128, 128, 2, 2>(p, sp, stream);
-            case 27: return launch_v2_cfg<T, 64, 128, 2, 2>(p, sp, stream);
-            case 28: return launch_v2_cfg<T, 64, 64, 2, 2>(p, sp, stream);
+                if constexpr (IsTwoPass<T>::value) break;
+                else return launch_persistent_cfg<GenV2, T, 256, 256, 4, 2>(p, plan, stream);
+            case 23: return launch_persistent_cfg<GenV2, T, 160, 320, 2, 4>(p, plan, stream);
+            case 25: return launch_persistent_cfg<GenV2, T, 128, 128, 2, 2>(p, plan, stream);
+            case 27: return launch_persistent_cfg<GenV2, T, 64, 128, 2, 2>(p, plan, stream);
+            case 28: return launch_persistent_cfg<GenV2, T, 64, 64, 2, 2>(p, plan, stream);
         }
-        geo4d_set_error("conv_gemm: unknown tile_hint");
-        return GEO4D_EINVAL;
     }
+    geo4d_set_error("conv_gemm: no second-generation kernel for this tile_hint and element type");      // (resolve() refuses these)
+    return GEO4D_EINVAL;
 }
 
 }  // namespace geo4d_gemm

@@ -32,11 +32,6 @@
 
 namespace geo4d_gemm {
 
-// the fall-back tiles live in the gemm_v2_*.hip translation units
-extern template int launch_v2_typed<bf16x3_t>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_v2_typed<bf16_t>(const geo4d_conv_gemm_t&, hipStream_t);
-extern template int launch_v2_typed<f16x2p_t>(const geo4d_conv_gemm_t&, hipStream_t);
-
 template <int BM, int BN>
 constexpr int v3_smem_bytes() { return 2 * (BM + BN) * PITCH; }
 
@@ -468,151 +463,29 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dummy pieces of the stream's tail must land before the LDS is released
 }
 
-// one workgroup per CU (96-155 KB of LDS); persistent over the tile list
-template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>
-int launch_v3_kernel(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    constexpr int smem = v3_smem_bytes<BM, BN>();
-    static_assert(smem <= 160 * 1024, "LDS");
-    static int resident = 0;
-    auto kern = conv_gemm_v3_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>;
-    if (!resident) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-            geo4d_set_error("hipFuncSetAttribute(max dynamic LDS) failed");
-            return GEO4D_EIO;
-        }
-        int dev = 0, cus = 0, occ = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kern, 512, smem) != hipSuccess || cus <= 0 || occ <= 0) {
-            geo4d_set_error("conv_gemm v3: occupancy query failed");
-            return GEO4D_EIO;
-        }
-        resident = cus * occ;
-    }
-    const int tiles_mn = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    const long total = (long)tiles_mn * p.batch * splits;
-    const long cap = p.debug_ablate == 2 ? 3 : resident;          // tests: 3 workgroups, so that small shapes walk the tile stream
-    const unsigned grid = (unsigned)(total < cap ? total : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, p, splits, tiles_mn);
-    GEO4D_CHECK_LAUNCH();
-    if (splits > 1) return launch_splitk_reduce<T>(p, splits, stream);
-    return GEO4D_OK;
-}
-
-template <typename T, int BM, int BN, int WM, int WN>
-int launch_v3_cfg(const geo4d_conv_gemm_t& p, int splits, hipStream_t stream) {
-    if (p.act == 2 && ((BN / WN / 16) % 4)) {
-        geo4d_set_error("conv_gemm v3: GEGLU needs wave tiles that are a multiple of 64 columns wide");
-        return GEO4D_EINVAL;
-    }
-    if (p.o_split && !IsX3<T>::value) { geo4d_set_error("conv_gemm: o_split is a bf16x3 option"); return GEO4D_EINVAL; }
-    if constexpr (IsTwoPass<T>::value) {
-        if (p.a_split != 2 || !p.w_split || (p.o_split && p.o_split != 2)) { geo4d_set_error("conv_gemm: f16x2 (dtype 4) takes plain f16 activation rows (a_split = 2) and a pre-split f16 weight; o_split 0 or 2 (plain f16 rows out)"); return GEO4D_EINVAL; }
-        if (p.o_split) {
-            // (the f16-row epilogue: every tile for plain rows - q | k, q | k | v, cross-attention q -, the GEGLU form on the tiles whose wave
-            // tiles are a multiple of 64 columns wide: checked at the top of this function)
-            if (o_f16_ok(p, splits)) return launch_v3_kernel<T, BM, BN, WM, WN, 2, true>(p, splits, stream);
-            geo4d_set_error("conv_gemm: o_split = 2 (plain f16 rows out) needs no split-K / residual / row biases / SiLU / GELU, stored columns % 8 == 0 and 16-byte aligned output rows");
-            return GEO4D_EINVAL;
-        }
-        return launch_v3_kernel<T, BM, BN, WM, WN, 2>(p, splits, stream);
-    } else {
-    if constexpr (IsX3<T>::value) {
-        if (p.o_split) {
-            if (o_split_ok(p, splits)) return launch_v3_kernel<T, BM, BN, WM, WN, 2, true>(p, splits, stream);
-            geo4d_set_error("conv_gemm: o_split needs pre-split x pre-split operands, no split-K, N % 8 == 0 and 32-byte aligned output rows");
-            return GEO4D_EINVAL;
-        }
-        if (p.w_split && !p.a_split) return launch_v3_kernel<T, BM, BN, WM, WN, 1>(p, splits, stream);
-        if (p.w_split && p.a_split) return launch_v3_kernel<T, BM, BN, WM, WN, 2>(p, splits, stream);
-    }
-    return launch_v3_kernel<T, BM, BN, WM, WN, 0>(p, splits, stream);
-    }
-}
+// one workgroup per CU (96-155 KB of LDS); persistent over the tile list (launch_persistent, gemm_kernel_v2.h)
+struct GenV3 {
+    template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT>
+    static auto kernel() { return conv_gemm_v3_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>; }
+    template <int BM, int BN> static constexpr int smem() { return v3_smem_bytes<BM, BN>(); }
+};
 
 // tile hints 71..74: phased K loop on 8 waves (2 x 4), one workgroup per CU
 //   71: 192x256 (wave tiles 96x64)   72: 160x320 (80x80)   73: 256x128 (128x32)   74: 128x256 (64x64)
 // (256x256 does not fit: 128 accumulators + the four fragment sets of the prefetching walk spill)
-// Launches the phased stream cannot take (an odd number or fewer than 4 K slabs per tile, an uneven split-K, outputs that are not 4-element aligned,
-// nearest-upsampling gathers, operands beyond the 2 GB buffer window) fall back to the second-generation tile of the same shape.
-inline int v3_wave_rows(int hint) { return hint == 71 ? 96 : hint == 72 ? 80 : hint == 73 ? 128 : 64; }
-inline int v3_fallback_hint(int hint) { return hint == 71 ? 22 : hint == 72 ? 23 : 25; }
-// does the phased stream take this launch (else its second-generation twin does)?
+// Launches the phased stream cannot take (v3_native, gemm_plan.h) arrive as the second-generation tile of the same shape instead.
 template <typename T>
-bool v3_native(const geo4d_conv_gemm_t& p, int sp) {
-    const int nslab = p.K / (BKC * Elem<T>::EPC);
-    // the phased kernel carries the vector-store epilogue only (its scalar fallback costs ~900 spilled registers there)
-    const bool geglu = sp == 1 && p.act == 2;
-    const long nout = geglu ? (p.N >> 1) : p.N;
-    const long oesz = (sp > 1 || p.out_dtype == GEO4D_F32) ? 4 : 2;
-    bool vec_ok = (nout & 3) == 0;
-    if (sp > 1) {
-        vec_ok = vec_ok && ((uintptr_t)p.workspace % 16) == 0;
-    } else {
-        vec_ok = vec_ok && (p.ldo & 3) == 0 && ((uintptr_t)p.O % (4 * oesz)) == 0 && (p.batch == 1 || (p.o_bs & 3) == 0);
-        if (p.R) vec_ok = vec_ok && (p.ldr & 3) == 0 && ((uintptr_t)p.R % (4 * oesz)) == 0 && (p.batch == 1 || (p.r_bs & 3) == 0);
+int launch_v3_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    if constexpr (std::is_same<T, bf16_t>::value || IsX3<T>::value) {
+        switch (plan.hint) {
+            case 71: return launch_persistent_cfg<GenV3, T, 192, 256, 2, 4>(p, plan, stream);
+            case 72: return launch_persistent_cfg<GenV3, T, 160, 320, 2, 4>(p, plan, stream);
+            case 73: return launch_persistent_cfg<GenV3, T, 256, 128, 2, 4>(p, plan, stream);
+            case 74: return launch_persistent_cfg<GenV3, T, 128, 256, 2, 4>(p, plan, stream);
+        }
     }
-    // the staging side addresses each operand through a 2 GB buffer window per tile (see the kernel): nearest-upsampling gathers have
-    // no uniform tap offsets, and a tile's rows plus its taps must stay inside the window
-    const long esz = 16 / Elem<T>::EPC, esz_a = IsTwoPass<T>::value ? 2 : esz;
-    const long frames = 256 / ((long)p.Hout * p.Wout) + 2 + p.KT;
-    const bool window_ok = p.ups == 1 && frames * p.Hin * p.Win * p.lda * esz_a < (1L << 31) && (320L * p.ldw + p.K) * esz < (1L << 31);
-    return !(nslab % sp || ((nslab / sp) & 1) || nslab / sp < 4 || !vec_ok || !window_ok);
-}
-// rows per gn_colsum entry of the launch `p` describes (tile_hint >= 21), 0 = this launch cannot emit the sums
-template <typename T>
-int colsum_rows_v23(const geo4d_conv_gemm_t& p) {
-    const int sp = p.split_k > 1 ? p.split_k : 1;
-    if (sp > 1) return (p.gn_colsum == nullptr || ((uintptr_t)p.gn_colsum % 8) == 0) ? splitk_colsum_rows(p, sp) : 0;     // from the reduce launch
-    int rows = 0;
-    if (p.tile_hint >= 71 && p.tile_hint <= 74) rows = v3_native<T>(p, sp) ? v3_wave_rows(p.tile_hint) : v2_wave_rows(v2_effective_hint<T>(v3_fallback_hint(p.tile_hint)));
-    else rows = v2_wave_rows(v2_effective_hint<T>(p.tile_hint));
-    if (rows == 0 || !colsum_fast_ok(p, sp) || p.M % rows) return 0;
-    return rows;
-}
-
-template <typename T>
-int launch_v3_typed(const geo4d_conv_gemm_t& p, hipStream_t stream) {
-    if constexpr (std::is_same<T, float>::value || std::is_same<T, f16_t>::value) {
-        geo4d_set_error("conv_gemm: tile hints 71..74 serve bf16 / bf16x3 (the exact-f32 and the f16 modes stay on hints 0..17)");
-        return GEO4D_EINVAL;
-    } else {
-        if (p.out_nchw) {
-            geo4d_set_error("conv_gemm: tile hints 71..74 have no NCTHW epilogue");
-            return GEO4D_EINVAL;
-        }
-        int sp = 1;
-        const int nslab = p.K / (BKC * Elem<T>::EPC);
-        if (p.split_k > 1) {
-            if (!p.workspace || p.act == 2 || (p.N % 8) || (size_t)p.split_k * p.batch * p.M * p.N * 4 > p.workspace_bytes || nslab / p.split_k < 1) {
-                geo4d_set_error("conv_gemm: split_k not applicable (workspace too small / epilogue not splittable)");
-                return GEO4D_EINVAL;
-            }
-            sp = p.split_k;
-        }
-        if (p.tile_hint < 71 || p.tile_hint > 74) {
-            geo4d_set_error("conv_gemm: unknown tile_hint");
-            return GEO4D_EINVAL;
-        }
-        if (!v3_native<T>(p, sp)) {
-            geo4d_conv_gemm_t q = p;
-            q.tile_hint = v3_fallback_hint(p.tile_hint);      // (every tile sums in the same order: same bits)
-            return launch_v2_typed<T>(q, stream);
-        }
-        if (p.gn_colsum && sp > 1) {      // split-K: the sums come from the reduce launch (gemm_kernel.h splitk_reduce_colsum_kernel)
-            if (!splitk_colsum_rows(p, sp)) { geo4d_set_error("conv_gemm: this split-K launch cannot emit gn_colsum (geo4d_conv_gemm_colsum_rows)"); return GEO4D_EINVAL; }
-        } else
-        if (p.gn_colsum && (!colsum_fast_ok(p, sp) || p.M % v3_wave_rows(p.tile_hint) || ((uintptr_t)p.gn_colsum % 16))) {
-            geo4d_set_error("conv_gemm: gn_colsum on tile hints 71..74 needs the plain f32-row epilogue (no activation / split-K / o_split / batch) and M % wave-tile rows == 0 (geo4d_conv_gemm_colsum_rows)");
-            return GEO4D_EINVAL;
-        }
-        switch (p.tile_hint) {
-            case 71: return launch_v3_cfg<T, 192, 256, 2, 4>(p, sp, stream);
-            case 72: return launch_v3_cfg<T, 160, 320, 2, 4>(p, sp, stream);
-            case 73: return launch_v3_cfg<T, 256, 128, 2, 4>(p, sp, stream);
-            case 74: return launch_v3_cfg<T, 128, 256, 2, 4>(p, sp, stream);
-        }
-        return GEO4D_EINVAL;
-    }
+    geo4d_set_error("conv_gemm: no third-generation kernel for this tile_hint and element type");      // (resolve() refuses these)
+    return GEO4D_EINVAL;
 }
 
 #undef GEO4D_V3_BAR

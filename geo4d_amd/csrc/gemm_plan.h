@@ -1,0 +1,205 @@
+// geo4d_amd/csrc/gemm_plan.h — the host-side planner of geo4d_conv_gemm: ONE tile table and ONE function, resolve(), that turns a
+// launch descriptor into the kernel variant that runs it. geo4d_conv_gemm launches what the plan says, geo4d_conv_gemm_colsum_rows
+// answers from the same plan, so the two cannot disagree. Host code only: no HIP call, no allocation, no device code.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include "geo4d_hip.h"
+
+namespace geo4d_gemm {
+
+constexpr int KSLAB_BYTES = 128;      // K bytes per operand row and pipeline stage (8 x 16-byte chunks) in every generation
+
+// The hint number space: first generation (gemm_kernel.h) below 21, second (gemm_kernel_v2.h) 21..70, third (gemm_kernel_v3.h) from 71.
+constexpr int generation(int hint) { return hint >= 71 ? 3 : hint >= 21 ? 2 : 1; }
+
+// One row per tile hint: workgroup tile BM x BN on WM x WN waves, and the second-generation tile that takes the launch when this one
+// cannot (`alt`; `alt_geglu` where the launch is a GEGLU, which needs wave tiles a multiple of 64 columns wide):
+//   first generation  - a pre-split output (o_split), which only the register epilogue of the later generations writes;
+//   third generation  - a launch the phased stream cannot take (v3_native); every tile sums in the same order, so the bits are the same;
+//   22                - the two-pass f16 type, which has no 256x256 instantiation (that tile spills around its K loop there).
+struct Tile {
+    int hint, bm, bn, wm, wn, alt, alt_geglu;
+    constexpr bool geglu() const { return (bn / wn) % 64 == 0; }
+    // rows of the output one gn_colsum entry covers: 32 from the first generation's LDS epilogue, the wave tile's rows from the register epilogue
+    constexpr int colsum_rows() const { return generation(hint) == 1 ? 32 : bm / wm; }
+};
+constexpr Tile TILES[] = {
+    {1, 128, 128, 2, 2, 25, 25},  {2, 128, 64, 4, 1, 25, 25},   {3, 64, 128, 2, 2, 27, 27},   {4, 64, 64, 2, 2, 28, 27},    {5, 128, 32, 4, 1, 25, 25},
+    {11, 256, 128, 4, 2, 22, 22}, {13, 256, 256, 4, 2, 22, 22}, {16, 160, 320, 5, 2, 23, 22}, {17, 160, 160, 5, 1, 25, 25},
+    {22, 256, 256, 4, 2, 23, 25}, {23, 160, 320, 2, 4, 0, 0},   {25, 128, 128, 2, 2, 0, 0},   {27, 64, 128, 2, 2, 0, 0},    {28, 64, 64, 2, 2, 0, 0},
+    {71, 192, 256, 2, 4, 22, 22}, {72, 160, 320, 2, 4, 23, 23}, {73, 256, 128, 2, 4, 25, 25}, {74, 128, 256, 2, 4, 25, 25},
+};
+constexpr int N_SCORED = 5;                      // hints 1..5 = TILES[0..4]: the tiles the library scores itself when the hint is 0
+constexpr float SCORED_EFF[N_SCORED] = {1.00f, 0.85f, 0.80f, 0.62f, 0.50f};      // their MFMA efficiency relative to 128x128
+constexpr int V2_DEFAULT = 25;                   // where a pre-split output goes from a hint without a row
+// two-pass f16 (dtype 4) without a hint: small problems, large ones, large GEGLUs
+constexpr int TWO_PASS_SMALL = 25, TWO_PASS_LARGE = 72, TWO_PASS_LARGE_GEGLU = 71;
+
+inline const Tile* find_tile(int hint) {
+    for (const Tile& t : TILES)
+        if (t.hint == hint) return &t;
+    return nullptr;
+}
+
+struct Plan {
+    int hint = 0;               // the tile that runs (a row of TILES) after defaults, redirects and fall-backs
+    int splits = 1;             // gridDim.z / K slices; > 1 is followed by the reduce launch
+    int hot = 0;                // operand layout fixed at compile time (4-byte types): 0 generic, 1 raw A x split W, 2 split A x split W
+    bool osplit = false;        // the epilogue writes the producers' pre-split format (o_split = 1) / plain f16 rows (o_split = 2)
+    int colsum_rows = 0;        // rows per gn_colsum entry this launch emits (would emit, where gn_colsum is null); 0 = it cannot
+    const char* error = nullptr;
+};
+
+inline bool aligned(const void* ptr, int bytes) { return ((uintptr_t)ptr % bytes) == 0; }
+
+// gn_colsum of the first generation: one entry per 32 rows from the vectorised LDS epilogue
+inline bool colsum_gen1_ok(const geo4d_conv_gemm_t& p, int split_k) {
+    const int oesz = p.out_dtype == GEO4D_F32 ? 4 : 2;
+    return !(p.M % 32) && !(p.N % 8) && !p.out_nchw && p.act != 2 && p.batch == 1 && split_k == 1 && !((p.ldo * oesz) % 16) && aligned(p.O, 16) &&
+           (!p.R || (!((p.ldr * oesz) % 16) && aligned(p.R, 16)));
+}
+// gn_colsum from the register epilogue's fast path: where the plain f32-row path runs (no activation, no split-K, no pre-split output)
+inline bool colsum_fast_ok(const geo4d_conv_gemm_t& p, int sp) {
+    return sp == 1 && p.act == 0 && !p.o_split && !p.out_nchw && p.batch == 1 && p.out_dtype == GEO4D_F32 && (p.N & 3) == 0 && (p.ldo & 3) == 0 &&
+           aligned(p.O, 16) && (!p.R || ((p.ldr & 3) == 0 && aligned(p.R, 16)));
+}
+// rows per gn_colsum entry a split-K launch of the second / third generation emits through splitk_reduce_colsum_kernel (0 = it cannot): 32, or 8
+// where a frame's rows are a multiple of 8 but not of 32 (the 5 x 8 level: per-frame GroupNorms need blocks that do not straddle frames)
+inline int splitk_colsum_rows(const geo4d_conv_gemm_t& p, int sp) {
+    if (sp <= 1 || p.batch != 1 || p.act != 0 || p.o_split || p.out_nchw || p.out_dtype != GEO4D_F32 || p.bias_per_row || (p.ldo & 3) || !aligned(p.O, 16) ||
+        (p.R && !aligned(p.R, 4))) return 0;
+    const int hw = p.Hout * p.Wout;
+    if (hw % 32 == 0 && p.M % 32 == 0 && p.N % 64 == 0) return 32;
+    if (hw % 8 == 0 && p.M % 8 == 0 && p.N % 256 == 0) return 8;
+    return 0;
+}
+
+// o_split = 1 (bf16x3, pre-split x pre-split operands only): the output in the producers' pre-split format - needs whole 8-column groups
+// and 32-byte aligned rows, has no split-K (the reduce kernel writes plain f32)
+inline bool o_split_ok(const geo4d_conv_gemm_t& p, int splits) {
+    const long nout = p.act == 2 ? (p.N >> 1) : p.N;
+    return splits == 1 && p.w_split && p.a_split && (nout & 7) == 0 && (p.ldo & 7) == 0 && aligned(p.O, 32) &&
+           (p.batch == 1 || (p.o_bs & 7) == 0) && (!p.R || ((p.ldr & 3) == 0 && aligned(p.R, 16) && (p.batch == 1 || (p.r_bs & 3) == 0)));
+}
+// o_split = 2 (the two-pass f16 type): plain f16 rows out - column bias + alpha (+ GEGLU) only, whole 8-column groups, 16-byte aligned rows
+inline bool o_f16_ok(const geo4d_conv_gemm_t& p, int splits) {
+    const long nout = p.act == 2 ? (p.N >> 1) : p.N;
+    return splits == 1 && p.w_split && p.a_split == 2 && (p.act == 0 || p.act == 2) && !p.R && !p.rowbias && !p.bias_per_row && (nout & 7) == 0 && (p.ldo & 7) == 0 &&
+           aligned(p.O, 16) && (p.batch == 1 || (p.o_bs & 7) == 0);
+}
+
+// Does the third generation's phased stream take this launch? Not an odd number or fewer than 4 K slabs per tile, an uneven split-K,
+// outputs that are not 4-element aligned, nearest-upsampling gathers, operands beyond the 2 GB buffer window.
+inline bool v3_native(const geo4d_conv_gemm_t& p, int sp, int nslab, long esz, long esz_a) {
+    // the phased kernel carries the vector-store epilogue only (its scalar fallback costs ~900 spilled registers there)
+    const bool geglu = sp == 1 && p.act == 2;
+    const long nout = geglu ? (p.N >> 1) : p.N;
+    const long oesz = (sp > 1 || p.out_dtype == GEO4D_F32) ? 4 : 2;
+    bool vec_ok = (nout & 3) == 0;
+    if (sp > 1) {
+        vec_ok = vec_ok && aligned(p.workspace, 16);
+    } else {
+        vec_ok = vec_ok && (p.ldo & 3) == 0 && aligned(p.O, 4 * oesz) && (p.batch == 1 || (p.o_bs & 3) == 0);
+        if (p.R) vec_ok = vec_ok && (p.ldr & 3) == 0 && aligned(p.R, 4 * oesz) && (p.batch == 1 || (p.r_bs & 3) == 0);
+    }
+    // the staging side addresses each operand through a 2 GB buffer window per tile (see the kernel): nearest-upsampling gathers have
+    // no uniform tap offsets, and a tile's rows plus its taps must stay inside the window
+    const long frames = 256 / ((long)p.Hout * p.Wout) + 2 + p.KT;
+    const bool window_ok = p.ups == 1 && frames * p.Hin * p.Win * p.lda * esz_a < (1L << 31) && (320L * p.ldw + p.K) * esz < (1L << 31);
+    return !(nslab % sp || ((nslab / sp) & 1) || nslab / sp < 4 || !vec_ok || !window_ok);
+}
+
+// Tile choice without a hint (first generation): score = MFMA efficiency of the tile shape x useful fraction x how full the last wave of
+// workgroups is (2 workgroups fit per CU by LDS => 512 slots on 256 CUs). Split-K multiplies the workgroup count
+// when M x N alone cannot fill the chip and K is deep enough to amortise the extra fp32 slab traffic.
+// `hint` 0 scores all of TILES[0..4], 1..5 only that tile; false = nothing applies.
+inline bool score_tiles(const geo4d_conv_gemm_t& p, int nslab, int& hint, int& splits) {
+    const bool can_split = p.workspace && p.act != 2 && !p.out_nchw && (p.N % 8) == 0 && p.split_k != 1;
+    int best = -1, best_split = 1;
+    float best_score = -1.f;
+    for (int i = 0; i < N_SCORED; ++i) {
+        const Tile& c = TILES[i];
+        if (p.act == 2 && !c.geglu()) continue;
+        if (hint && c.hint != hint) continue;
+        const double tm = (p.M + c.bm - 1) / c.bm, tn = (p.N + c.bn - 1) / c.bn;
+        const double tiles = tm * tn * p.batch;
+        const double useful = ((double)p.M * p.N * p.batch) / (tiles * c.bm * c.bn);
+        for (int s = 1; s <= 16; s *= 2) {
+            if (s > 1 && (!can_split || nslab / s < 8)) break;
+            if (p.split_k > 1 && s != p.split_k) continue;
+            if (s > 1 && (size_t)s * p.batch * p.M * p.N * 4 > p.workspace_bytes) break;
+            const double wgs = tiles * s;
+            const double waves = (double)(long)((wgs + 511) / 512);
+            const double fill = wgs / (waves * 512);
+            const double split_cost = s > 1 ? 0.92 : 1.0;      // slab write + reduce kernel
+            const float score = (float)(SCORED_EFF[i] * useful * (0.30 + 0.70 * fill) * split_cost);
+            if (score > best_score) { best_score = score; best = i; best_split = s; }
+        }
+    }
+    if (best < 0) return false;
+    hint = TILES[best].hint;
+    splits = best_split;
+    return true;
+}
+
+// The kernel variant the (validated) descriptor `p` becomes, or why it cannot run. The gn_colsum pointer only decides whether a launch
+// that cannot emit the sums is an error; colsum_rows is filled either way.
+inline Plan resolve(const geo4d_conv_gemm_t& p) {
+    Plan pl;
+    auto refuse = [&pl](const char* why) { pl.error = why; pl.colsum_rows = 0; return pl; };
+    const bool two_pass = p.dtype == GEO4D_F16X2, wide = two_pass || p.dtype == GEO4D_BF16X3;
+    const long esz = (wide || p.dtype == GEO4D_F32) ? 4 : 2, esz_a = two_pass ? 2 : esz;
+    const int nslab = p.K / (KSLAB_BYTES / (int)esz);
+    int hint = p.tile_hint, split_k = p.split_k;
+    if (two_pass) {      // second / third generation only, never split by default
+        if (hint == 0) hint = p.M < 4096 ? TWO_PASS_SMALL : p.act == 2 ? TWO_PASS_LARGE_GEGLU : TWO_PASS_LARGE;
+        if (split_k == 0) split_k = 1;
+    }
+    const Tile* t = find_tile(hint);
+    if (generation(hint) == 1 && p.o_split) {
+        hint = !t ? V2_DEFAULT : p.act == 2 ? t->alt_geglu : t->alt;
+        t = find_tile(hint);
+    }
+    int gen = generation(hint);
+    if (gen > 1 && !wide && p.dtype != GEO4D_BF16)
+        return refuse("conv_gemm: tile hints 22..28 and 71..74 serve bf16 / bf16x3 / f16x2 (the exact-f32 and the f16 modes stay on hints 0..17)");
+    if (gen > 1 && p.out_nchw) return refuse("conv_gemm: tile hints 22..28 and 71..74 have no NCTHW epilogue");
+    if (gen == 1 && hint <= N_SCORED) {
+        if (!score_tiles(p, nslab, hint, pl.splits)) return refuse("conv_gemm: no tile configuration (split_k / tile_hint not applicable to this problem?)");
+        t = find_tile(hint);
+    } else if (split_k > 1) {
+        if (!p.workspace || p.act == 2 || (gen == 1 && p.out_nchw) || (p.N % 8) || (size_t)split_k * p.batch * p.M * p.N * 4 > p.workspace_bytes || nslab / split_k < 1)
+            return refuse("conv_gemm: split_k not applicable (workspace too small / epilogue not splittable)");
+        pl.splits = split_k;
+    }
+    if (!t) return refuse("conv_gemm: unknown tile_hint");
+    if (gen == 3 && !v3_native(p, pl.splits, nslab, esz, esz_a)) {
+        t = find_tile(t->alt);
+        gen = 2;
+    }
+    if (gen == 2 && two_pass && t->alt) t = find_tile(p.act == 2 ? t->alt_geglu : t->alt);
+    pl.hint = t->hint;
+    if (p.act == 2 && !t->geglu()) return refuse("conv_gemm: GEGLU needs wave tiles that are a multiple of 64 columns wide");
+    if (p.o_split) {
+        if (!wide) return refuse("conv_gemm: o_split is a bf16x3 / f16x2 option");
+        if (two_pass ? !o_f16_ok(p, pl.splits) : !o_split_ok(p, pl.splits))
+            return refuse(two_pass ? "conv_gemm: o_split = 2 (plain f16 rows out) needs no split-K / residual / row biases / SiLU / GELU, stored columns % 8 == 0 and 16-byte aligned output rows"
+                                   : "conv_gemm: o_split needs pre-split x pre-split operands, no split-K, N % 8 == 0 and 32-byte aligned output rows");
+        pl.hot = 2;
+        pl.osplit = true;
+    } else if (two_pass) {
+        pl.hot = 2;
+    } else if (wide && p.w_split) {
+        pl.hot = p.a_split ? 2 : 1;
+    }
+    if (gen == 1) pl.colsum_rows = colsum_gen1_ok(p, split_k) ? t->colsum_rows() : 0;
+    else if (pl.splits > 1) pl.colsum_rows = splitk_colsum_rows(p, pl.splits);      // from the reduce launch
+    else pl.colsum_rows = (colsum_fast_ok(p, 1) && p.M % t->colsum_rows() == 0) ? t->colsum_rows() : 0;
+    if (p.gn_colsum && (!pl.colsum_rows || (pl.splits == 1 && !aligned(p.gn_colsum, 16))))
+        return refuse("conv_gemm: this launch cannot emit gn_colsum (geo4d_conv_gemm_colsum_rows): it needs a row-major 16-byte aligned output, batch 1, no GEGLU, "
+                      "M a multiple of the rows per entry; first generation: no split-K; later generations: f32 rows, no activation");
+    return pl;
+}
+
+}  // namespace geo4d_gemm

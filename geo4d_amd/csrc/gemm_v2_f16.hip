@@ -3,5 +3,5 @@
 #include "gemm_kernel_v2.h"
 
 namespace geo4d_gemm {
-template int launch_v2_typed<f16_t>(const geo4d_conv_gemm_t&, hipStream_t);
+template int launch_v2_typed<f16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
 }  // namespace geo4d_gemm

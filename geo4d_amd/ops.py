@@ -168,7 +168,21 @@ _CANDIDATES = [(1, 1), (2, 1), (3, 1), (4, 1), (11, 1), (13, 1), (16, 1), (17, 1
                # Splits that do not divide the K slabs evenly run on the second-generation twin inside the library.
                (71, 1), (72, 1), (73, 1), (74, 1), (71, 2), (72, 2), (73, 2), (74, 2), (71, 3), (72, 3), (73, 3), (74, 3), (71, 4), (73, 4), (74, 4),
                (71, 5), (73, 5), (74, 5), (73, 6), (74, 6), (73, 8), (74, 8), (73, 10), (74, 10)]
-_VALID_HINTS = {t for t, _ in _CANDIDATES} | {0}
+# One row per tile hint of the library (include/geo4d_hip.h; the library's own table is csrc/gemm_plan.h): hint -> (kernel generation,
+# the nearest tile whose wave tiles are a multiple of 64 columns wide - where a GEGLU that writes f16 rows goes; itself if it is one or
+# the generation has no such launch)
+_TILES = {1: (1, 1), 2: (1, 2), 3: (1, 3), 4: (1, 4), 5: (1, 5), 11: (1, 11), 13: (1, 13), 16: (1, 16), 17: (1, 17),
+          22: (2, 25), 23: (2, 25), 25: (2, 25), 27: (2, 27), 28: (2, 27),
+          71: (3, 71), 72: (3, 71), 73: (3, 74), 74: (3, 74)}
+assert {t for t, _ in _CANDIDATES} == set(_TILES)
+_VALID_HINTS = set(_TILES) | {0}
+
+
+def _generation(tile_hint):
+    """1, 2 or 3; hint 0 (the library's own choice) and hints without a row count as the first generation."""
+    return _TILES.get(tile_hint, (1, tile_hint))[0]
+
+
 AUTOTUNE = _os.environ.get("GEO4D_AUTOTUNE", "1") != "0"
 # GEMM epilogues can emit the next GroupNorm's column sums (gn_stats=True call sites), which removes that GroupNorm's statistics pass
 # over the tensor. 1 (default since round 4): where the second / third generation's fast epilogue does it per wave-tile row range at
@@ -187,8 +201,8 @@ def _env_level(name, default):
 
 
 GN_FUSED_STATS = _env_level("GEO4D_GN_FUSED", 1)
-SPLITK_COLSUM = _env_level("GEO4D_SPLITK_COLSUM", 1)
-TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)     # tools/tune_gemm.py: measure a pre-split launch under its OWN key instead of borrowing the raw-activation entry of the same shape       # 0: split-K launches leave the GroupNorm statistics to the GroupNorm (the state before round 6)
+SPLITK_COLSUM = _env_level("GEO4D_SPLITK_COLSUM", 1)     # 0: split-K launches leave the GroupNorm statistics to the GroupNorm (the state before round 6)
+TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)     # tools/tune_gemm.py: measure a pre-split launch under its OWN key instead of borrowing the raw-activation entry of the same shape
 TUNE_LOG = []          # (key, chosen (tile, split), ms per launch, finalists) of every shape autotuned in this process (tools/tune_gemm.py prints it)
 DEBUG_ABLATE = _env_level("GEO4D_DEBUG_ABLATE", 0)       # tests / A-B runs: 2 = three persistent workgroups; 16 + g = tile order with GROUP_M = g (17 = column-fastest)
 GEMM_TIMELINE = None   # set to a list to have conv_gemm bracket every launch with HIP events: (flops, start, end, MFMA passes per product)
@@ -247,6 +261,36 @@ def _autotune(launch, key):
     _tune_table()[key] = best
     TUNE_LOG.append((key, best, best_of[best], [(t, s, round(v * 1e3, 1)) for (t, s), v in sorted(best_of.items(), key=lambda kv: kv[1])]))
     return best
+
+
+def _tuned_config(table, key, code, a_split, w_split, o_split, may_measure):
+    """(tile_hint, split_k) of the launch `key` from the tuning table - its own entry, or the entry of a launch with the same tile geometry -
+    or None: no entry applies (the caller measures now if that is allowed, else the library chooses). `may_measure()`: whether timing
+    candidates is allowed now (AUTOTUNE on, no capture running); only asked when `key` itself has no entry."""
+    cfg = table.get(key)
+    if cfg is None and code == BF16X3 and a_split and w_split and not (TUNE_EXACT and may_measure()):
+        # pre-split activations: same tile geometry as the raw-activation launch of the same shape (table measured on those)
+        base = key.split("|x")[0]
+        cfg = (table.get(base + "|x11") if o_split else None) or table.get(base + "|x01") or table.get(base + "|x10")
+        if cfg is not None and o_split and cfg[1] > 1:
+            # the pre-split output has no split-K form (the reduce kernel writes plain f32): measure this launch on its own when
+            # that is allowed, else keep the tile and drop the split
+            cfg = None if may_measure() else (cfg[0], 1)
+    if cfg is None and code == F16X2 and not may_measure():
+        # no entry and no measuring now: the bf16x3 launch of the same shape is the same tile geometry and the same bytes
+        cfg = table.get("3" + key[1:])
+        if cfg is not None and _generation(cfg[0]) == 1:
+            cfg = None                   # (the two-pass kernels exist on the second / third generation only: library default)
+        elif cfg is not None and o_split and cfg[1] > 1:
+            cfg = (cfg[0], 1)            # (a pre-split output has no split-K form)
+    return cfg
+
+
+def _f16_rows_config(cfg, act):
+    """The f16-row epilogue (o_split = 2) has no split-K, and its GEGLU form lives on the tiles whose wave tiles are a multiple of 64
+    columns wide: a tile measured on, or borrowed from, another launch goes to its nearest such neighbour."""
+    tile_hint, split_k = cfg
+    return (_TILES.get(tile_hint, (1, tile_hint))[1] if act == 2 else tile_hint), min(split_k, 1)
 
 
 def workspace(device):
@@ -346,43 +390,27 @@ def conv_gemm(a, w, out, *, M, N, K, Cin, lda, ldw, ldo, T=1, Hin=1, Win=1, Hout
         key = f"{p.dtype}/{p.out_dtype}|{M}x{N}x{K}|c{Cin}|t{KT}{KH}{KW}s{stride}u{ups}|a{act}r{int(residual is not None)}n{int(out_nchw)}|b{batch}"
         if code in (BF16X3, F16X2):
             key += f"|x{int(bool(a_split))}{int(w_split)}" + ("o" if p.o_split else "")       # (dtype 4's "o" = its f16 rows)
-        cfg = _tune_table().get(key)
-        if cfg is None and code == BF16X3 and a_split and w_split and not (TUNE_EXACT and AUTOTUNE and not torch.cuda.is_current_stream_capturing()):
-            # pre-split activations: same tile geometry as the raw-activation launch of the same shape (table measured on those)
-            base = key.split("|x")[0]
-            cfg = (_tune_table().get(base + "|x11") if p.o_split else None) or _tune_table().get(base + "|x01") or _tune_table().get(base + "|x10")
-            if cfg is not None and p.o_split and cfg[1] > 1:
-                # the pre-split output has no split-K form (the reduce kernel writes plain f32): measure this launch on its own when
-                # that is allowed, else keep the tile and drop the split
-                cfg = None if (AUTOTUNE and not torch.cuda.is_current_stream_capturing()) else (cfg[0], 1)
-        if cfg is None and code == F16X2 and not (AUTOTUNE and not torch.cuda.is_current_stream_capturing()):
-            # no entry and no measuring now: the bf16x3 launch of the same shape is the same tile geometry and the same bytes
-            cfg = _tune_table().get("3" + key[1:])
-            if cfg is not None and cfg[0] < 22:
-                cfg = None                   # (the two-pass kernels exist on the second / third generation only: library default)
-            elif cfg is not None and p.o_split and cfg[1] > 1:
-                cfg = (cfg[0], 1)            # (a pre-split output has no split-K form)
-        if cfg is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+
+        def may_measure():
+            return AUTOTUNE and not torch.cuda.is_current_stream_capturing()
+        cfg = _tuned_config(_tune_table(), key, code, a_split, w_split, p.o_split, may_measure)
+        if cfg is None and may_measure():
             cfg = _autotune(launch, key)
         tile_hint, split_k = cfg if cfg is not None else (0, 0)
         if p.o_split == 2:
-            # the f16-row epilogue has no split-K; its GEGLU form lives on the tiles whose wave tiles are a multiple of 64 columns wide
-            # (25, 27, 71, 74): a tile borrowed from the bf16x3 entry of the same shape goes to its nearest such neighbour
-            split_k = min(split_k, 1)
-            if act == 2:
-                tile_hint = {22: 25, 23: 25, 28: 27, 72: 71, 73: 74}.get(tile_hint, tile_hint)
+            tile_hint, split_k = _f16_rows_config((tile_hint, split_k), act)
     if gn_stats and GN_FUSED_STATS and not p.o_split and batch == 1 and out.dim() == 2 and out.shape[0] == M:
         # the consumer GroupNorm's statistics pass, for free: per row block and column (sum, sum of squares) from the epilogue. The library
         # says how many rows one entry of THIS launch covers (32 for the first generation, the wave tile's rows for the second / third; 0 =
         # this configuration cannot emit them - split-K, activations, unaligned rows: the GroupNorm then runs its own pass)
         p.tile_hint, p.split_k = tile_hint, split_k
-        rows = lib.geo4d_conv_gemm_colsum_rows(C.byref(p)) if (tile_hint >= 21 or int(GN_FUSED_STATS) >= 2) else 0
+        rows = lib.geo4d_conv_gemm_colsum_rows(C.byref(p)) if (_generation(tile_hint) > 1 or int(GN_FUSED_STATS) >= 2) else 0
         if split_k > 1 and not SPLITK_COLSUM:      # (A/B switch: round 6 lets a split-K launch's reduce kernel emit the sums)
             rows = 0
         if rows == 0 and int(GN_FUSED_STATS) >= 2:
             # mode 2 (A/B, tests): a tuned configuration that cannot emit the sums (split-K; a second / third generation tile on 16-bit rows)
             # gives way to an un-split first-generation launch, as this path did before round 4
-            p.tile_hint, p.split_k = (tile_hint if tile_hint < 21 else 0), 1
+            p.tile_hint, p.split_k = (tile_hint if _generation(tile_hint) == 1 else 0), 1
             rows = lib.geo4d_conv_gemm_colsum_rows(C.byref(p))
             if rows > 0:
                 tile_hint, split_k = p.tile_hint, 1

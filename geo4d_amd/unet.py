@@ -165,8 +165,8 @@ def layer_shapes(add, L, c):
 
 
 PRESPLIT = os.environ.get("GEO4D_X3_PRESPLIT", "1") != "0"
-PRESPLIT_UP = os.environ.get("GEO4D_X3_PRESPLIT_UP", "1") != "0"
-FUSED_CONCAT = os.environ.get("GEO4D_FUSED_CONCAT", "1") != "0"     # the skip concatenations' producers write into the consumer's buffer (no concat_channels launches); 0: A/B      # A/B switch of round 6: pre-split pass in front of the Upsample convolutions (U-Net and VAE)
+PRESPLIT_UP = os.environ.get("GEO4D_X3_PRESPLIT_UP", "1") != "0"     # A/B switch of round 6: pre-split pass in front of the Upsample convolutions (U-Net and VAE)
+FUSED_CONCAT = os.environ.get("GEO4D_FUSED_CONCAT", "1") != "0"     # the skip concatenations' producers write into the consumer's buffer (no concat_channels launches); 0: A/B
 
 
 # ------------------------------------------------------------------------------------------------------

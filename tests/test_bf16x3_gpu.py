@@ -238,3 +238,31 @@ def test_groupnorm_statistics_from_the_fast_epilogue(dev, tile, F, fps):
             assert ((fused - ref).norm() / ref.norm()).item() < 2e-5 and ((fused - plain).norm() / plain.norm()).item() < 1e-5, (tile, list(kw))
     finally:
         ops.GN_FUSED_STATS = old
+
+
+def test_groupnorm_statistics_follow_the_tile_that_really_runs(dev):
+    """The library answers geo4d_conv_gemm_colsum_rows from the plan it launches (csrc/gemm_plan.h). A third-generation hint whose launch
+    the phased stream cannot take (9 K slabs: an odd count) runs on its second-generation twin: the sums have the TWIN's rows per entry
+    (71 -> 22: 64 rows, not 96; 73 -> 25: 64, not 128), equal the sums computed from the output, and the output has the twin's bits. A
+    first-generation hint with a pre-split output is redirected to the second generation (13 -> 22, 4 -> 28): such a launch emits no sums
+    (the pre-split epilogue has none - the query says 0 and the output carries no statistics) and has the redirect target's bits."""
+    from geo4d_amd import ops, pack
+    from test_presplit_gpu import make_split
+    M, K, Cc = 1920, 288, 320
+    g = torch.Generator().manual_seed(77)
+    x, w = torch.randn((M, K), generator=g).to(dev), (torch.randn((Cc, K), generator=g) * 0.1).to(dev)
+    b, r = torch.randn((Cc,), generator=g).to(dev), torch.randn((M, Cc), generator=g).to(dev)
+    wp = pack.pack_linear(w, "bf16x3")
+    for tile, twin, twin_rows, native_rows in ((71, 22, 64, 96), (73, 25, 64, 128)):
+        h = ops.linear(x, wp, b, residual=r, tile_hint=tile, split_k=1, gn_stats=True)
+        assert M % native_rows == 0 and h._gn_colsum_rows == twin_rows and h._gn_colsum.shape == (M // twin_rows, Cc, 2), (tile, h._gn_colsum_rows)
+        hf = h.double()
+        cs_ref = torch.stack([hf.reshape(M // twin_rows, twin_rows, Cc).sum(1), (hf ** 2).reshape(M // twin_rows, twin_rows, Cc).sum(1)], -1).float()
+        assert ((h._gn_colsum - cs_ref).norm() / cs_ref.norm()).item() < 2e-6, tile
+        t = ops.linear(x, wp, b, residual=r, tile_hint=twin, split_k=1, gn_stats=True)
+        assert torch.equal(h, t) and torch.equal(h._gn_colsum, t._gn_colsum), tile
+    xs = make_split(x)
+    for tile, target in ((13, 22), (4, 28)):
+        s = ops.linear(xs, wp, b, tile_hint=tile, split_k=1, gn_stats=True, split_out=True)
+        assert getattr(s, "_gn_colsum", None) is None, tile
+        assert torch.equal(s.as_subclass(torch.Tensor), ops.linear(xs, wp, b, tile_hint=target, split_k=1, split_out=True).as_subclass(torch.Tensor)), tile
