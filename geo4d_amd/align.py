@@ -672,6 +672,10 @@ class GroupAligner:
         pixel grid (geo4d_amd/pnp.py, confidence > 0.5), tried at the image's ray-map focal and -/+ 3 % of the image size; images of
         the FIRST window take the winning candidate as their focal, the others keep the ray-map estimate (as the reference's
         `if im_focals[img_idx] is None` leaves them); the shared focal is the mean. `traj` is then only used by the trajectory term.
+        pose_init = "prefix": the initialisation the reference's command line actually runs (use_raymap = False ->
+        init_im_poses.align_group_prefix :226-405), which needs no ray maps: one focal per window from its reference frame's point map
+        alone (geometry.recover_focal_pixels on the device), windows chained WITH overwriting, PnP per image started at its predecessor's
+        focal (see _init_prefix). `traj` and `raymaps` are not used by it.
         pose_init = "traj" (default): cameras from the Plücker ray maps instead (below).
         traj [G, S, 4, 4]: camera-to-world of every frame in its window's own frame (the Plücker cameras of N2);
         focal: pixels; raymaps [G, S, H, W, 3] (pred_pts['raydir']): when given and `focal` is None, every image's focal is the
@@ -684,6 +688,10 @@ class GroupAligner:
         done = set()
         if pose_init == "pnp":
             return self._init_pnp(pred, conf, focal, raymaps, niter_PnP, pnp_seed)
+        if pose_init == "prefix":
+            return self._init_prefix(pred, conf, focal, niter_PnP, pnp_seed)
+        if pose_init != "traj":
+            raise ValueError(f"pose_init={pose_init!r}: 'traj', 'pnp' or 'prefix'")
         for k, i in enumerate(self.groups[0]):
             pts3d[i], conf_list[i], im_poses[i] = pred[0, k].clone(), conf[0, k].clone(), traj[0, k].clone().float()
             done.add(i)
@@ -797,6 +805,13 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
                     im_focals[i] = res[0]
             if im_poses[i] is None:
                 im_poses[i] = torch.eye(4, device=self.dev)
+    return self._finish_group_init(pred, conf, pts3d, conf_list, im_poses, im_focals, focal)
+
+
+def _finish_group_init(self, pred, conf, pts3d, conf_list, im_poses, im_focals, focal):
+    """init_from_pts3d_group (init_im_poses.py:569-635) on the chained clouds: pairwise poses, scale normalisation, depth maps, camera
+    poses and the focal(s)."""
+    H, W = self.H, self.W
     for g, grp in enumerate(self.groups):                                   # pairwise poses: every window onto the chained cloud
         s, R, T = rigid_points_registration(pred[g], torch.stack([pts3d[i] for i in grp]), torch.stack([conf[g, k] * conf_list[i] for k, i in enumerate(grp)]))
         self.P["pw_poses"][g, :4] = rotmat_to_quat(R).to(self.dev)
@@ -827,6 +842,74 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
 
 
 GroupAligner._init_pnp = _init_pnp
+GroupAligner._finish_group_init = _finish_group_init
+
+
+def filter_outlier_focals(focal_group):
+    """init_im_poses.align_group_prefix :264-269 on the per-window focals (pixels): the mean over focals above 30 replaces every focal
+    whose relative distance to that mean exceeds 0.6. Returns (filtered copy, mean)."""
+    focal_group = focal_group.clone()
+    mean = focal_group[focal_group > 30].mean()
+    focal_group[torch.abs(focal_group - mean) / mean > 0.6] = mean
+    return focal_group, mean
+
+
+def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
+    """GroupAligner.init_from_group(pose_init="prefix"): align_group_prefix + init_from_pts3d_group of the reference.
+      1. the reference frame of every window, z - min(z) + 1 with ONE min over all of them (:259-260), pixels with confidence > 0.5, the
+         shift / focal solve at full resolution (:261) -> one focal in pixels per window (:262-263), outliers replaced (:264-269);
+         a map the solver cannot fit takes the reference's `except` path: PnP without a focal on window 0's first frame, one focal
+         for all windows (:272-277). Device-resident up to the G focals and status words, which cross to the host in one copy.
+      2. window 0 is the world frame; later windows are registered onto the chained cloud and OVERWRITE the point map and confidence
+         of the images they share with it (:347-355).
+      3. every image of every window: RANSAC-PnP started at `temp_focal` = the window's focal for its reference frame, else the current
+         focal of the PREVIOUS image (:307-311, 372-376); pose and focal are overwritten on success (:381-388)."""
+    from . import geometry, pnp
+    G, S, H, W = self.G, self.S, self.H, self.W
+    pts3d, conf_list, im_poses, im_focals = [None] * self.n, [None] * self.n, [None] * self.n, [None] * self.n
+    ref_pts = self.pred.reshape(G, S, H, W, 3)[:, 0]                            # strided views: solved in place
+    ref_conf = self.conf.reshape(G, S, H, W)[:, 0]
+    z_offset = (1.0 - ref_pts[..., 2].min()).reshape(1)
+    focal_px, status = geometry.recover_focal_pixels(ref_pts, ref_conf, (H, W), z_offset=z_offset, return_status=True)
+    host = torch.stack([focal_px, status.float()]).cpu()                        # the one copy: 2 G numbers
+    self.prefix_focals_raw = host[0].clone()
+    if bool((host[1] != 0).any()):
+        res = pnp.fast_pnp(pred[0, 0].reshape(H, W, 3).double().cpu().numpy(), None, (conf[0, 0] > 0.5).reshape(H, W).cpu().numpy(),
+                           niter_PnP=niter_PnP, seed=seed)
+        focal_group = [res[0] if res else max(H, W) / (2.0 * math.tan(math.radians(30.0)))] * G
+    else:
+        focal_group = filter_outlier_focals(host[0])[0].numpy().tolist()
+    self.prefix_focals = torch.tensor(focal_group)
+
+    def run_pnp(i, g, k, temp_focal):
+        msk = (conf[g, k] > 0.5).reshape(H, W).cpu().numpy()
+        return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), temp_focal, msk, niter_PnP=niter_PnP, seed=seed)
+    done = set()
+    for g, grp in enumerate(self.groups):
+        if g:
+            assert grp[0] in done, "the first image of every window must belong to an earlier window"
+            seen = [k for k, i in enumerate(grp) if i in done]
+            s, R, T = rigid_points_registration(pred[g, seen], torch.stack([pts3d[grp[k]] for k in seen]),
+                                                torch.stack([conf[g, k] * conf_list[grp[k]] for k in seen]))
+        for k, i in enumerate(grp):
+            if g == 0:
+                if k == 0:
+                    im_focals[i] = focal_group[0]
+                pts3d[i], conf_list[i] = pred[0, k].clone(), conf[0, k].clone()
+                temp_focal = im_focals[i - 1] if i != 0 else im_focals[i]
+            else:
+                pts3d[i], conf_list[i] = s * (pred[g, k] @ R.t()) + T, conf[g, k].clone()
+                temp_focal = focal_group[g] if k == 0 else im_focals[i - 1]
+            done.add(i)
+            res = run_pnp(i, g, k, temp_focal)
+            if res:
+                im_focals[i], im_poses[i] = res[0], torch.from_numpy(res[1]).float().to(self.dev)
+            if im_poses[i] is None:
+                im_poses[i] = torch.eye(4, device=self.dev)
+    return self._finish_group_init(pred, conf, pts3d, conf_list, im_poses, im_focals, focal)
+
+
+GroupAligner._init_prefix = _init_prefix
 
 
 def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03, align=True, intrinsics=None,
@@ -841,7 +924,9 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     Returns the optimised ``GroupAligner`` (``get_depthmaps`` / ``get_im_poses_matrix`` / ``get_focals``).
     ``intrinsics [n_images, 3, 3]`` presets the focals and freezes them (scene.preset_focal(..., requires_grad=False) in the script).
     ``imgs``: the clip's frames in [-1, 1] (``[1, 3, T, H, W]`` as run_clip takes them, ``[3, T, H, W]`` or ``[T, 3, H, W]``) or uint8,
-    kept as ``scene.imgs`` [n, H, W, 3] in [0, 1] (dust3r.utils.image.rgb) for the export (geo4d_amd/scene_export.py)."""
+    kept as ``scene.imgs`` [n, H, W, 3] in [0, 1] (dust3r.utils.image.rgb) for the export (geo4d_amd/scene_export.py).
+    ``pose_init``: "traj" (default, Plücker cameras), "pnp" (align_group, the reference's opt_raydir branch) or "prefix"
+    (align_group_prefix, what the reference's script runs with its use_raymap = False): GroupAligner.init_from_group."""
     from .pipeline import postprocess_window
     get = (lambda k, d: args.get(k, d)) if isinstance(args, dict) else (lambda k, d: getattr(args, k, d))
     if args is None:

@@ -973,3 +973,44 @@ def scene_mesh_faces(mask, n, H, W, device):
     _lib.check(lib.geo4d_scene_mesh_faces(_ptr(m), n, H, W, faces.data_ptr(), count.data_ptr(), ws.data_ptr(), need, _stream()),
                "geo4d_scene_mesh_faces")
     return faces, count
+
+
+def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=None, iters=40):
+    """(shift [B], focal [B] fp32, status [B] int32) of point maps `points` fp32 [B, H, W, 3] (any map stride: `pred[:, 0]` is used in
+    place): the z-shift and normalised focal that minimise sum |focal * xy / (z + shift) - uv|^2 over the pixels with `weight` [B, H, W]
+    > `thr` (None: all) - utils.geometry.solve_optimal_shift_focal(..., ransac_iters=None) for every map in one enqueue, nothing read back.
+    `downsample_size` (h, w): solve on F.interpolate(mode="nearest")'s sample of the maps (None: every pixel); `z_offset`: device fp32
+    scalar added to every z; `iters`: solver iterations enqueued (converged maps skip theirs). status: 0 ok, 1 fewer than 3 selected
+    pixels, 2 non-finite / non-positive result."""
+    lib = _lib.load()
+    _dev(points, "points")
+    if points.dtype != torch.float32 or points.dim() != 4 or points.shape[-1] != 3 or 0 in points.shape:
+        raise ValueError(f"focal_shift: points must be a non-empty fp32 [B, H, W, 3] tensor, got {points.dtype} {tuple(points.shape)}")
+    B, H, W, _ = points.shape
+    if points.stride()[1:] != (3 * W, 3, 1) or (B > 1 and points.stride(0) < 0):
+        points = points.contiguous()
+    wp, wstride = None, 0
+    if weight is not None:
+        _dev(weight, "weight")
+        if tuple(weight.shape) != (B, H, W) or weight.device != points.device:
+            raise ValueError(f"focal_shift: weight must be [B, H, W] = {(B, H, W)} on {points.device}, got {tuple(weight.shape)} on {weight.device}")
+        if weight.dtype != torch.float32:
+            weight = weight.float()
+        if weight.stride()[1:] != (W, 1) or (B > 1 and weight.stride(0) < 0):
+            weight = weight.contiguous()
+        wp, wstride = weight.data_ptr(), weight.stride(0)
+    if z_offset is not None:
+        _dev(z_offset, "z_offset")
+        if z_offset.dtype != torch.float32 or z_offset.numel() != 1 or z_offset.device != points.device:
+            raise ValueError("focal_shift: z_offset must be ONE fp32 value on the points' device")
+    h_lr, w_lr = (H, W) if downsample_size is None else (int(downsample_size[0]), int(downsample_size[1]))
+    if h_lr <= 0 or w_lr <= 0 or int(iters) <= 0:
+        raise ValueError(f"focal_shift: downsample_size {downsample_size} and iters {iters} must be positive")
+    shift = torch.empty(B, device=points.device, dtype=torch.float32)
+    focal = torch.empty(B, device=points.device, dtype=torch.float32)
+    status = torch.empty(B, device=points.device, dtype=torch.int32)
+    need = lib.geo4d_focal_shift_workspace(B, h_lr, w_lr)
+    ws = torch.empty(need // 8, device=points.device, dtype=torch.float64)
+    _lib.check(lib.geo4d_focal_shift(points.data_ptr(), points.stride(0), wp, wstride, float(thr), _ptr(z_offset), B, H, W, h_lr, w_lr, int(iters),
+                                     shift.data_ptr(), focal.data_ptr(), status.data_ptr(), ws.data_ptr(), need, _stream()), "geo4d_focal_shift")
+    return shift, focal, status

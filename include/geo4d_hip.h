@@ -370,6 +370,24 @@ size_t geo4d_scene_mesh_faces_workspace(int n, int H, int W);
 int geo4d_scene_mesh_faces(const unsigned char* mask, int n, int H, int W, int* faces, long* count, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
+ * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
+ * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
+ *   minimise E(shift) = sum | f xy / (z + shift) - uv |^2 with f = sum(p.uv) / sum(p.p), p = xy / (z + shift), uv = image_plane_uv(W, H)
+ *   (utils/geometry.py:217-229, computed in the kernel); local minimum reached downhill from shift 0 with z + shift > 0 kept for every
+ *   selected pixel (when shift 0 already violates that, the start is min z + shift = 1).
+ * points: fp32, map b at points + b * map_stride, each map a dense [H][W][3]; weight (may be NULL: every pixel) fp32, map b at
+ * weight + b * weight_stride, dense [H][W]: a pixel is selected when weight > thr; z_offset (may be NULL) one device fp32 added to every
+ * z; the (h_lr, w_lr) grid samples the maps at F.interpolate(mode="nearest")'s source indices, (H, W) = every pixel. iters: solver
+ * iterations, all enqueued at once (two launches each; a converged map skips its pixel passes); nothing is read back in between.
+ * Outputs (device): shift [B], focal [B] fp32 (the normalised optim_focal: fov_x = 2 atan(W / diagonal / focal)), status [B] int32 = 0 ok,
+ * 1 fewer than 3 selected pixels (shift 0, focal 1), 2 non-finite / non-positive result; outputs are finite in every case.
+ * workspace: geo4d_focal_shift_workspace bytes, 8-byte aligned, holds ALL solver state. Deterministic (fixed-order fp64 reductions). */
+size_t geo4d_focal_shift_workspace(int B, int h_lr, int w_lr);
+int geo4d_focal_shift(const float* points, long map_stride, const float* weight, long weight_stride, float thr, const float* z_offset, int B,
+                      int H, int W, int h_lr, int w_lr, int iters, float* shift, float* focal, int* status, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 const char* geo4d_last_error(void);
 int geo4d_abi_version(void);
 /* sizeof of the parameter structs as the LIBRARY was compiled (which: 0 conv_gemm, 1 groupnorm, 2 attention, 3 align, 4 align_small; else 0):
