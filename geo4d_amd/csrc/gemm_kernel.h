@@ -6,25 +6,41 @@
 #include "common.h"
 #include "geo4d_hip.h"
 #include "gemm_plan.h"
+#include "gemm_epilogue.h"
 
 namespace geo4d_gemm {
-
 
 constexpr int PITCH = 128;  // LDS row pitch in bytes: 8 x 16-byte slots, XOR-swizzled
 constexpr int BKC = 8;      // 16-byte chunks per row per stage
 constexpr int MAXTAP = 9;
 static_assert(BKC * 16 == KSLAB_BYTES, "gemm_plan.h counts K slabs of BKC 16-byte chunks");
 
-__device__ __forceinline__ void store_out(void* O, long idx, float v, int dt) {
-    if (dt == GEO4D_F32) ((float*)O)[idx] = v;
-    else if (dt == GEO4D_BF16) ((unsigned short*)O)[idx] = f32_to_bf16_bits(v);
-    else ((unsigned short*)O)[idx] = f32_to_f16_bits(v);
+// gather table: source pixel index of (tile row, tap) of row tile tm, -1 where the tap falls into padding (or the row beyond M). The
+// caller places its own barrier between this and the first read.
+template <int BM, int NT>
+__device__ __forceinline__ void fill_gather_table(const geo4d_conv_gemm_t& p, const int tm, const int ntap, const int hw, int* rowpix, const int tid) {
+    const int hlim = p.ups == 2 ? 2 * p.Hin : p.Hin, wlim = p.ups == 2 ? 2 * p.Win : p.Win;
+    const int ush = p.ups == 2 ? 1 : 0;
+    for (int e = tid; e < BM * ntap; e += NT) {
+        const int row = e / ntap, tap = e - row * ntap;
+        const int m = tm * BM + row;
+        int pix = -1;
+        if (m < p.M) {
+            const int f = m / hw, rem = m - f * hw;
+            const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
+            const int kt = tap / (p.KH * p.KW), r2 = tap - kt * (p.KH * p.KW);
+            const int ky = r2 / p.KW, kx = r2 - ky * p.KW;
+            const int iy = oy * p.stride - p.ph + ky, ix = ox * p.stride - p.pw + kx;
+            const int tt = (f % p.T) + kt - p.pt;
+            if ((unsigned)iy < (unsigned)hlim && (unsigned)ix < (unsigned)wlim && (unsigned)tt < (unsigned)p.T)
+                pix = ((f + kt - p.pt) * p.Hin + (iy >> ush)) * p.Win + (ix >> ush);
+        }
+        rowpix[e] = pix;
+    }
 }
-__device__ __forceinline__ float load_res(const void* R, long idx, int dt) {
-    if (dt == GEO4D_F32) return ((const float*)R)[idx];
-    if (dt == GEO4D_BF16) return bf16_bits_to_f32(((const unsigned short*)R)[idx]);
-    return f16_bits_to_f32(((const unsigned short*)R)[idx]);
-}
+// operand layouts of the 4-byte types: fixed at compile time by HOT (1 = raw A x split W, 2 = split A x split W), else read from the descriptor
+template <int HOT> __device__ __forceinline__ bool a_is_split(const geo4d_conv_gemm_t& p) { return HOT ? (HOT == 2) : (p.a_split != 0); }
+template <int HOT> __device__ __forceinline__ bool w_is_split(const geo4d_conv_gemm_t& p) { return HOT ? true : (p.w_split != 0); }
 
 template <int BM, int BN, int WM, int WN, int ST>
 constexpr int stage_bytes() {
@@ -77,24 +93,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
     const bool direct_rows = ntap == 1 && p.stride == 1 && p.ups == 1 && p.ph == 0 && p.pw == 0 && p.pt == 0 &&
                              p.Hin * p.Win == hw;
     if (!direct_rows) {
-        const int hlim = p.ups == 2 ? 2 * p.Hin : p.Hin, wlim = p.ups == 2 ? 2 * p.Win : p.Win;
-        const int ush = p.ups == 2 ? 1 : 0;
-        for (int e = tid; e < BM * ntap; e += NT) {
-            const int row = e / ntap, tap = e - row * ntap;
-            const int m = tm * BM + row;
-            int pix = -1;
-            if (m < p.M) {
-                const int f = m / hw, rem = m - f * hw;
-                const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-                const int kt = tap / (p.KH * p.KW), r2 = tap - kt * (p.KH * p.KW);
-                const int ky = r2 / p.KW, kx = r2 - ky * p.KW;
-                const int iy = oy * p.stride - p.ph + ky, ix = ox * p.stride - p.pw + kx;
-                const int tt = (f % p.T) + kt - p.pt;
-                if ((unsigned)iy < (unsigned)hlim && (unsigned)ix < (unsigned)wlim && (unsigned)tt < (unsigned)p.T)
-                    pix = ((f + kt - p.pt) * p.Hin + (iy >> ush)) * p.Win + (ix >> ush);
-            }
-            rowpix[e] = pix;
-        }
+        fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid);
         __syncthreads();
     }
 
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
 #pragma unroll
             for (int j = 0; j < 2; ++j) foffx[s2][j] = li * PITCH + (((4 * s2 + 2 * g + j) ^ ((li >> 1) & 7)) << 4);
     }
-    const bool a_split = HOT ? (HOT == 2) : (p.a_split != 0), w_split = HOT ? true : (p.w_split != 0);
+    const bool a_split = a_is_split<HOT>(p), w_split = w_is_split<HOT>(p);
     auto compute_slab = [&](int buf) {
         const char* abase = smem + buf * (BM + BN) * PITCH + (wr * WTM) * PITCH;
         const char* bbase = smem + buf * (BM + BN) * PITCH + (BM + wc * WTN) * PITCH;
@@ -272,14 +271,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
     const int m_w0 = tm * BM + wr * WTM;
     const int n_w0 = tn * BN + wc * WTN;
     const bool partial = gridDim.z > 1;          // split-K: raw fp32 slab, epilogue runs in the reduce kernel
-    const int odt = partial ? GEO4D_F32 : p.out_dtype;
-    void* O = partial ? (void*)((float*)p.workspace + ((long)kz * p.batch + bz) * (long)p.M * p.N) : p.O;
-    const long ldo = partial ? (long)p.N : p.ldo;
-    const long obase = partial ? 0 : bz * p.o_bs;
-    const bool geglu = !partial && p.act == 2;
+    const EpiDest d = epi_dest(p, partial, kz, bz);
+    void* const O = d.O;
+    const long ldo = d.ldo, obase = d.obase;
+    const int odt = d.odt, oesz = d.oesz, nout = d.nout;
+    const bool geglu = d.geglu;
     const bool gn_on = !partial && p.gn_colsum != nullptr;
-    const int oesz = odt == GEO4D_F32 ? 4 : 2;
-    const int nout = geglu ? (p.N >> 1) : p.N;
     const bool vec_ok = !p.out_nchw && ((ldo * oesz) & 15) == 0 && (nout & 7) == 0 && (((uintptr_t)O + obase * oesz) & 15) == 0 &&
                         (partial || !p.R || (((p.ldr * oesz) & 15) == 0 && (((uintptr_t)p.R + bz * p.r_bs * oesz) & 15) == 0));
 
@@ -309,9 +306,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
                         for (int r = 0; r < 16; ++r) {
                             const int nn = n_w0 + 64 * b2 + 8 * (r >> 2) + 4 * g + (r & 3);
                             if (nn + 32 >= p.N) continue;
-                            const float xv = acc[a][2 * b2][r] * p.alpha + (p.bias ? p.bias[nn] : 0.f);
-                            const float gv = acc[a][2 * b2 + 1][r] * p.alpha + (p.bias ? p.bias[nn + 32] : 0.f);
-                            store_out(O, obase + orow + (long)((n_w0 >> 1) + 32 * b2 + 8 * (r >> 2) + 4 * g + (r & 3)) * ocol, xv * gelu_erf_f(gv), odt);
+                            const float v = geglu_value(p.alpha, acc[a][2 * b2][r], acc[a][2 * b2 + 1][r], p.bias ? p.bias[nn] : 0.f, p.bias ? p.bias[nn + 32] : 0.f);
+                            store_out(O, obase + orow + (long)((n_w0 >> 1) + 32 * b2 + 8 * (r >> 2) + 4 * g + (r & 3)) * ocol, v, odt);
                         }
                 }
                 continue;
@@ -324,10 +320,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
                     if (n >= p.N) continue;
                     float v = acc[a][b][r];
                     if (!partial) {
-                        v = v * p.alpha + brow;
-                        if (p.bias && !p.bias_per_row) v += p.bias[n];
-                        if (p.rowbias) v += p.rowbias[rboff + n];
-                        if (p.act == 1) v = silu_f(v);
+                        v = epi_value<false>(p, v, brow, rboff, n);
                         if (p.R) v += load_res(p.R, bz * p.r_bs + (long)m * p.ldr + n, odt);
                     }
                     store_out(O, obase + orow + (long)n * ocol, v, odt);
@@ -385,9 +378,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const bool ok = nn + 32 + j < p.N;
-                            const float xv = acc[a][2 * cg][4 * q + j] * p.alpha + ((p.bias && ok) ? p.bias[nn + j] : 0.f);
-                            const float gv = acc[a][2 * cg + 1][4 * q + j] * p.alpha + ((p.bias && ok) ? p.bias[nn + 32 + j] : 0.f);
-                            o[j] = xv * gelu_erf_f(gv);
+                            o[j] = geglu_value(p.alpha, acc[a][2 * cg][4 * q + j], acc[a][2 * cg + 1][4 * q + j], (p.bias && ok) ? p.bias[nn + j] : 0.f,
+                                               (p.bias && ok) ? p.bias[nn + 32 + j] : 0.f);
                         }
                         *(f32x4*)(stg + li * SP + 8 * q + 4 * g) = o;
                     }
@@ -403,15 +395,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_kernel(const geo4d_con
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             float v = acc[a][b][4 * q + j];
-                            if (!partial) {
-                                v = v * p.alpha + brow;
-                                if (n + j < p.N) {
-                                    if (p.bias && !p.bias_per_row) v += p.bias[n + j];
-                                    if (p.rowbias) v += p.rowbias[rboff + n + j];
-                                }
-                                if (p.act == 1) v = silu_f(v);
-                        else if (p.act == 3) v = gelu_erf_f(v);
-                            }
+                            if (!partial) v = epi_value(p, v, brow, rboff, n + j, n + j < p.N);
                             o[j] = v;
                         }
                         *(f32x4*)(stg + li * SP + bb * 32 + 8 * q + 4 * g) = o;
@@ -515,11 +499,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const geo4d_conv_gem
     const long rboff = p.rowbias ? (long)(m / p.rowbias_div) * (p.ldrb ? p.ldrb : (long)p.N) : 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        float v = e[j] * p.alpha + brow;
-        if (p.bias && !p.bias_per_row) v += p.bias[n + j];
-        if (p.rowbias) v += p.rowbias[rboff + n + j];
-        if (p.act == 1) v = silu_f(v);
-        else if (p.act == 3) v = gelu_erf_f(v);
+        float v = epi_value(p, e[j], brow, rboff, n + j);
         if (p.R) v += load_res(p.R, bz * p.r_bs + (long)m * p.ldr + n + j, p.out_dtype);
         e[j] = v;
     }
@@ -583,17 +563,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_colsum_kernel(const geo4d_c
         dst[0] = s0; dst[1] = s1;
     }
 }
-// the reduce launch of a split-K GEMM (every generation's launcher ends here): with gn_colsum, the column-sum form at the plan's granularity
-template <typename T>
+// the reduce launch of a split-K GEMM (every generation's launcher ends here): with gn_colsum, the column-sum form at the plan's granularity.
+// COLSUM = false: the first generation, whose split launches never carry gn_colsum (resolve() refuses them) - no column-sum kernels built there.
+template <typename T, bool COLSUM = true>
 int launch_splitk_reduce(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
-    if (p.gn_colsum && plan.colsum_rows == 32) {
-        hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 32>), dim3((unsigned)((p.M / 32) * (p.N / 64))), dim3(256), 0, stream, p, plan.splits);
-    } else if (p.gn_colsum) {
-        hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 8>), dim3((unsigned)((p.M / 8) * (p.N / 256))), dim3(256), 0, stream, p, plan.splits);
-    } else {
-        const long tot = (long)p.batch * p.M * (p.N / 8);
-        hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, p, plan.splits);
+    if constexpr (COLSUM) {
+        if (p.gn_colsum) {
+            if (plan.colsum_rows == 32) hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 32>), dim3((unsigned)((p.M / 32) * (p.N / 64))), dim3(256), 0, stream, p, plan.splits);
+            else hipLaunchKernelGGL((splitk_reduce_colsum_kernel<T, 8>), dim3((unsigned)((p.M / 8) * (p.N / 256))), dim3(256), 0, stream, p, plan.splits);
+            GEO4D_CHECK_LAUNCH();
+            return GEO4D_OK;
+        }
     }
+    const long tot = (long)p.batch * p.M * (p.N / 8);
+    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, p, plan.splits);
     GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
 }
@@ -628,10 +611,7 @@ int launch_cfg(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream)
         rc = launch_kernel<T, BM, BN, WM, WN, ST, 0>(p, plan.splits, stream);
     }
     if (rc != GEO4D_OK || plan.splits == 1) return rc;
-    const long total = (long)p.batch * p.M * (p.N / 8);      // (no gn_colsum from a split first-generation launch: the plain reduce)
-    hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, plan.splits);
-    GEO4D_CHECK_LAUNCH();
-    return GEO4D_OK;
+    return launch_splitk_reduce<T, false>(p, plan, stream);
 }
 
 // the plan's tile on the first generation (hints 1..17). The later generations are instantiated in their own translation units so that

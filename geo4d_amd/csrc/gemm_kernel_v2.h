@@ -49,6 +49,18 @@ template <typename T> __device__ __forceinline__ int swz_key(int row) {
     else return p;
 }
 
+// fragment offsets inside a 16-row block: lane (lr, lq) reads row lr; 16-bit types: chunk 4h + lq of K half h; bf16x3: chunks 2lq (hi), 2lq + 1 (lo)
+template <typename T> __device__ __forceinline__ void frag_offsets(const int lr, const int lq, int (&foff)[2]) {
+    const int fkey = swz_key<T>(lr);
+    if constexpr (IsX3<T>::value) {
+        foff[0] = lr * PITCH + (((2 * lq) ^ fkey) << 4);
+        foff[1] = lr * PITCH + (((2 * lq + 1) ^ fkey) << 4);
+    } else {
+        foff[0] = lr * PITCH + ((lq ^ fkey) << 4);
+        foff[1] = lr * PITCH + (((4 + lq) ^ fkey) << 4);
+    }
+}
+
 // Tile order inside one (batch, split) slab of tiles_m x tiles_n tiles. The persistent workgroups of an XCD work on ~32 CONSECUTIVE
 // tile ids at a time (xcd_remap): with the N index fastest (the default) those are 1 row-tile x 32 column-tiles - one A panel shared, 32
 // weight panels streamed, and every row-tile streams the whole weight matrix again (PMC: the level-2 GEGLU launch fetches 14 x its 52 MB
@@ -86,11 +98,10 @@ __device__ __forceinline__ int swz_key_a64(int row) { return (4 - ((row >> 2) & 
 constexpr int PITCH_A64 = 64;
 
 // ---- register epilogue shared by the second- and third-generation kernels: acc[a][b][j] is out[m_w0 + 16a + lr][n_w0 + 16b + 4lq + j]
-// (bias / row-bias / activation / GEGLU / residual / rounding in registers, 16-byte (f32) or 8-byte (16-bit) stores). `partial`:
-// split-K launch, the raw fp32 slab of split e_kz goes to the workspace and the epilogue runs in splitk_reduce_kernel.
+// (bias / row-bias / activation / GEGLU / residual / rounding in registers, 16-byte (f32) or 8-byte (16-bit) stores; pieces: gemm_epilogue.h).
 // Round 4 - fast paths for 4-byte rows (every bf16x3 projection / conv except the ResBlocks' emb-add convs and the per-row-bias V^T
 // projections). tools/gemm_kscan.py measured a K-INDEPENDENT ~30 us per tile in these kernels (profiles/r04_gemm_kscan.md: 97 us of a
-// 151 us level-0 qkv launch): the generic code below loads bias / residual element by element behind per-element branches, each load
+// 151 us level-0 qkv launch): the generic path (generic_rows) loads bias / residual element by element behind per-element branches, each load
 // followed by s_waitcnt vmcnt(0) - and vmcnt is in order over loads AND stores, so every block's loads waited until the previous
 // block's stores were acknowledged (~1.3 us x 24-25 blocks per tile). The fast paths have no per-element branches: the column bias
 // is ONE 16-byte load per block outside the row loop, the residual one 16-byte load issued a row block AHEAD of the stores (counted
@@ -107,280 +118,108 @@ __device__ __forceinline__ float row16_sum(float v) {      // sum over the 16 la
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));     // row_mirror
     return v;
 }
-template <int MB, int NB, bool OSPLIT, bool VECONLY = false, bool ROWS4 = false, bool OH = false>   // OH: the two-pass f16 type - its OSPLIT output (o_split = 2) is PLAIN f16 rows instead of bf16 hi | lo halves; VECONLY: the host checked the vector-store conditions (no scalar fallback code); ROWS4: 4-byte element kernels (bf16x3) - the 16-bit-row fast paths are not instantiated
-__device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const int m_w0, const int n_w0,
-                                             const long e_bz, const int e_kz, const bool partial, const int lr, const int lq) {
-    const int odt = partial ? GEO4D_F32 : p.out_dtype;
-    const int oesz = odt == GEO4D_F32 ? 4 : 2;
-    const bool geglu = !partial && p.act == 2;
-    const int nout = geglu ? (p.N >> 1) : p.N;
-    void* O = partial ? (void*)((float*)p.workspace + ((long)e_kz * p.batch + e_bz) * (long)p.M * p.N) : p.O;
-    const long ldo = partial ? (long)p.N : p.ldo;
-    const long obase = partial ? 0 : e_bz * p.o_bs;
-    const bool has_res = !partial && p.R != nullptr;
-    const long rbase = e_bz * p.r_bs;
-    // 4-element vectors need 4-element aligned rows and bases (16 B for f32, 8 B for 16-bit outputs)
-    const bool vec_ok = VECONLY || ((nout & 3) == 0 && (ldo & 3) == 0 && (((uintptr_t)O + obase * oesz) % (4 * oesz)) == 0 &&
-                                    (!has_res || ((p.ldr & 3) == 0 && (((uintptr_t)p.R + rbase * oesz) % (4 * oesz)) == 0)));
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-    // this lane's 16-byte chunk `lq` of a block's 64 output bytes (4-byte rows)
-    auto chunk_of = [&](const float (&e)[4]) __attribute__((always_inline)) -> u32x4 {
-        if constexpr (OSPLIT) {
-            unsigned int h0, h1, l0, l1;
-            h0 = f32x2_to_bf16x2(e[0], e[1]); h1 = f32x2_to_bf16x2(e[2], e[3]);
-            l0 = f32x2_to_bf16x2(e[0] - __uint_as_float(h0 << 16), e[1] - __uint_as_float(h0 & 0xffff0000u));
-            l1 = f32x2_to_bf16x2(e[2] - __uint_as_float(h1 << 16), e[3] - __uint_as_float(h1 & 0xffff0000u));
-            // rows of 16 lanes = lq: odd rows of (h) <-> even rows of (l): even lq ends with [h own | h of lq + 1] = the group's hi chunk,
-            // odd lq with [l of lq - 1 | l own] = its lo chunk (every lane of the wave takes part: no divergence before this point)
-            const u32x2 s0 = __builtin_amdgcn_permlane16_swap(h0, l0, false, false);
-            const u32x2 s1 = __builtin_amdgcn_permlane16_swap(h1, l1, false, false);
-            return u32x4{s0[0], s1[0], s0[1], s1[1]};
-        } else {
-            return u32x4{__float_as_uint(e[0]), __float_as_uint(e[1]), __float_as_uint(e[2]), __float_as_uint(e[3])};
+// The wide f32 plain fast path (also the split-K partial), the one that carries gn_colsum and the row biases. Store = StoreF32 or StoreSplit.
+template <int MB, int NB, typename Store>
+__device__ __forceinline__ void wide_plain(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const EpiDest& d, const bool partial, const bool has_res, const long rbase,
+                                           const int m_w0, const int n_w0, const int lr, const int lq) {
+    constexpr unsigned OOB = EPI_OOB;
+    const long ldo = d.ldo;
+    const float alpha = partial ? 1.0f : p.alpha;
+    const bool hb = !partial && p.bias != nullptr && !p.bias_per_row;      // bias per output column
+    const bool hr = !partial && p.bias != nullptr && p.bias_per_row;       // bias per output row (the operand-swapped V^T projection)
+    const bool ht = !partial && p.rowbias != nullptr;                      // row-bias table (the ResBlocks' per-frame emb add): row m / rowbias_div
+    const __amdgpu_buffer_rsrc_t rsO = tile_rsrc((float*)d.O + d.obase + (long)m_w0 * ldo + n_w0);
+    const __amdgpu_buffer_rsrc_t rsR = tile_rsrc(has_res ? (const void*)((const float*)p.R + rbase + (long)m_w0 * p.ldr + n_w0) : p.zeros, has_res);
+    const int mleft = p.M - m_w0;
+    const __amdgpu_buffer_rsrc_t rsB = bias_rsrc(p, hb, n_w0);
+    const __amdgpu_buffer_rsrc_t rsBr = __builtin_amdgcn_make_buffer_rsrc(
+        uniform_ptr(hr ? (const void*)(p.bias + m_w0) : p.zeros), 0, (hr && mleft > 0) ? (unsigned)mleft * 4u : 0u, EPI_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rsT = tile_rsrc(ht ? (const void*)(p.rowbias + n_w0) : p.zeros, ht);
+    const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 4u, offR = (unsigned)(lr * (int)p.ldr + 4 * lq) * 4u;
+    const unsigned rowO = (unsigned)ldo * 64u, rowR = (unsigned)p.ldr * 64u;       // bytes per 16-row block
+    // (the launcher checked M % (16 MB) == 0 and the fast-path conditions; a wave tile that starts beyond M - the last row tile of a
+    // ragged M - has no entry: its chunk index would lie beyond the [M / rows] buffer)
+    const bool gn = !partial && p.gn_colsum != nullptr && m_w0 < p.M;
+    const __amdgpu_buffer_rsrc_t rsC = tile_rsrc(gn ? (const void*)(p.gn_colsum + ((long)(m_w0 / (16 * MB)) * p.N + n_w0) * 2) : p.zeros, gn);
+    unsigned offT[MB];                                                              // byte offset of this lane's row-bias row per row block
+#pragma unroll
+    for (int a = 0; a < MB; ++a) offT[a] = 0u;
+    if (ht) {
+        const unsigned ldt = (unsigned)(p.ldrb ? p.ldrb : (long)p.N);
+#pragma unroll
+        for (int a = 0; a < MB; ++a) {
+            const int m = m_w0 + a * 16 + lr;
+            offT[a] = ((unsigned)((m < p.M ? m : p.M - 1) / p.rowbias_div) * ldt + 4u * lq) * 4u;
         }
-    };
-    if constexpr (OSPLIT && OH) {
-        // o_split = 2 (the two-pass f16 type; round 6): O = PLAIN f16 rows - the A operand of the next dtype-4 launch (GEGLU -> ff-out). The
-        // launcher checked: no split-K, no residual / row biases, act 0 or GEGLU, stored columns % 8 == 0, 16-byte aligned rows. 8-byte
-        // vector stores through a buffer resource (a lane outside M x N offers an out-of-window offset), values clamped to the finite f16
-        // range with NaN kept (common.h pack4_f16_sat); p.sat_count (debug) counts the clamped lanes.
-        constexpr unsigned OOB2 = 0x80000000u;
-        auto uptr = [](const void* q) __attribute__((always_inline)) -> void* {
-            const unsigned long long v = (unsigned long long)q;
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-            return (void*)(((unsigned long long)hi << 32) | lo);
-        };
-        const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(
-            uptr((unsigned short*)p.O + e_bz * p.o_bs + (long)m_w0 * p.ldo + (geglu ? (n_w0 >> 1) : n_w0)), 0, OOB2, 0x00020000);
-        const int nleft = p.N - n_w0;
-        const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-            uptr(p.bias ? (const void*)(p.bias + n_w0) : p.zeros), 0, (p.bias && nleft > 0) ? (unsigned)nleft * 4u : 0u, 0x00020000);
-        const unsigned offO = (unsigned)(lr * (int)p.ldo + 4 * lq) * 2u, rowO = (unsigned)p.ldo * 32u;       // bytes per 16-row block
-        if (geglu) {
-            if constexpr (NB % 4 == 0) {
+    }
 #pragma unroll
-                for (int b = 0; b < NB; ++b) {
-                    if ((b & 3) >= 2) continue;
-                    const bool grp = n_w0 + 16 * (b & ~3) + 64 <= p.N;       // whole 64-column value | gate groups only (N % 64 == 0)
-                    const u32x4 bv = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-                    const u32x4 bg = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b + 128u, 0, 0);
+    for (int b = 0; b < NB; ++b) {
+        const bool colok = n_w0 + 16 * b + 4 * lq < p.N;
+        const u32x4 bcu = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
+        u32x4 ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, ((colok && m_w0 + lr < p.M) ? offR : OOB) + 64u * b, 0, 0);
+        u32x4 tu = __builtin_amdgcn_raw_buffer_load_b128(rsT, (colok ? offT[0] : OOB) + 64u * b, 0, 0);
+        unsigned bru = __builtin_amdgcn_raw_buffer_load_b32(rsBr, (unsigned)lr * 4u, 0, 0);
+        float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int a = 0; a < MB; ++a) {
-                        const bool ok = grp && m_w0 + a * 16 + lr < p.M;
-                        float e[4];
+        for (int a = 0; a < MB; ++a) {
+            const bool ok = colok && m_w0 + a * 16 + lr < p.M;
+            const float brow = __uint_as_float(bru);
+            float e[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            e[j] = (acc[a][b][j] * p.alpha + __uint_as_float(bv[j])) * gelu_erf_f(acc[a][b + 2 < NB ? b + 2 : b][j] * p.alpha + __uint_as_float(bg[j]));
-                        count_f16_saturation(p.sat_count, e);
-                        __builtin_amdgcn_raw_buffer_store_b64(pack4_f16_sat(e), rsO, (ok ? offO + a * rowO : OOB2) + (unsigned)(32 * (b >> 2) + 16 * (b & 1)) * 2u, 0, 0);
-                    }
-                }
+            for (int j = 0; j < 4; ++j)
+                e[j] = (((acc[a][b][j] * alpha + brow) + __uint_as_float(bcu[j])) + __uint_as_float(tu[j])) + __uint_as_float(ru[j]);
+            if (gn) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { cs[j] += e[j]; cq[j] += e[j] * e[j]; }
             }
-        } else {
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const bool colok = n_w0 + 16 * b + 4 * lq < p.N;
-                const u32x4 bcu = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-#pragma unroll
-                for (int a = 0; a < MB; ++a) {
-                    const bool ok = colok && m_w0 + a * 16 + lr < p.M;
-                    float e[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) e[j] = acc[a][b][j] * p.alpha + __uint_as_float(bcu[j]);
-                    count_f16_saturation(p.sat_count, e);
-                    __builtin_amdgcn_raw_buffer_store_b64(pack4_f16_sat(e), rsO, (ok ? offO + a * rowO : OOB2) + 32u * b, 0, 0);
-                }
+            const u32x4 c = Store::pack(p, e);
+            if (a + 1 < MB) {            // the next row block's residual / row biases go out BEFORE this block's store: their wait stays counted
+                ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, ((colok && m_w0 + (a + 1) * 16 + lr < p.M) ? offR : OOB) + 64u * b, (a + 1) * rowR, 0);
+                tu = __builtin_amdgcn_raw_buffer_load_b128(rsT, (colok ? offT[a + 1 < MB ? a + 1 : a] : OOB) + 64u * b, 0, 0);
+                bru = __builtin_amdgcn_raw_buffer_load_b32(rsBr, (unsigned)(lr + 16 * (a + 1)) * 4u, 0, 0);
             }
+            // (row-block offset in the VGPR offset, soffset = 0: with an SGPR soffset hipcc's hazard recognizer assumes a 16-byte buffer
+            // store's data registers may be overwritten right away - on gfx950 the last lanes of every 16 then stored the NEXT block's
+            // values, tools/dbg_epilogue.py; measured round 4)
+            Store::store(c, rsO, (ok ? offO + a * rowO : OOB) + 64u * b);
         }
+        if (gn) {                        // [chunk][n][2]: lane lr == 0 of every 16-lane row writes its 4 columns' (sum, sum of squares)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cs[j] = row16_sum(cs[j]); cq[j] = row16_sum(cq[j]); }
+            const unsigned offC = (lr == 0 && colok) ? (unsigned)(16 * b + 4 * lq) * 8u : OOB;
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cs[0]), __float_as_uint(cq[0]), __float_as_uint(cs[1]), __float_as_uint(cq[1])}, rsC, offC, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cs[2]), __float_as_uint(cq[2]), __float_as_uint(cs[3]), __float_as_uint(cq[3])}, rsC, offC + 16u, 0, 0);
+        }
+    }
+}
+
+// 4 consecutive columns of row `row` (elements from the tensor base): one vector where the rows are aligned for it, else element by element
+template <bool OSPLIT>
+__device__ __forceinline__ void store4_generic(const EpiDest& d, const bool vec_ok, const long row, const int col, const float (&e)[4]) {
+    const long oidx = row + col;
+    if (!vec_ok) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) store_out(d.O, oidx + j, e[j], d.odt);
         return;
     }
-    const bool wide = vec_ok && odt == GEO4D_F32;       // (o_split: N % 8 == 0, so the two lanes of an 8-column group are in range together)
-    // Fast paths: every access goes through a raw buffer resource whose base is this wave's tile corner (wave-uniform, SGPRs): a lane
-    // outside M x N offers an offset beyond the 2 GB window (stores dropped, loads return 0 - no exec-masked branches, so hipcc's
-    // waits stay COUNTED), an absent bias / residual is a resource with zero records (its loads return 0 without touching memory).
-    constexpr unsigned OOB = 0x80000000u;
-    auto uniform_ptr = [](const void* q) __attribute__((always_inline)) -> void* {
-        const unsigned long long v = (unsigned long long)q;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (void*)(((unsigned long long)hi << 32) | lo);
-    };
-    if (wide && !geglu && (partial || p.act == 0)) {
-        const float alpha = partial ? 1.0f : p.alpha;
-        const bool hb = !partial && p.bias != nullptr && !p.bias_per_row;      // bias per output column
-        const bool hr = !partial && p.bias != nullptr && p.bias_per_row;       // bias per output row (the operand-swapped V^T projection)
-        const bool ht = !partial && p.rowbias != nullptr;                      // row-bias table (the ResBlocks' per-frame emb add): row m / rowbias_div
-        const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((float*)O + obase + (long)m_w0 * ldo + n_w0), 0, OOB, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(has_res ? (const void*)((const float*)p.R + rbase + (long)m_w0 * p.ldr + n_w0) : p.zeros), 0, has_res ? OOB : 0u, 0x00020000);
-        const int nleft = p.N - n_w0, mleft = p.M - m_w0;
-        const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(hb ? (const void*)(p.bias + n_w0) : p.zeros), 0, (hb && nleft > 0) ? (unsigned)nleft * 4u : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsBr = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(hr ? (const void*)(p.bias + m_w0) : p.zeros), 0, (hr && mleft > 0) ? (unsigned)mleft * 4u : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(ht ? (const void*)(p.rowbias + n_w0) : p.zeros), 0, ht ? OOB : 0u, 0x00020000);
-        const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 4u, offR = (unsigned)(lr * (int)p.ldr + 4 * lq) * 4u;
-        const unsigned rowO = (unsigned)ldo * 64u, rowR = (unsigned)p.ldr * 64u;       // bytes per 16-row block
-        // (the launcher checked M % (16 MB) == 0 and the fast-path conditions; a wave tile that starts beyond M - the last row tile of a
-        // ragged M - has no entry: its chunk index would lie beyond the [M / rows] buffer)
-        const bool gn = !partial && p.gn_colsum != nullptr && m_w0 < p.M;
-        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(gn ? (const void*)(p.gn_colsum + ((long)(m_w0 / (16 * MB)) * p.N + n_w0) * 2) : p.zeros), 0, gn ? OOB : 0u, 0x00020000);
-        unsigned offT[MB];                                                              // byte offset of this lane's row-bias row per row block
-#pragma unroll
-        for (int a = 0; a < MB; ++a) offT[a] = 0u;
-        if (ht) {
-            const unsigned ldt = (unsigned)(p.ldrb ? p.ldrb : (long)p.N);
-#pragma unroll
-            for (int a = 0; a < MB; ++a) {
-                const int m = m_w0 + a * 16 + lr;
-                offT[a] = ((unsigned)((m < p.M ? m : p.M - 1) / p.rowbias_div) * ldt + 4u * lq) * 4u;
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const bool colok = n_w0 + 16 * b + 4 * lq < p.N;
-            const u32x4 bcu = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-            u32x4 ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, ((colok && m_w0 + lr < p.M) ? offR : OOB) + 64u * b, 0, 0);
-            u32x4 tu = __builtin_amdgcn_raw_buffer_load_b128(rsT, (colok ? offT[0] : OOB) + 64u * b, 0, 0);
-            unsigned bru = __builtin_amdgcn_raw_buffer_load_b32(rsBr, (unsigned)lr * 4u, 0, 0);
-            float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int a = 0; a < MB; ++a) {
-                const bool ok = colok && m_w0 + a * 16 + lr < p.M;
-                const float brow = __uint_as_float(bru);
-                float e[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    e[j] = (((acc[a][b][j] * alpha + brow) + __uint_as_float(bcu[j])) + __uint_as_float(tu[j])) + __uint_as_float(ru[j]);
-                if (gn) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cs[j] += e[j]; cq[j] += e[j] * e[j]; }
-                }
-                const u32x4 c = chunk_of(e);
-                if (a + 1 < MB) {            // the next row block's residual / row biases go out BEFORE this block's store: their wait stays counted
-                    ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, ((colok && m_w0 + (a + 1) * 16 + lr < p.M) ? offR : OOB) + 64u * b, (a + 1) * rowR, 0);
-                    tu = __builtin_amdgcn_raw_buffer_load_b128(rsT, (colok ? offT[a + 1 < MB ? a + 1 : a] : OOB) + 64u * b, 0, 0);
-                    bru = __builtin_amdgcn_raw_buffer_load_b32(rsBr, (unsigned)(lr + 16 * (a + 1)) * 4u, 0, 0);
-                }
-                // (row-block offset in the VGPR offset, soffset = 0: with an SGPR soffset hipcc's hazard recognizer assumes a 16-byte buffer
-                // store's data registers may be overwritten right away - on gfx950 the last lanes of every 16 then stored the NEXT block's
-                // values, tools/dbg_epilogue.py; measured round 4)
-                __builtin_amdgcn_raw_buffer_store_b128(c, rsO, (ok ? offO + a * rowO : OOB) + 64u * b, 0, 0);
-            }
-            if (gn) {                        // [chunk][n][2]: lane lr == 0 of every 16-lane row writes its 4 columns' (sum, sum of squares)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { cs[j] = row16_sum(cs[j]); cq[j] = row16_sum(cq[j]); }
-                const unsigned offC = (lr == 0 && colok) ? (unsigned)(16 * b + 4 * lq) * 8u : OOB;
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cs[0]), __float_as_uint(cq[0]), __float_as_uint(cs[1]), __float_as_uint(cq[1])}, rsC, offC, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(cs[2]), __float_as_uint(cq[2]), __float_as_uint(cs[3]), __float_as_uint(cq[3])}, rsC, offC + 16u, 0, 0);
-            }
-        }
-        return;
-    }
-    if (wide && geglu) {             // bias (value | gate columns) once per block, outside the row loop; only stores inside
-        if constexpr (NB % 4 == 0) {
-            const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((float*)O + obase + (long)m_w0 * ldo + (n_w0 >> 1)), 0, OOB, 0x00020000);
-            const int nleft = p.N - n_w0;
-            const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-                uniform_ptr(p.bias ? (const void*)(p.bias + n_w0) : p.zeros), 0, (p.bias && nleft > 0) ? (unsigned)nleft * 4u : 0u, 0x00020000);
-            const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 4u, rowO = (unsigned)ldo * 64u;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if ((b & 3) >= 2) continue;
-                // whole 64-column value | gate groups only (N % 64 == 0): wave-uniform, folded into the store offset
-                const bool grp = n_w0 + 16 * (b & ~3) + 64 <= p.N;
-                const u32x4 bv = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-                const u32x4 bg = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b + 128u, 0, 0);
-#pragma unroll
-                for (int a = 0; a < MB; ++a) {
-                    const bool ok = grp && m_w0 + a * 16 + lr < p.M;
-                    float e[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        e[j] = (acc[a][b][j] * p.alpha + __uint_as_float(bv[j])) * gelu_erf_f(acc[a][b + 2 < NB ? b + 2 : b][j] * p.alpha + __uint_as_float(bg[j]));
-                    const u32x4 c = chunk_of(e);
-                    __builtin_amdgcn_raw_buffer_store_b128(c, rsO, (ok ? offO + a * rowO : OOB) + (unsigned)(32 * (b >> 2) + 16 * (b & 1)) * 4u, 0, 0);
-                }
-            }
-        }
-        return;
-    }
-    if constexpr (!ROWS4)
-    if (vec_ok && odt != GEO4D_F32 && !geglu && p.act == 0 && !p.rowbias && !(p.bias && p.bias_per_row)) {
-        // 16-bit rows (the bf16 / f16 modes): the same structure with 8-byte vectors
-        const bool isbf = odt == GEO4D_BF16;
-        const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((unsigned short*)O + obase + (long)m_w0 * ldo + n_w0), 0, OOB, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(has_res ? (const void*)((const unsigned short*)p.R + rbase + (long)m_w0 * p.ldr + n_w0) : p.zeros), 0, has_res ? OOB : 0u, 0x00020000);
-        const int nleft = p.N - n_w0;
-        const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-            uniform_ptr(p.bias ? (const void*)(p.bias + n_w0) : p.zeros), 0, (p.bias && nleft > 0) ? (unsigned)nleft * 4u : 0u, 0x00020000);
-        const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 2u, offR = (unsigned)(lr * (int)p.ldr + 4 * lq) * 2u;
-        const unsigned rowO = (unsigned)ldo * 32u, rowR = (unsigned)p.ldr * 32u;       // bytes per 16-row block
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const bool colok = n_w0 + 16 * b + 4 * lq < p.N;
-            const u32x4 bcu = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-            u32x2 ru = __builtin_amdgcn_raw_buffer_load_b64(rsR, ((colok && m_w0 + lr < p.M) ? offR : OOB) + 32u * b, 0, 0);
-#pragma unroll
-            for (int a = 0; a < MB; ++a) {
-                const bool ok = colok && m_w0 + a * 16 + lr < p.M;
-                float rf[4];
-                if (isbf) {
-                    rf[0] = __uint_as_float(ru[0] << 16); rf[1] = __uint_as_float(ru[0] & 0xffff0000u);
-                    rf[2] = __uint_as_float(ru[1] << 16); rf[3] = __uint_as_float(ru[1] & 0xffff0000u);
-                } else {
-                    rf[0] = f16_bits_to_f32((unsigned short)(ru[0] & 0xffffu)); rf[1] = f16_bits_to_f32((unsigned short)(ru[0] >> 16));
-                    rf[2] = f16_bits_to_f32((unsigned short)(ru[1] & 0xffffu)); rf[3] = f16_bits_to_f32((unsigned short)(ru[1] >> 16));
-                }
-                float e[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) e[j] = (acc[a][b][j] * p.alpha + __uint_as_float(bcu[j])) + rf[j];
-                const u32x2 c = isbf ? u32x2{f32x2_to_bf16x2(e[0], e[1]), f32x2_to_bf16x2(e[2], e[3])} : u32x2{f32x2_to_f16x2(e[0], e[1]), f32x2_to_f16x2(e[2], e[3])};
-                if (a + 1 < MB)
-                    ru = __builtin_amdgcn_raw_buffer_load_b64(rsR, ((colok && m_w0 + (a + 1) * 16 + lr < p.M) ? offR : OOB) + 32u * b, (a + 1) * rowR, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(c, rsO, (ok ? offO + a * rowO : OOB) + 32u * b, 0, 0);
-            }
-        }
-        return;
-    }
-    if constexpr (!ROWS4)
-    if (vec_ok && odt != GEO4D_F32 && geglu) {
-        if constexpr (NB % 4 == 0) {
-            const bool isbf = odt == GEO4D_BF16;
-            const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((unsigned short*)O + obase + (long)m_w0 * ldo + (n_w0 >> 1)), 0, OOB, 0x00020000);
-            const int nleft = p.N - n_w0;
-            const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-                uniform_ptr(p.bias ? (const void*)(p.bias + n_w0) : p.zeros), 0, (p.bias && nleft > 0) ? (unsigned)nleft * 4u : 0u, 0x00020000);
-            const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 2u, rowO = (unsigned)ldo * 32u;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if ((b & 3) >= 2) continue;
-                const bool grp = n_w0 + 16 * (b & ~3) + 64 <= p.N;
-                const u32x4 bv = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
-                const u32x4 bg = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b + 128u, 0, 0);
-#pragma unroll
-                for (int a = 0; a < MB; ++a) {
-                    const bool ok = grp && m_w0 + a * 16 + lr < p.M;
-                    float e[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        e[j] = (acc[a][b][j] * p.alpha + __uint_as_float(bv[j])) * gelu_erf_f(acc[a][b + 2 < NB ? b + 2 : b][j] * p.alpha + __uint_as_float(bg[j]));
-                    const u32x2 c = isbf ? u32x2{f32x2_to_bf16x2(e[0], e[1]), f32x2_to_bf16x2(e[2], e[3])} : u32x2{f32x2_to_f16x2(e[0], e[1]), f32x2_to_f16x2(e[2], e[3])};
-                    __builtin_amdgcn_raw_buffer_store_b64(c, rsO, (ok ? offO + a * rowO : OOB) + (unsigned)(32 * (b >> 2) + 16 * (b & 1)) * 2u, 0, 0);
-                }
-            }
-        }
-        return;
-    }
-    // ---- generic path (activations, row-bias tables, per-row bias, 16-bit rows, unaligned rows): element by element ----------------
+    if constexpr (OSPLIT) store_split4((float*)d.O + row, col >> 2, e);     // (OSPLIT launches are never partial)
+    else if (d.odt == GEO4D_F32) *(f32x4*)((float*)d.O + oidx) = f32x4{e[0], e[1], e[2], e[3]};
+    else *(u32x2*)((unsigned short*)d.O + oidx) = pack4_16(e, d.odt == GEO4D_BF16);
+}
+
+// The generic path (activations; row-bias tables / per-row bias on 16-bit rows; unaligned rows): element by element.
+template <int MB, int NB, bool OSPLIT>
+__device__ __forceinline__ void generic_rows(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const EpiDest& d, const bool partial, const bool vec_ok,
+                                             const bool has_res, const long rbase, const int m_w0, const int n_w0, const int lr, const int lq) {
+    const int odt = d.odt;
 #pragma unroll
     for (int a = 0; a < MB; ++a) {
         const int m = m_w0 + a * 16 + lr;
         if (m >= p.M) continue;
         const float brow = (!partial && p.bias && p.bias_per_row) ? p.bias[m] : 0.f;
         const long rboff = (!partial && p.rowbias) ? (long)(m / p.rowbias_div) * (p.ldrb ? p.ldrb : (long)p.N) : 0;
-        if (geglu) {
+        const long orow = d.obase + (long)m * d.ldo;
+        if (d.geglu) {
             if constexpr (NB % 4 == 0) {
                 // packed GEGLU weights interleave value / gate in 32-column blocks: 16-blocks 4j, 4j+1 = value, 4j+2, 4j+3 = gate
 #pragma unroll
@@ -391,21 +230,9 @@ __device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f
                     const int oc = (n_w0 >> 1) + 32 * (b >> 2) + 16 * (b & 1) + 4 * lq;
                     float e[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float xv = acc[a][b][j] * p.alpha + (p.bias ? p.bias[n + j] : 0.f);
-                        const float gv = acc[a][b + 2 < NB ? b + 2 : b][j] * p.alpha + (p.bias ? p.bias[n + 32 + j] : 0.f);
-                        e[j] = xv * gelu_erf_f(gv);
-                    }
-                    const long oidx = obase + (long)m * ldo + oc;
-                    if (vec_ok) {
-                        if constexpr (OSPLIT) store_split4((float*)O + obase + (long)m * ldo, oc >> 2, e);
-                        else if (odt == GEO4D_F32) *(f32x4*)((float*)O + oidx) = f32x4{e[0], e[1], e[2], e[3]};
-                        else if (odt == GEO4D_BF16) *(u32x2*)((unsigned short*)O + oidx) = u32x2{f32x2_to_bf16x2(e[0], e[1]), f32x2_to_bf16x2(e[2], e[3])};
-                        else *(u32x2*)((unsigned short*)O + oidx) = u32x2{f32x2_to_f16x2(e[0], e[1]), f32x2_to_f16x2(e[2], e[3])};
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) store_out(O, oidx + j, e[j], odt);
-                    }
+                    for (int j = 0; j < 4; ++j)
+                        e[j] = geglu_value(p.alpha, acc[a][b][j], acc[a][b + 2 < NB ? b + 2 : b][j], p.bias ? p.bias[n + j] : 0.f, p.bias ? p.bias[n + 32 + j] : 0.f);
+                    store4_generic<OSPLIT>(d, vec_ok, orow, oc, e);
                 }
             }
             continue;
@@ -417,54 +244,70 @@ __device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f
             float e[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) e[j] = acc[a][b][j];
-            const long oidx = obase + (long)m * ldo + n;
             if (!partial) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = e[j] * p.alpha + brow;
-                    if (n + j < p.N) {
-                        if (p.bias && !p.bias_per_row) v += p.bias[n + j];
-                        if (p.rowbias) v += p.rowbias[rboff + n + j];
-                    }
-                    if (p.act == 1) v = silu_f(v);
-                    else if (p.act == 3) v = gelu_erf_f(v);
-                    e[j] = v;
-                }
+                for (int j = 0; j < 4; ++j) e[j] = epi_value(p, e[j], brow, rboff, n + j, n + j < p.N);
             }
             if (vec_ok) {
-                if (odt == GEO4D_F32) {
-                    if (has_res) {
+                if (has_res) {
+                    if (odt == GEO4D_F32) {
                         const f32x4 r = *(const f32x4*)((const float*)p.R + rbase + (long)m * p.ldr + n);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) e[j] += r[j];
+                    } else {
+                        float rf[4];
+                        unpack4_16(*(const u32x2*)((const unsigned short*)p.R + rbase + (long)m * p.ldr + n), odt == GEO4D_BF16, rf);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) e[j] += rf[j];
                     }
-                    if constexpr (OSPLIT) store_split4((float*)O + obase + (long)m * ldo, n >> 2, e);     // (OSPLIT launches are never partial)
-                    else *(f32x4*)((float*)O + oidx) = f32x4{e[0], e[1], e[2], e[3]};
-                } else {
-                    if (has_res) {
-                        const u32x2 r = *(const u32x2*)((const unsigned short*)p.R + rbase + (long)m * p.ldr + n);
-                        if (odt == GEO4D_BF16) {
-                            e[0] += __uint_as_float(r[0] << 16); e[1] += __uint_as_float(r[0] & 0xffff0000u);
-                            e[2] += __uint_as_float(r[1] << 16); e[3] += __uint_as_float(r[1] & 0xffff0000u);
-                        } else {
-                            e[0] += f16_bits_to_f32((unsigned short)(r[0] & 0xffffu)); e[1] += f16_bits_to_f32((unsigned short)(r[0] >> 16));
-                            e[2] += f16_bits_to_f32((unsigned short)(r[1] & 0xffffu)); e[3] += f16_bits_to_f32((unsigned short)(r[1] >> 16));
-                        }
-                    }
-                    if (odt == GEO4D_BF16) *(u32x2*)((unsigned short*)O + oidx) = u32x2{f32x2_to_bf16x2(e[0], e[1]), f32x2_to_bf16x2(e[2], e[3])};
-                    else *(u32x2*)((unsigned short*)O + oidx) = u32x2{f32x2_to_f16x2(e[0], e[1]), f32x2_to_f16x2(e[2], e[3])};
                 }
+                store4_generic<OSPLIT>(d, true, orow, n, e);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     if (n + j >= p.N) continue;
                     float v = e[j];
                     if (has_res) v += load_res(p.R, rbase + (long)m * p.ldr + n + j, odt);
-                    store_out(O, oidx + j, v, odt);
+                    store_out(d.O, orow + n + j, v, odt);
                 }
             }
         }
     }
+}
+
+// The dispatcher. T: the element type (4-byte types never take the 16-bit-row fast paths; the two-pass f16 type's OSPLIT output,
+// o_split = 2, is PLAIN f16 rows instead of bf16 hi | lo halves); VECONLY: the host checked the vector-store conditions (no scalar
+// fallback code).
+template <typename T, int MB, int NB, bool OSPLIT, bool VECONLY = false>
+__device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const int m_w0, const int n_w0,
+                                             const long e_bz, const int e_kz, const bool partial, const int lr, const int lq) {
+    const EpiDest d = epi_dest(p, partial, e_kz, e_bz);
+    const int odt = d.odt, oesz = d.oesz;
+    const bool geglu = d.geglu;
+    const bool has_res = !partial && p.R != nullptr;
+    const long rbase = e_bz * p.r_bs;
+    // 4-element vectors need 4-element aligned rows and bases (16 B for f32, 8 B for 16-bit outputs)
+    const bool vec_ok = VECONLY || ((d.nout & 3) == 0 && (d.ldo & 3) == 0 && (((uintptr_t)d.O + d.obase * oesz) % (4 * oesz)) == 0 &&
+                                    (!has_res || ((p.ldr & 3) == 0 && (((uintptr_t)p.R + rbase * oesz) % (4 * oesz)) == 0)));
+    if constexpr (OSPLIT && IsTwoPass<T>::value) {
+        // o_split = 2 (the two-pass f16 type; round 6): O = PLAIN f16 rows - the A operand of the next dtype-4 launch (GEGLU -> ff-out). The
+        // launcher checked: no split-K, no residual / row biases, act 0 or GEGLU, stored columns % 8 == 0, 16-byte aligned rows.
+        const unsigned short* corner = (unsigned short*)p.O + e_bz * p.o_bs + (long)m_w0 * p.ldo + (geglu ? (n_w0 >> 1) : n_w0);
+        if (geglu) geglu_fast<MB, NB, StoreF16Sat>(p, acc, corner, p.ldo, m_w0, n_w0, lr, lq);
+        else plain_fast16<MB, NB, false, StoreF16Sat>(p, acc, corner, p.ldo, nullptr, false, m_w0, n_w0, lr, lq);
+        return;
+    }
+    using Wide = std::conditional_t<OSPLIT, StoreSplit, StoreF32>;
+    const bool wide = vec_ok && odt == GEO4D_F32;       // (o_split: N % 8 == 0, so the two lanes of an 8-column group are in range together)
+    if (wide && !geglu && (partial || p.act == 0)) return wide_plain<MB, NB, Wide>(p, acc, d, partial, has_res, rbase, m_w0, n_w0, lr, lq);
+    if (wide && geglu) return geglu_fast<MB, NB, Wide>(p, acc, (float*)d.O + d.obase + (long)m_w0 * d.ldo + (n_w0 >> 1), d.ldo, m_w0, n_w0, lr, lq);
+    if constexpr (!IsX3<T>::value) {      // 16-bit rows (the bf16 / f16 modes): the same structures with 8-byte vectors
+        const unsigned short* row0 = (unsigned short*)d.O + d.obase + (long)m_w0 * d.ldo;
+        if (vec_ok && odt != GEO4D_F32 && !geglu && p.act == 0 && !p.rowbias && !(p.bias && p.bias_per_row))
+            return plain_fast16<MB, NB, true, StoreRows16>(p, acc, row0 + n_w0, d.ldo, (const unsigned short*)p.R + rbase + (long)m_w0 * p.ldr + n_w0, has_res, m_w0, n_w0, lr, lq);
+        if (vec_ok && odt != GEO4D_F32 && geglu) return geglu_fast<MB, NB, StoreRows16>(p, acc, row0 + (n_w0 >> 1), d.ldo, m_w0, n_w0, lr, lq);
+    }
+    generic_rows<MB, NB, OSPLIT>(p, acc, d, partial, vec_ok, has_res, rbase, m_w0, n_w0, lr, lq);
 }
 
 template <int BM, int BN>
@@ -548,26 +391,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
         const int s_begin = kz * per;
         nslab = min(nslab_all, s_begin + per) - s_begin;
         if (!direct_rows) {
-            // gather table: source pixel of (tile row, tap), -1 = zero padding. The previous tile's table is dead here: its last
-            // fetch_pix ran before the K loop's final barrier.
-            const int hlim = p.ups == 2 ? 2 * p.Hin : p.Hin, wlim = p.ups == 2 ? 2 * p.Win : p.Win;
-            const int ush = p.ups == 2 ? 1 : 0;
-            for (int e = tid; e < BM * ntap; e += NT) {
-                const int row = e / ntap, tp = e - row * ntap;
-                const int m = tm * BM + row;
-                int px = -1;
-                if (m < p.M) {
-                    const int f = m / hw, rem = m - f * hw;
-                    const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-                    const int kt = tp / (p.KH * p.KW), r2 = tp - kt * (p.KH * p.KW);
-                    const int ky = r2 / p.KW, kx = r2 - ky * p.KW;
-                    const int iy = oy * p.stride - p.ph + ky, ix = ox * p.stride - p.pw + kx;
-                    const int tt = (f % p.T) + kt - p.pt;
-                    if ((unsigned)iy < (unsigned)hlim && (unsigned)ix < (unsigned)wlim && (unsigned)tt < (unsigned)p.T)
-                        px = ((f + kt - p.pt) * p.Hin + (iy >> ush)) * p.Win + (ix >> ush);
-                }
-                rowpix[e] = px;
-            }
+            // the previous tile's table is dead here: its last fetch_pix ran before the K loop's final barrier
+            fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid);
             __syncthreads();
         }
         tap = tapB = s_begin % ntap;
@@ -603,17 +428,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
         if (++tapB == ntap) { tapB = 0; c0B += BK; }
     };
     f32x4 acc[MB][NB];
-    // fragment offsets inside a 16-row block: lane (lr, lq) reads row lr; 16-bit types: chunk 4h + lq of half h; bf16x3: chunks 2lq, 2lq + 1
-    const int fkey = swz_key<T>(lr);
     int foff[2];
-    if constexpr (IsX3<T>::value) {
-        foff[0] = lr * PITCH + (((2 * lq) ^ fkey) << 4);
-        foff[1] = lr * PITCH + (((2 * lq + 1) ^ fkey) << 4);
-    } else {
-        foff[0] = lr * PITCH + ((lq ^ fkey) << 4);
-        foff[1] = lr * PITCH + (((4 + lq) ^ fkey) << 4);
-    }
-    const bool a_split = HOT ? (HOT == 2) : (p.a_split != 0), w_split = HOT ? true : (p.w_split != 0);
+    frag_offsets<T>(lr, lq, foff);
+    const bool a_split = a_is_split<HOT>(p), w_split = w_is_split<HOT>(p);
     auto compute_slab = [&](int buf) {
         const char* abase = smem + (buf * BM + wr * WTM) * PITCH;
         const char* bbase = smem + (2 * BM + buf * BN + wc * WTN) * PITCH;
@@ -670,7 +487,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
 
     const bool partial = splits > 1;                  // split-K: raw fp32 slab, the epilogue runs in the reduce kernel
     auto epilogue = [&](int e_tm, int e_tn, long e_bz, int e_kz) {
-        reg_epilogue<MB, NB, OSPLIT, false, IsX3<T>::value, IsTwoPass<T>::value>(p, acc, e_tm * BM + wr * WTM, e_tn * BN + wc * WTN, e_bz, e_kz, partial, lr, lq);
+        reg_epilogue<T, MB, NB, OSPLIT>(p, acc, e_tm * BM + wr * WTM, e_tn * BN + wc * WTN, e_bz, e_kz, partial, lr, lq);
     };
 
     // ---- persistent tile loop --------------------------------------------------------------------------------------------------------
@@ -763,8 +580,7 @@ int launch_persistent_cfg(const geo4d_conv_gemm_t& p, const Plan& plan, hipStrea
     return GEO4D_EINVAL;      // (unreachable: resolve() gives the two-pass type hot = 2)
 }
 
-// tile hints of the second generation (16x16x32 MFMA, register epilogue, persistent workgroups). Round 4 kept the five the measured
-// table selects (profiles/r04_gemm_census_bf16x3.log); 21 / 24 / 26 / 29 and the three-A-buffer twins 31..39 are gone:
+// tile hints of the second generation (16x16x32 MFMA, register epilogue, persistent workgroups): the five the measured table selects
 //   22: 256x256, 8 waves (64x128 wave tiles)    23: 160x320, 8 waves (80x80)    25: 128x128, 4 waves (64x64)
 //   27: 64x128, 4 waves (32x64)                 28: 64x64, 4 waves (32x32)
 // The two-pass f16 type has no 256x256 instantiation (that tile spills a few registers around its K loop, and the long-K convolutions

@@ -26,7 +26,7 @@
 // only from 222 us to 210 us on the largest conv of the U-Net (+4.5 %), +/- 4 % elsewhere: with the DMA and the fragment reads off
 // the critical path the loop sits at ~75 % of what its MFMAs alone take on this chip (163 us, not the 103 us of the nominal clock).
 // Same ABI struct, same K order (channel-slab major, tap minor), same per-accumulator summation order as conv_gemm_v2_kernel:
-// results are bit-identical to tile hints 21..29.
+// results are bit-identical to the second-generation tile hints 22..28.
 #pragma once
 #include "gemm_kernel_v2.h"
 
@@ -262,18 +262,10 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
 
     // ---- MFMA side -------------------------------------------------------------------------------------------------------------------
     f32x4 acc[MB][NB];
-    // fragment offsets inside a 16-row block: lane (lr, lq) reads row lr; 16-bit types: chunk 4h + lq of K half h; bf16x3: chunks 2lq (hi), 2lq + 1 (lo)
-    const int fkey = swz_key<T>(lr);
     int foff[2];
-    if constexpr (IsX3<T>::value) {
-        foff[0] = lr * PITCH + (((2 * lq) ^ fkey) << 4);
-        foff[1] = lr * PITCH + (((2 * lq + 1) ^ fkey) << 4);
-    } else {
-        foff[0] = lr * PITCH + ((lq ^ fkey) << 4);
-        foff[1] = lr * PITCH + (((4 + lq) ^ fkey) << 4);
-    }
+    frag_offsets<T>(lr, lq, foff);
     const int foffA = lr * PITCH_A64 + ((lq ^ swz_key_a64(lr)) << 4);
-    const bool a_split = HOT ? (HOT == 2) : (p.a_split != 0), w_split = HOT ? true : (p.w_split != 0);
+    const bool a_split = a_is_split<HOT>(p), w_split = w_is_split<HOT>(p);
     u32x4 fa[2][2][MB0];                               // A fragments [half][bf16x3: hi | lo; 16-bit: K half][block]: every half panel has its own
     u32x4 fb[2][2][NB0];                               // registers, so that a phase can read the set the NEXT phase multiplies
     auto read_A = [&](auto hc, const char* sb) {
@@ -452,7 +444,7 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
             // (dozens of 64-bit row offsets) are hoisted out of the tile loop and live - spilled - across the K loop
             int lr_ = lr, lq_ = lq;
             asm volatile("" : "+v"(lr_), "+v"(lq_));
-            reg_epilogue<MB, NB, OSPLIT, true, IsX3<T>::value, IsTwoPass<T>::value>(p, acc, tmC * BM + wr * WTM, tnC * BN + wc * WTN, bzC, kzC, partial, lr_, lq_);
+            reg_epilogue<T, MB, NB, OSPLIT, true>(p, acc, tmC * BM + wr * WTM, tnC * BN + wc * WTN, bzC, kzC, partial, lr_, lq_);
         }
         // a REAL s_waitcnt vmcnt(0) (the builtin, which the compiler's wait-count pass tracks; an inline-asm one it does not see):
         // without it the pass has to assume pending loads into VGPRs at the K loop's header and drains the DMA queue every slab

@@ -1,4 +1,4 @@
-// geo4d_amd/csrc/gemm_v2_bf16x3.hip — second-generation conv_gemm kernels (tile hints 21..39) for element type bf16x3_t
+// geo4d_amd/csrc/gemm_v2_bf16x3.hip — second-generation conv_gemm kernels (tile hints 22..28) for element type bf16x3_t
 // (one translation unit per type: parallel build).
 #include "gemm_kernel_v2.h"
 

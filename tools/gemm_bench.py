@@ -59,7 +59,7 @@ def main():
     ap.add_argument("--explore", action="store_true", help="time every (tile, split) pair per shape and report the best")
     ap.add_argument("--explore-all", action="store_true", help="per shape: every candidate of the host tuner (ops._CANDIDATES, all three kernel generations x split-K) "
                     "at `--iters` launches each, the 6 best re-measured interleaved; prints the table's choice next to the best (round 4: the tuner's own sample was too noisy)")
-    ap.add_argument("--explore2", action="store_true", help="per shape: best 32x32-MFMA configuration (tile hints 1..17) vs best second-generation one (21..29), and every 21..29 tile at split 1")
+    ap.add_argument("--explore2", action="store_true", help="per shape: best 32x32-MFMA configuration (tile hints 1..17) vs best second-generation one (22..28), and every 22..28 tile at split 1")
     ap.add_argument("--tiles", default="", help="comma list of tile hints to time per shape (split 1), e.g. the ablation builds 40..64")
     ap.add_argument("--zeros", action="store_true", help="zero-filled operands: same instruction stream, no data toggling (how much of the time is the chip's power-limited clock?)")
     ap.add_argument("--presplit", action="store_true", help="bf16x3: hand the activation over in the producers' pre-split format (what the networks run)")
@@ -217,7 +217,7 @@ def main():
             print(f"  {nm:34s} best t{cfg[0]}/s{cfg[1]} {u:8.1f} us   table {ut:8.1f} us   ({ut / u:4.2f}x)")
     if args.explore2:
         t1, t2 = globals()["_TOT2"]
-        print(f"census with the best 32x32-MFMA configuration per shape: {t1:.1f} ms; with the best 21..29 configuration per shape: {t2:.1f} ms")
+        print(f"census with the best 32x32-MFMA configuration per shape: {t1:.1f} ms; with the best 22..28 configuration per shape: {t2:.1f} ms")
 
 
 if __name__ == "__main__":
