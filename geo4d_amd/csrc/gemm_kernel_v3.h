@@ -151,7 +151,8 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
         refresh_B();
     };
     // the A window of tile (tm_, bz_): base = the tap-0 source pixel of the tile's first row (the smallest address any of its rows
-    // reads; it may lie before the tensor when that pixel is padding - only in-image taps are ever dereferenced)
+    // reads - v3_native in gemm_plan.h admits only geometries in which the tap-0 pixel never decreases with the row; it may lie before
+    // the tensor when that pixel is padding - only in-image taps are ever dereferenced)
     auto tap0_pixel = [&](int m) -> long {
         const int f = m / hw, rem = m - f * hw;
         const int oy = rem / p.Wout, ox = rem - oy * p.Wout;

@@ -90,7 +90,8 @@ inline bool o_f16_ok(const geo4d_conv_gemm_t& p, int splits) {
 }
 
 // Does the third generation's phased stream take this launch? Not an odd number or fewer than 4 K slabs per tile, an uneven split-K,
-// outputs that are not 4-element aligned, nearest-upsampling gathers, operands beyond the 2 GB buffer window.
+// outputs that are not 4-element aligned, nearest-upsampling gathers, operands beyond the 2 GB buffer window, a geometry whose rows do not
+// walk forward through the input (padding wider than the kernel's reach).
 inline bool v3_native(const geo4d_conv_gemm_t& p, int sp, int nslab, long esz, long esz_a) {
     // the phased kernel carries the vector-store epilogue only (its scalar fallback costs ~900 spilled registers there)
     const bool geglu = sp == 1 && p.act == 2;
@@ -107,7 +108,14 @@ inline bool v3_native(const geo4d_conv_gemm_t& p, int sp, int nslab, long esz, l
     // no uniform tap offsets, and a tile's rows plus its taps must stay inside the window
     const long frames = 256 / ((long)p.Hout * p.Wout) + 2 + p.KT;
     const bool window_ok = p.ups == 1 && frames * p.Hin * p.Win * p.lda * esz_a < (1L << 31) && (320L * p.ldw + p.K) * esz < (1L << 31);
-    return !(nslab % sp || ((nslab / sp) & 1) || nslab / sp < 4 || !vec_ok || !window_ok);
+    // a lane's offset is UNSIGNED and relative to the tap-0 pixel of the tile's first row: that pixel must be the smallest of the tile, i.e.
+    // tap-0 pixel(row m) = (f - pt) Hin Win + (oy stride - ph) Win + ox stride - pw must not decrease from the end of one output row to the
+    // start of the next, nor from the last row of a frame to the first of the next (a smaller one wraps beyond the window and the row's
+    // in-image taps are staged as zeros). The networks' convolutions (pad <= (K - 1) / 2, a 3x3 with pad_end) pass; the first condition
+    // is stricter than needed where Hout == 1 and a 1x1 with pad_end fails it - such a launch only runs the tile's alt. The second also
+    // bounds a frame's rows by a frame of pixels, which `frames` above assumes.
+    const bool forward = (long)p.Wout - 1 <= p.Win && ((long)(p.Hout - 1) * p.Win + (p.Wout - 1)) * p.stride <= (long)p.Hin * p.Win;
+    return !(nslab % sp || ((nslab / sp) & 1) || nslab / sp < 4 || !vec_ok || !window_ok || !forward);
 }
 
 // Tile choice without a hint (first generation): score = MFMA efficiency of the tile shape x useful fraction x how full the last wave of

@@ -110,6 +110,41 @@ def test_colsum_rows_answers_as_before_the_planner():
     assert seen == {1: {False, True}, 2: {False, True}, 3: {False, True}}, seen
 
 
+def geometry_descriptor(Hin, Win, KH, KW, ph, pw, frames, Cin=128, stride=1, hint=73):
+    """bf16 rows in, f32 rows out, hint 73 (256 x 128 on 2 x 4 waves: 128 rows per gn_colsum entry; its second-generation twin 25: 64)."""
+    Hout, Wout = (Hin + 2 * ph - KH) // stride + 1, (Win + 2 * pw - KW) // stride + 1
+    M, K = frames * Hout * Wout, KH * KW * Cin
+    p = descriptor(f"{M}x64x{K}|c{Cin}|t1{KH}{KW}s{stride}u1", 1, 1, Hout, Wout, FORMATS[1], hint, 1, 0, 0, 0)
+    p.Hin, p.Win, p.ph, p.pw = Hin, Win, ph, pw
+    return p
+
+
+def test_geometries_whose_rows_walk_backwards_leave_the_third_generation():
+    """The third generation addresses a tile's rows with unsigned offsets from the first tap of the tile's first row, so it may only take
+    geometries in which that pixel never decreases with the row: Wout - 1 <= Win and ((Hout - 1) Win + Wout - 1) stride <= Hin Win.
+    Descriptors on both sides of each condition, told apart by the rows per gn_colsum entry of the tile that really runs (128 on hint
+    73, 64 on its second-generation twin); every one has an even number >= 4 of K slabs and M a multiple of 128."""
+    from geo4d_amd import _lib
+    lib = _lib.load()
+    rows = lambda p: lib.geo4d_conv_gemm_colsum_rows(ctypes.byref(p))
+    native = [geometry_descriptor(8, 8, 3, 3, 1, 1, 16),                  # the networks' 3x3, pad 1
+              geometry_descriptor(8, 8, 3, 3, 1, 1, 32, stride=2),        # stride 2
+              geometry_descriptor(7, 3, 2, 3, 1, 0, 16),                  # both conditions with equality: Hout = Hin + 1, Wout = 1
+              geometry_descriptor(8, 8, 1, 2, 0, 1, 16, Cin=256)]         # a 1x2 kernel with pad (0, 1): Wout - 1 == Win, again with equality in both
+    redirected = [geometry_descriptor(8, 8, 3, 3, 2, 2, 32),              # 3x3 with pad 2: both conditions broken
+                  geometry_descriptor(8, 8, 3, 3, 2, 1, 16),              # rows only: Hout = Hin + 2 (the second condition)
+                  geometry_descriptor(8, 8, 3, 3, 0, 2, 32),              # columns only: Wout - 1 = 9 > Win, 5 * 8 + 9 <= 64 (the first condition)
+                  geometry_descriptor(8, 8, 3, 3, 1, 2, 16),              # pad (1, 2): both again, the second by one pixel (65 > 64)
+                  geometry_descriptor(6, 6, 1, 1, 1, 1, 2, Cin=256)]      # a padded 1x1 (both)
+    for p in native + redirected:
+        assert p.M % 128 == 0 and (p.K // 64) % 2 == 0 and p.K // 64 >= 4, (p.M, p.K)
+    assert [rows(p) for p in native] == [128] * len(native)
+    assert [rows(p) for p in redirected] == [64] * len(redirected)
+    for p in native + redirected:      # the second-generation tile itself answers 64 either way
+        p.tile_hint = 25
+        assert rows(p) == 64
+
+
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     from geo4d_amd import _lib

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from conv_cases import both_grids
+
 pytestmark = pytest.mark.gpu
 
 V2_TILES = [22, 23, 25, 27, 28]
@@ -38,19 +40,6 @@ def pack_mode(mode):
 def rounded(t, mode):
     """The value the kernel multiplies: operands are rounded to the mode's storage type (bf16x3 keeps ~16 mantissa bits: exact here)."""
     return t.to(act_dtype(mode)).float()
-
-
-def both_grids(fn):
-    """fn() with the production grid and with 3 persistent workgroups; returns the production result after checking equality."""
-    from geo4d_amd import ops
-    a = fn()
-    ops.DEBUG_ABLATE = 2
-    try:
-        b = fn()
-    finally:
-        ops.DEBUG_ABLATE = 0
-    assert torch.equal(a, b), f"persistent-loop result differs from one-tile-per-workgroup result: {rel(b, a):.3e}"
-    return a
 
 
 def check(name, got, ref, mode, scale=1.0):
