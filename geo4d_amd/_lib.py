@@ -164,6 +164,10 @@ SIGNATURES = {
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_pnp_ransac_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "geo4d_pnp_ransac": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_last_error": (C.c_char_p, []),
     "geo4d_align_refresh": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),
     "geo4d_align_small_grads": (C.c_int, [C.POINTER(AlignSmall), C.c_void_p]),

@@ -666,7 +666,7 @@ class GroupAligner:
 
     # ---- initialisation (init_im_poses.py:82-181, 569-635) ----------------------------------------------------------------------
     @torch.no_grad()
-    def init_from_group(self, traj, focal=None, raymaps=None, pose_init="traj", niter_PnP=100, pnp_seed=0):
+    def init_from_group(self, traj, focal=None, raymaps=None, pose_init="traj", niter_PnP=100, pnp_seed=0, pnp_backend="host"):
         """pose_init = "pnp": the reference's initialisation (init_im_poses.align_group :82-214): windows chained by registration
         WITHOUT overwriting an image's first estimate, every camera from seeded RANSAC-PnP of its chained point map against the
         pixel grid (geo4d_amd/pnp.py, confidence > 0.5), tried at the image's ray-map focal and -/+ 3 % of the image size; images of
@@ -680,16 +680,20 @@ class GroupAligner:
         traj [G, S, 4, 4]: camera-to-world of every frame in its window's own frame (the Plücker cameras of N2);
         focal: pixels; raymaps [G, S, H, W, 3] (pred_pts['raydir']): when given and `focal` is None, every image's focal is the
         Weiszfeld estimate on its first ray map and the shared focal their mean, as align_group / init_from_pts3d_group do
-        (init_im_poses.py:133-136, 183-185, 627-628); with neither, the focal is estimated from window 0's first point map."""
+        (init_im_poses.py:133-136, 183-185, 627-628); with neither, the focal is estimated from window 0's first point map.
+        pnp_backend: "host" (default, geo4d_amd/pnp.py in numpy) or "device" (ops.pnp_ransac, csrc/pnp.hip: the same solver hypothesis
+        for hypothesis, the image chain enqueued without host copies; see _init_prefix / _init_pnp). Used by "pnp" and "prefix" only."""
+        if pnp_backend not in ("host", "device"):
+            raise ValueError(f"pnp_backend={pnp_backend!r}: 'host' or 'device'")
         G, S, H, W = self.G, self.S, self.H, self.W
         pred = self.pred.reshape(G, S, H * W, 3)
         conf = self.conf.reshape(G, S, H * W)
         pts3d, conf_list, im_poses = [None] * self.n, [None] * self.n, [None] * self.n
         done = set()
         if pose_init == "pnp":
-            return self._init_pnp(pred, conf, focal, raymaps, niter_PnP, pnp_seed)
+            return self._init_pnp(pred, conf, focal, raymaps, niter_PnP, pnp_seed, pnp_backend)
         if pose_init == "prefix":
-            return self._init_prefix(pred, conf, focal, niter_PnP, pnp_seed)
+            return self._init_prefix(pred, conf, focal, niter_PnP, pnp_seed, pnp_backend)
         if pose_init != "traj":
             raise ValueError(f"pose_init={pose_init!r}: 'traj', 'pnp' or 'prefix'")
         for k, i in enumerate(self.groups[0]):
@@ -759,12 +763,91 @@ class GroupAligner:
         return self
 
 
-def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
-    """GroupAligner.init_from_group(pose_init="pnp"): align_group + init_from_pts3d_group of the reference (see the docstring there)."""
+class _DevicePnp:
+    """What the device backend of the "pnp" / "prefix" initialisations keeps: the sampler's tables of every (window, frame) slot, uploaded
+    once (the masked-pixel counts come from ONE reduction and ONE host copy before the chain starts), the per-image focals (NaN = unset)
+    and camera-to-world poses (identity = unset) as device arrays ops.pnp_ransac writes in place on success, and the status words."""
+
+    def __init__(self, scene, conf, niter_PnP, seed):
+        from . import ops, pnp
+        G, S = scene.G, scene.S
+        counts = (conf > 0.5).sum(-1).reshape(-1).cpu().tolist()                              # the one host wait before the chain
+        self.tables = ops.PnpTables([pnp.sample_tables(n, niter_PnP, seed) for n in counts], counts, niter_PnP, scene.dev)
+        self.scene, self.iterations = scene, int(niter_PnP)
+        self.focals = torch.full((scene.n,), float("nan"), device=scene.dev, dtype=torch.float64)
+        self.poses = torch.eye(4, device=scene.dev, dtype=torch.float64).repeat(scene.n, 1, 1)
+        self.status = torch.full((G * S,), -1, device=scene.dev, dtype=torch.int32)          # -1: the slot was not solved
+        self.delta = 0.03 * max(scene.H, scene.W)                                            # fast_pnp's -/+ 3 % of the image size
+
+    def solve(self, slots, points, conf, base, focal_out, pose_out):
+        """One launch for the `slots` (flat window * S + frame indices) with points [B, H W, 3], conf [B, H W], base focals [B] fp64."""
+        from . import ops
+        sc, B = self.scene, len(slots)
+        cand = torch.stack([base, -self.delta + base, self.delta + base], 1)                 # fast_pnp: [focal] + geomspace(-d + focal, d + focal, 2)
+        _, _, status, _ = ops.pnp_ransac(points.reshape(B, sc.H, sc.W, 3), conf.reshape(B, sc.H, sc.W), cand, self.tables.rows(slots),
+                                         iterations=self.iterations, out=(focal_out, pose_out))
+        if slots == list(range(slots[0], slots[0] + B)):
+            self.status[slots[0]:slots[0] + B] = status
+        else:
+            self.status[torch.as_tensor(slots, device=sc.dev)] = status
+
+    def finish(self):
+        """The one copy at the end: (status words [G, S], focals as the host path's list (None = unset), poses as its fp32 list)."""
+        sc = self.scene
+        host = torch.cat([self.status.double(), self.focals]).cpu()
+        status = host[:sc.G * sc.S].to(torch.int32).reshape(sc.G, sc.S)
+        focals = [None if math.isnan(f) else f for f in host[sc.G * sc.S:].tolist()]
+        return status, focals, [M.float() for M in self.poses]
+
+
+def _record_pnp_status(self, status):
+    """pnp_status [G, S] int32 of the last "pnp" / "prefix" initialisation: -1 slot not solved, 0 solved, else the failure (the device
+    backend's status bits of ops.pnp_ransac; the host backend knows only success, and records 1 for any failure)."""
+    self.pnp_status = status
+
+
+def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed, backend="host"):
+    """GroupAligner.init_from_group(pose_init="pnp"): align_group + init_from_pts3d_group of the reference (see the docstring there).
+    backend "device": the first window's images in one ops.pnp_ransac launch, every later window's newly seen images in one launch, base
+    focals from estimate_focal_weiszfeld kept on the device; results are applied only where the host code applies them (an image's
+    first pose, the focal of first-window images). A base focal the solver cannot use (no ray maps: the host would search 63 candidates)
+    reruns the whole initialisation on the host."""
     from . import pnp
     G, S, H, W = self.G, self.S, self.H, self.W
     pts3d, conf_list, im_poses, im_focals = [None] * self.n, [None] * self.n, [None] * self.n, [None] * self.n
     rm = None if raymaps is None else raymaps.reshape(G, S, H, W, 3)
+    if backend == "device":
+        dp = _DevicePnp(self, conf, niter_PnP, seed)
+
+        def launch(g, ks, first_window):
+            idx = torch.as_tensor([self.groups[g][k] for k in ks], device=self.dev)
+            # per image, as the host path calls it: a batched reduction may round differently, and the candidates must be the same bits
+            base = (torch.cat([estimate_focal_weiszfeld(rm[g, k][None].to(self.dev)) for k in ks]).double() if rm is not None
+                    else torch.full((len(ks),), float("nan"), device=self.dev, dtype=torch.float64))
+            fo, po = base.clone(), dp.poses[idx]
+            dp.solve([g * S + k for k in ks], torch.stack([pts3d[self.groups[g][k]] for k in ks]), conf[g, ks], base, fo, po)
+            dp.focals[idx] = fo if first_window else base
+            dp.poses[idx] = po
+        for k, i in enumerate(self.groups[0]):
+            pts3d[i], conf_list[i] = pred[0, k].clone(), conf[0, k].clone()
+        launch(0, list(range(len(self.groups[0]))), True)
+        for g in range(1, G):
+            grp = self.groups[g]
+            assert pts3d[grp[0]] is not None, "the first image of every window must belong to an earlier window"
+            seen = [k for k, i in enumerate(grp) if pts3d[i] is not None]
+            s, R, T = rigid_points_registration(pred[g, seen], torch.stack([pts3d[grp[k]] for k in seen]),
+                                                torch.stack([conf[g, k] * conf_list[grp[k]] for k in seen]))
+            new = [k for k, i in enumerate(grp) if pts3d[i] is None]
+            for k in new:
+                pts3d[grp[k]], conf_list[grp[k]] = s * (pred[g, k] @ R.t()) + T, conf[g, k].clone()
+            if new:
+                launch(g, new, False)
+        status, im_focals, im_poses = dp.finish()
+        if bool(((status > 0) & ((status & 4) != 0)).any()):
+            return self._init_pnp(pred, conf, focal, raymaps, niter_PnP, seed, "host")
+        _record_pnp_status(self, status)
+        return self._finish_group_init(pred, conf, pts3d, conf_list, im_poses, im_focals, focal)
+    ok = torch.full((G, S), -1, dtype=torch.int32)
 
     def ray_focal(g, k):
         return None if rm is None else float(estimate_focal_weiszfeld(rm[g, k][None].to(self.dev))[0])
@@ -777,6 +860,7 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
         pts3d[i], conf_list[i] = pred[0, k].clone(), conf[0, k].clone()
         im_focals[i] = ray_focal(0, k)
         res = run_pnp(i, 0, k)
+        ok[0, k] = 0 if res else 1
         if res:
             im_focals[i], im_poses[i] = res[0], torch.from_numpy(res[1]).float().to(self.dev)
         if im_poses[i] is None:
@@ -797,7 +881,10 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
             # the PnP result is only used where pose / focal are still unset (both assignments below are `is None`-guarded, as in the
             # reference) and the solver's sampler is re-seeded per call: skipping the call for already-initialised images (~3 of 4
             # occurrences at stride 4) changes nothing but the start-up time (host-side numpy RANSAC)
-            res = run_pnp(i, g, k) if (im_poses[i] is None or im_focals[i] is None) else None
+            res = None
+            if im_poses[i] is None or im_focals[i] is None:
+                res = run_pnp(i, g, k)
+                ok[g, k] = 0 if res else 1
             if res:
                 if im_poses[i] is None:
                     im_poses[i] = torch.from_numpy(res[1]).float().to(self.dev)
@@ -805,6 +892,7 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed):
                     im_focals[i] = res[0]
             if im_poses[i] is None:
                 im_poses[i] = torch.eye(4, device=self.dev)
+    _record_pnp_status(self, ok)
     return self._finish_group_init(pred, conf, pts3d, conf_list, im_poses, im_focals, focal)
 
 
@@ -854,7 +942,7 @@ def filter_outlier_focals(focal_group):
     return focal_group, mean
 
 
-def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
+def _init_prefix(self, pred, conf, focal, niter_PnP, seed, backend="host"):
     """GroupAligner.init_from_group(pose_init="prefix"): align_group_prefix + init_from_pts3d_group of the reference.
       1. the reference frame of every window, z - min(z) + 1 with ONE min over all of them (:259-260), pixels with confidence > 0.5, the
          shift / focal solve at full resolution (:261) -> one focal in pixels per window (:262-263), outliers replaced (:264-269);
@@ -863,7 +951,12 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
       2. window 0 is the world frame; later windows are registered onto the chained cloud and OVERWRITE the point map and confidence
          of the images they share with it (:347-355).
       3. every image of every window: RANSAC-PnP started at `temp_focal` = the window's focal for its reference frame, else the current
-         focal of the PREVIOUS image (:307-311, 372-376); pose and focal are overwritten on success (:381-388)."""
+         focal of the PREVIOUS image (:307-311, 372-376); pose and focal are overwritten on success (:381-388).
+    backend "device": step 3 through ops.pnp_ransac in the same order, one launch per image (B = 1, C = 3). The candidates are built on the
+    device from the device-resident focal array the previous launch wrote (or left alone, when it failed: the earlier window's value
+    stays), so between the masked-pixel counts copied up front and the status words copied at the end the PnP chain reads nothing back;
+    the window registrations of step 2 keep their own 3 x 3 host solve. A start focal that is unset or unusable (where the host would
+    search 63 candidates) reruns the whole initialisation on the host. The `except` path of step 1 stays on the host."""
     from . import geometry, pnp
     G, S, H, W = self.G, self.S, self.H, self.W
     pts3d, conf_list, im_poses, im_focals = [None] * self.n, [None] * self.n, [None] * self.n, [None] * self.n
@@ -885,6 +978,9 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
         msk = (conf[g, k] > 0.5).reshape(H, W).cpu().numpy()
         return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), temp_focal, msk, niter_PnP=niter_PnP, seed=seed)
     done = set()
+    dp = _DevicePnp(self, conf, niter_PnP, seed) if backend == "device" else None
+    window_focals = torch.tensor(focal_group, dtype=torch.float64, device=self.dev) if dp else None
+    ok = torch.full((G, S), -1, dtype=torch.int32)
     for g, grp in enumerate(self.groups):
         if g:
             assert grp[0] in done, "the first image of every window must belong to an earlier window"
@@ -892,6 +988,18 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
             s, R, T = rigid_points_registration(pred[g, seen], torch.stack([pts3d[grp[k]] for k in seen]),
                                                 torch.stack([conf[g, k] * conf_list[grp[k]] for k in seen]))
         for k, i in enumerate(grp):
+            if dp:                                                   # the same bookkeeping on the device-resident focal array
+                if g == 0:
+                    if k == 0:
+                        dp.focals[i] = window_focals[0]
+                    pts3d[i], conf_list[i] = pred[0, k].clone(), conf[0, k].clone()
+                    temp = dp.focals[i - 1:i] if i != 0 else dp.focals[i:i + 1]
+                else:
+                    pts3d[i], conf_list[i] = s * (pred[g, k] @ R.t()) + T, conf[g, k].clone()
+                    temp = window_focals[g:g + 1] if k == 0 else dp.focals[i - 1:i]
+                done.add(i)
+                dp.solve([g * S + k], pts3d[i][None], conf[g, k][None], temp.clone(), dp.focals[i:i + 1], dp.poses[i:i + 1])
+                continue
             if g == 0:
                 if k == 0:
                     im_focals[i] = focal_group[0]
@@ -902,10 +1010,16 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed):
                 temp_focal = focal_group[g] if k == 0 else im_focals[i - 1]
             done.add(i)
             res = run_pnp(i, g, k, temp_focal)
+            ok[g, k] = 0 if res else 1
             if res:
                 im_focals[i], im_poses[i] = res[0], torch.from_numpy(res[1]).float().to(self.dev)
             if im_poses[i] is None:
                 im_poses[i] = torch.eye(4, device=self.dev)
+    if dp:
+        ok, im_focals, im_poses = dp.finish()
+        if bool(((ok > 0) & ((ok & 4) != 0)).any()):
+            return self._init_prefix(pred, conf, focal, niter_PnP, seed, "host")
+    _record_pnp_status(self, ok)
     return self._finish_group_init(pred, conf, pts3d, conf_list, im_poses, im_focals, focal)
 
 
@@ -914,7 +1028,7 @@ GroupAligner._init_prefix = _init_prefix
 
 def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03, align=True, intrinsics=None,
                       use_raymap=True, use_inverse_depthmap=True, use_traj=True, pointmap_vae_used=True, depth_traj_start_iter=150,
-                      sharded=None, pose_init="traj", imgs=None):
+                      sharded=None, pose_init="traj", imgs=None, pnp_backend="host"):
     """The consumer of the gathered clip: ``post_optimization`` of scripts/evaluation/test_geo4d.py:30-51 with the pred_list its
     window loop builds (:446-501). ``slices`` / ``maps [n_windows, 11, T, H, W]`` / ``traj [n_windows, T, 4, 4]`` are what
     ``pipeline.run_clip(..., with_cameras=True)`` returns; ``args`` = the config's ``postprocess`` tree (a dict or any object with
@@ -926,7 +1040,8 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     ``imgs``: the clip's frames in [-1, 1] (``[1, 3, T, H, W]`` as run_clip takes them, ``[3, T, H, W]`` or ``[T, 3, H, W]``) or uint8,
     kept as ``scene.imgs`` [n, H, W, 3] in [0, 1] (dust3r.utils.image.rgb) for the export (geo4d_amd/scene_export.py).
     ``pose_init``: "traj" (default, Plücker cameras), "pnp" (align_group, the reference's opt_raydir branch) or "prefix"
-    (align_group_prefix, what the reference's script runs with its use_raymap = False): GroupAligner.init_from_group."""
+    (align_group_prefix, what the reference's script runs with its use_raymap = False): GroupAligner.init_from_group.
+    ``pnp_backend``: "host" (default) or "device", the RANSAC-PnP backend of the "pnp" and "prefix" initialisations."""
     from .pipeline import postprocess_window
     get = (lambda k, d: args.get(k, d)) if isinstance(args, dict) else (lambda k, d: getattr(args, k, d))
     if args is None:
@@ -950,7 +1065,8 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     if intrinsics is not None:
         per_image = (intrinsics[:, 0, 0] + intrinsics[:, 1, 1]) / 2.0
         focal = per_image.to(scene.dev).float() if not scene.shared_focal else float(per_image.float().mean())
-    scene.init_from_group(traj, focal=focal, raymaps=torch.stack([p["raymap"] for p in post]) if use_raymap else None, pose_init=pose_init)
+    scene.init_from_group(traj, focal=focal, raymaps=torch.stack([p["raymap"] for p in post]) if use_raymap else None, pose_init=pose_init,
+                          pnp_backend=pnp_backend)
     if intrinsics is not None:
         scene.frozen.add("im_focals")
     if imgs is not None:

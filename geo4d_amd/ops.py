@@ -1014,3 +1014,104 @@ def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=Non
     _lib.check(lib.geo4d_focal_shift(points.data_ptr(), points.stride(0), wp, wstride, float(thr), _ptr(z_offset), B, H, W, h_lr, w_lr, int(iters),
                                      shift.data_ptr(), focal.data_ptr(), status.data_ptr(), ws.data_ptr(), need, _stream()), "geo4d_focal_shift")
     return shift, focal, status
+
+
+PNP_FEW, PNP_NO_CONSENSUS, PNP_BAD_FOCAL, PNP_BAD_TABLES = 1, 2, 4, 8       # status bits of pnp_ransac
+
+
+class PnpTables:
+    """pnp.sample_tables of B images on the device, in the layout geo4d_pnp_ransac reads: n [B], m [B], sub [B, max_points],
+    draws [B, iterations, 6], all int32 (rows padded with zeros). Built once per set of masked-pixel counts and reused."""
+
+    def __init__(self, tables, n, iterations, device):
+        import numpy as np
+        B = len(tables)
+        if B == 0 or len(n) != B:
+            raise ValueError("pnp tables: one (sub, draws) pair and one masked-pixel count per image")
+        self.iterations = int(iterations)
+        self.max_points = max(6, max(len(t[0]) for t in tables))
+        sub = np.zeros((B, self.max_points), np.int32)
+        draws = np.zeros((B, self.iterations, 6), np.int32)
+        m = np.zeros(B, np.int32)
+        for b, (s, d) in enumerate(tables):
+            s, d = np.asarray(s), np.asarray(d)
+            if d.size and (d.shape[0] < self.iterations or d.shape[1] != 6):
+                raise ValueError(f"pnp tables: draws of image {b} are {d.shape}, need at least [{self.iterations}, 6]")
+            m[b] = len(s)
+            sub[b, :len(s)] = s
+            if d.size:
+                draws[b] = d[:self.iterations]
+        host = torch.from_numpy(np.concatenate([np.asarray(n, np.int32).reshape(B), m, sub.reshape(-1), draws.reshape(-1)]))
+        flat = host.to(device)                                  # one upload
+        self.B = B
+        self.n, self.m = flat[:B], flat[B:2 * B]
+        self.sub = flat[2 * B:2 * B + B * self.max_points].view(B, self.max_points)
+        self.draws = flat[2 * B + B * self.max_points:].view(B, self.iterations * 6)
+
+    def rows(self, which):
+        """The tables of the images `which` (a list of indices) as another PnpTables: views for a contiguous run, else a device gather."""
+        which = [int(w) for w in which]
+        t = object.__new__(PnpTables)
+        t.B, t.iterations, t.max_points = len(which), self.iterations, self.max_points
+        if which == list(range(which[0], which[0] + len(which))):
+            sl = slice(which[0], which[0] + len(which))
+            t.n, t.m, t.sub, t.draws = self.n[sl], self.m[sl], self.sub[sl], self.draws[sl]
+        else:
+            ix = torch.as_tensor(which, device=self.n.device)
+            t.n, t.m, t.sub, t.draws = self.n[ix], self.m[ix], self.sub[ix], self.draws[ix]
+        return t
+
+
+def pnp_ransac(points, conf, cand_focals, tables, *, thr=0.5, reproj=5.0, iterations, pp=None, out=None):
+    """Batched RANSAC-PnP of geo4d_amd/pnp.py on the device (csrc/pnp.hip): B images x C candidate focals in one enqueue, nothing read
+    back. points fp32 [B, H, W, 3] world points (any image stride), conf [B, H, W] (pixels with conf > thr take part), cand_focals fp64
+    [B, C] ON THE DEVICE (C <= 64); `tables`: a PnpTables, or a list of B `(sub, draws, n)` triples / `(sub, draws)` pairs of
+    pnp.sample_tables (n = the image's masked-pixel count; with a pair, len(sub) when that is below the sampler's max_points);
+    pp = (x, y), default (W / 2, H / 2). Returns (focal [B] fp64, c2w [B, 4, 4] fp64, status [B] int32, info [B, C, 4] int32): focal and
+    pose are written only where status == 0 - pass `out=(focal, c2w)` to keep earlier values on failure (fresh outputs start at NaN).
+    status bits: PNP_FEW, PNP_NO_CONSENSUS, PNP_BAD_FOCAL, PNP_BAD_TABLES; info = iterations run, chosen hypothesis, sub-sample inliers
+    after the refit, inliers over all masked pixels."""
+    lib = _lib.load()
+    _dev(points, "points"); _dev(conf, "conf"); _dev(cand_focals, "cand_focals")
+    if points.dtype != torch.float32 or points.dim() != 4 or points.shape[-1] != 3 or 0 in points.shape:
+        raise ValueError(f"pnp_ransac: points must be a non-empty fp32 [B, H, W, 3] tensor, got {points.dtype} {tuple(points.shape)}")
+    B, H, W, _ = points.shape
+    if points.stride()[1:] != (3 * W, 3, 1) or (B > 1 and points.stride(0) < 0):
+        points = points.contiguous()
+    if tuple(conf.shape) != (B, H, W) or conf.device != points.device:
+        raise ValueError(f"pnp_ransac: conf must be [B, H, W] = {(B, H, W)} on {points.device}, got {tuple(conf.shape)} on {conf.device}")
+    if conf.dtype != torch.float32:
+        conf = conf.float()
+    if conf.stride()[1:] != (W, 1) or (B > 1 and conf.stride(0) < 0):
+        conf = conf.contiguous()
+    if cand_focals.dtype != torch.float64 or cand_focals.dim() != 2 or cand_focals.shape[0] != B or not 1 <= cand_focals.shape[1] <= 64:
+        raise ValueError(f"pnp_ransac: cand_focals must be fp64 [B, C] with 1 <= C <= 64, got {cand_focals.dtype} {tuple(cand_focals.shape)}")
+    cand_focals = cand_focals.contiguous()
+    C = cand_focals.shape[1]
+    iterations = int(iterations)
+    if iterations <= 0:
+        raise ValueError(f"pnp_ransac: iterations {iterations} must be positive")
+    if not isinstance(tables, PnpTables):
+        tables = list(tables)
+        tables = PnpTables([t[:2] for t in tables], [t[2] if len(t) > 2 else len(t[0]) for t in tables], iterations, points.device)
+    if tables.B != B or tables.iterations != iterations or tables.n.device != points.device:
+        raise ValueError(f"pnp_ransac: tables are for {tables.B} images x {tables.iterations} iterations on {tables.n.device}")
+    px, py = (W / 2, H / 2) if pp is None else (float(v) for v in torch.as_tensor(pp).reshape(-1).tolist())
+    if out is None:
+        focal = torch.full((B,), float("nan"), device=points.device, dtype=torch.float64)
+        c2w = torch.full((B, 4, 4), float("nan"), device=points.device, dtype=torch.float64)
+    else:
+        focal, c2w = out
+        _dev(focal, "out focal"); _dev(c2w, "out c2w")
+        if focal.dtype != torch.float64 or c2w.dtype != torch.float64 or tuple(focal.shape) != (B,) or tuple(c2w.shape) != (B, 4, 4) or \
+                not focal.is_contiguous() or not c2w.is_contiguous():
+            raise ValueError("pnp_ransac: out = (focal [B], c2w [B, 4, 4]), contiguous fp64")
+    status = torch.empty(B, device=points.device, dtype=torch.int32)
+    info = torch.empty((B, C, 4), device=points.device, dtype=torch.int32)
+    need = lib.geo4d_pnp_ransac_workspace(B, C, H, W, iterations, tables.max_points)
+    ws = torch.empty(need // 8, device=points.device, dtype=torch.float64)
+    _lib.check(lib.geo4d_pnp_ransac(points.data_ptr(), points.stride(0), conf.data_ptr(), conf.stride(0), float(thr), cand_focals.data_ptr(), px, py,
+                                    float(reproj), iterations, 6, tables.n.data_ptr(), tables.m.data_ptr(), tables.sub.data_ptr(),
+                                    tables.draws.data_ptr(), tables.max_points, B, C, H, W, focal.data_ptr(), c2w.data_ptr(), status.data_ptr(),
+                                    info.data_ptr(), ws.data_ptr(), need, _stream()), "geo4d_pnp_ransac")
+    return focal, c2w, status, info

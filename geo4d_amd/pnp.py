@@ -91,15 +91,50 @@ def reprojection_error(X, pix, K, R, t):
     return np.where(Xc[:, 2] > 0, err, np.inf)
 
 
-def solve_pnp_ransac(X, pix, K, iterations=100, reproj=5.0, seed=0, sample=6, max_points=4096, confidence=0.99):
+_TABLES = {}
+
+
+def sample_tables(n, iterations, seed=0, sample=6, max_points=4096):
+    """The index stream `solve_pnp_ransac` draws for `n` points, as tables: (sub, draws). `sub` is the sorted sub-sample of range(n) the
+    consensus is scored on (arange(n) when n <= max_points), `draws` [iterations, sample] the first `iterations` hypothesis samples
+    (indices into `sub`) from the same generator in the same order ([0, sample] when there are fewer than `sample` points: the solver
+    fails before it draws). They depend on the arguments alone, so they are cached (up to 1024 entries, then the cache starts over: a clip
+    has about one distinct masked-pixel count per slot, so the cache saves repeated initialisations of a clip, not its first); the arrays
+    are read-only. Drawing one costs 1 - 2 ms at n ~ 130 000 (the sorted 4096-of-n choice). The device backend
+    (ops.pnp_ransac) uploads them instead of reimplementing numpy's PCG64 sampler."""
+    key = (int(n), int(iterations), int(seed), int(sample), int(max_points))
+    if key not in _TABLES:
+        n, iterations, seed, sample, max_points = key
+        rng = np.random.Generator(np.random.PCG64(seed))
+        sub = np.arange(n) if n <= max_points else np.sort(rng.choice(n, max_points, replace=False))
+        if len(sub) >= sample:
+            draws = np.stack([rng.choice(len(sub), sample, replace=False) for _ in range(iterations)]).reshape(iterations, sample)
+        else:
+            draws = np.zeros((0, sample), np.int64)
+        sub.setflags(write=False)
+        draws.setflags(write=False)
+        if len(_TABLES) >= 1024:                     # an entry is about 37 KB at max_points 4096 and 100 iterations: at most ~40 MB
+            _TABLES.clear()
+        _TABLES[key] = (sub, draws)
+    return _TABLES[key]
+
+
+def solve_pnp_ransac(X, pix, K, iterations=100, reproj=5.0, seed=0, sample=6, max_points=4096, confidence=0.99, tables=None):
     """cv2.solvePnPRansac's contract on (object points [n, 3], image points [n, 2], K): returns (success, R world->camera, t, inlier
-    indices). Seeded; see the module docstring for what differs from OpenCV."""
+    indices). Seeded; see the module docstring for what differs from OpenCV. `tables`: (sub, draws) of `sample_tables` for this n, used
+    instead of drawing (the same indices, so the same result)."""
     X, pix, K = np.asarray(X, np.float64), np.asarray(pix, np.float64), np.asarray(K, np.float64)
     n = len(X)
     if n < sample:
         return False, None, None, np.zeros(0, np.int64)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    sub = np.arange(n) if n <= max_points else np.sort(rng.choice(n, max_points, replace=False))     # consensus is scored on a sub-sample
+    if tables is None:
+        rng = np.random.Generator(np.random.PCG64(seed))
+        sub = np.arange(n) if n <= max_points else np.sort(rng.choice(n, max_points, replace=False))     # consensus is scored on a sub-sample
+    else:
+        sub = np.asarray(tables[0])
+        if len(sub) != min(n, max_points) or np.shape(tables[1])[1:] != (sample,) or len(tables[1]) < iterations:
+            raise ValueError(f"solve_pnp_ransac: tables hold {len(sub)} sub-sampled indices and draws {np.shape(tables[1])}; {n} points with "
+                             f"max_points {max_points} need {min(n, max_points)} and at least [{iterations}, {sample}] (pnp.sample_tables)")
     Xs, ps = X[sub], pix[sub]
     Kinv = np.linalg.inv(K)
     bs = np.concatenate([ps, np.ones((len(ps), 1))], 1) @ Kinv.T
@@ -107,7 +142,7 @@ def solve_pnp_ransac(X, pix, K, iterations=100, reproj=5.0, seed=0, sample=6, ma
     it, needed = 0, iterations
     while it < min(iterations, needed):
         it += 1
-        idx = rng.choice(len(Xs), sample, replace=False)
+        idx = rng.choice(len(Xs), sample, replace=False) if tables is None else np.asarray(tables[1][it - 1])
         R, t = pnp_orthogonal_iteration(Xs[idx], bs[idx], iters=15)
         inl = reprojection_error(Xs, ps, K, R, t) < reproj
         cnt = int(inl.sum())

@@ -388,6 +388,27 @@ int geo4d_focal_shift(const float* points, long map_stride, const float* weight,
                       int H, int W, int h_lr, int w_lr, int iters, float* shift, float* focal, int* status, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Batched RANSAC-PnP, B images x C candidate focals (geo4d_amd/csrc/pnp.hip): geo4d_amd/pnp.py's fast_pnp / solve_pnp_ransac hypothesis
+ * for hypothesis, with the sampler's tables (pnp.sample_tables) drawn on the host. Everything but the scalars is on the device.
+ *   points fp32, image b at points + b * image_stride, dense [H*W][3] world points; conf fp32, image b at conf + b * conf_stride, dense
+ *   [H*W]: a pixel is masked in when conf > thr. Pixel coordinates are the raster grid (x = column, y = row). cand_focals fp64 [B][C],
+ *   1 <= C <= 64, B * C <= 65535; (ppx, ppy) the principal point; reproj the inlier threshold in pixels; iterations the RANSAC cap; sample must be 6.
+ *   n [B] int32: masked pixels of image b as the caller counted them (the tables depend on it; a different count fails the image);
+ *   m [B] int32: length of image b's sub-sample, 6 <= m <= min(n, max_points); sub [B][max_points] int32: sorted ranks into the masked
+ *   pixels in raster order; draws [B][iterations][6] int32 into sub. Indices are range-checked on the device.
+ * Outputs: focal [B] and c2w [B][4][4] fp64 (winning candidate: strictly most inliers over all n masked pixels, ties to the first;
+ *   camera-to-world) are WRITTEN ONLY for an image with status 0, so the caller's values survive a failure. status [B] int32 bits:
+ *   1 fewer than 4 masked pixels / fewer than `sample` points, 2 no consensus, 4 a candidate focal non-finite or not positive, 8 tables
+ *   do not fit the image. info [B][C][4] int32: RANSAC iterations run, index of the chosen hypothesis (-1: none), sub-sample inliers
+ *   after the refit, inliers over all n masked pixels.
+ * workspace: geo4d_pnp_ransac_workspace bytes (0 for arguments the solver rejects), 8-byte aligned. Six launches, no allocation, no
+ * synchronisation; fp64 with fixed-order reductions (deterministic). */
+size_t geo4d_pnp_ransac_workspace(int B, int C, int H, int W, int iterations, int max_points);
+int geo4d_pnp_ransac(const float* points, long image_stride, const float* conf, long conf_stride, float thr, const double* cand_focals,
+                     double ppx, double ppy, double reproj, int iterations, int sample, const int* n, const int* m, const int* sub,
+                     const int* draws, int max_points, int B, int C, int H, int W, double* focal, double* c2w, int* status, int* info,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 const char* geo4d_last_error(void);
 int geo4d_abi_version(void);
 /* sizeof of the parameter structs as the LIBRARY was compiled (which: 0 conv_gemm, 1 groupnorm, 2 attention, 3 align, 4 align_small; else 0):
