@@ -52,6 +52,23 @@ class GroupNorm(C.Structure):
     ]
 
 
+class GroupNormSrc(C.Structure):
+    _fields_ = [("colsum", C.c_void_p), ("rows", C.c_int), ("c0", C.c_int), ("channels", C.c_int)]
+
+
+class GroupNorm2(C.Structure):      # geo4d_groupnorm2_t: the GroupNorm descriptor + up to two sources of column sums + the launch-sequence choice
+    _fields_ = [("base", GroupNorm), ("src", GroupNormSrc * 2), ("nsrc", C.c_int), ("path", C.c_int), ("fuse_fraction", C.c_float),
+                ("min_workgroups", C.c_int)]
+
+
+class GroupNormPlan(C.Structure):
+    _fields_ = [("path", C.c_int), ("launches", C.c_int), ("rows_per_wg", C.c_int), ("nchunk", C.c_int), ("channel_slices", C.c_int),
+                ("stat_slices", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
+GN_PATH_AUTO, GN_PATH_PARTIAL, GN_PATH_COLS, GN_PATH_FUSED, GN_PATH_SLICED = 0, 1, 2, 3, 4
+
+
 class Attention(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("o", C.c_void_p),
@@ -99,6 +116,8 @@ SIGNATURES = {
     "geo4d_conv_gemm_colsum_rows": (C.c_int, [C.POINTER(ConvGemm)]),
     "geo4d_groupnorm_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "geo4d_groupnorm": (C.c_int, [C.POINTER(GroupNorm), C.c_void_p]),
+    "geo4d_groupnorm_plan": (C.c_int, [C.POINTER(GroupNorm2), C.POINTER(GroupNormPlan)]),
+    "geo4d_groupnorm2": (C.c_int, [C.POINTER(GroupNorm2), C.c_void_p]),
     "geo4d_layernorm": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]),
     "geo4d_layernorm_split": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_float, C.c_void_p,

@@ -9,6 +9,16 @@
 // Statistics are always fp32 (partials merged with Chan's formula in fp64), activations are read and written
 // as 16-byte chunks (8 x bf16/f16 or 4 x f32 per lane) — cdna_hip_programming.md G13.
 // All reductions are order-deterministic (no atomics): the same input gives bit-identical output.
+// Launch sequences of a GroupNorm (gn_plan decides; geo4d_groupnorm_plan is the query):
+//   PARTIAL  gn_partial + gn_finalize + gn_apply      no producer sums: a statistics pass over x
+//   FUSED    gn_apply_sums                             producer sums small beside the rows a workgroup normalises: every workgroup adds
+//                                                      the sums of its own groups in its prologue (fp64, fixed order) - one launch, no
+//                                                      statistics in memory. Fewer, taller workgroups (R raised) keep the sums small per
+//                                                      workgroup, channel slices of whole groups give the launch its workgroups back.
+//   SLICED   gn_slice_sums + gn_apply_sums             the other GroupNorms with sums (across-time statistics of the large levels): ns
+//                                                      workgroups per (stat, group) write one fp64 partial each, the apply prologue adds them.
+//   COLS     gn_finalize_cols + gn_apply               the two-launch sequence before those (A/B: GEO4D_GN_ONE_LAUNCH=0)
+// The sums may come from two producers (the halves of a channel concatenation). Nothing waits on another workgroup in any of them.
 #include <type_traits>
 #include "common.h"
 #include "geo4d_hip.h"
@@ -193,10 +203,11 @@ __global__ __launch_bounds__(256) void gn_finalize_cols_kernel(const float* __re
 template <typename T, int SPLIT>      // SPLIT: 0 plain rows, 1 pre-split bf16 hi | lo (bf16x3 consumers), 2 plain f16 rows from f32 input (f16x2 consumers; ldy in f16 elements)
 __device__ __forceinline__ void gn_apply_body(const T* __restrict__ x, long ldx, T* __restrict__ y, long ldy,
                                               int HW, int C, int G, int R, const float* st, const float* __restrict__ gamma,
-                                              const float* __restrict__ beta, int act, int chunk, int f, unsigned long long* sat) {
+                                              const float* __restrict__ beta, int act, int chunk, int f, unsigned long long* sat,
+                                              int cbeg, int cend) {      // [cbeg, cend): the 16-byte chunks of a row this workgroup handles (all of them, or a channel slice)
     constexpr int EPC = Elem<T>::EPC;
     const int tid = threadIdx.x;
-    const int CPR = C / EPC;
+    const int CPR = cend - cbeg;
     const int TC = CPR < 256 ? CPR : 256;
     const int TR = 256 / TC;
     const int tc = tid % TC, tr = tid / TC;
@@ -206,7 +217,7 @@ __device__ __forceinline__ void gn_apply_body(const T* __restrict__ x, long ldx,
     const int cpg = C / G;
     const T* xb = x + ((long)f * HW + row0) * ldx;
     T* yb = y + ((long)f * HW + row0) * ldy;
-    for (int cc = tc; cc < CPR; cc += TC) {
+    for (int cc = cbeg + tc; cc < cend; cc += TC) {
         float sc[EPC], sh[EPC];
 #pragma unroll
         for (int j = 0; j < EPC; ++j) {
@@ -250,7 +261,112 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                                                        const float* __restrict__ stats, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, int act, unsigned long long* sat) {
     const int f = blockIdx.y;
-    gn_apply_body<T, SPLIT>(x, ldx, y, ldy, HW, C, G, R, stats + (long)(f / fps) * G * 2, gamma, beta, act, blockIdx.x, f, sat);
+    gn_apply_body<T, SPLIT>(x, ldx, y, ldy, HW, C, G, R, stats + (long)(f / fps) * G * 2, gamma, beta, act, blockIdx.x, f, sat, 0, C / Elem<T>::EPC);
+}
+
+// ---- GroupNorm from producer sums without a statistics round trip -----------------------------------------------------------------
+// The sums of one statistic come from up to two producers (a channel concatenation: one GEMM launch per half, each with its own
+// rows per entry). A source is [nstat][nb][nc][2] floats and covers the channels [c0, c0 + nc) of x.
+struct GnSrc { const float* cs; int nb, c0, nc; };
+struct GnSums { GnSrc s[2]; int nsrc; };
+
+// lane l of a team of ts lanes adds its share of the (sum, sum of squares) pairs of channels [ca, cb) x blocks [b0, b1) of one source,
+// in fp64. Consecutive lanes take consecutive channels of one block (the layout's contiguous run), 4 independent 8-byte loads in flight.
+__device__ __forceinline__ void gn_sum_items(const GnSrc& S, int stat, int b0, int b1, int ca, int cb, int l, int ts, double& s, double& q) {
+    const int lo = max(ca, S.c0), hi = min(cb, S.c0 + S.nc);
+    const int nch = hi - lo;
+    if (nch <= 0 || b1 <= b0) return;
+    const int total = (b1 - b0) * nch;
+    const float* base = S.cs + (((long)stat * S.nb + b0) * S.nc + (lo - S.c0)) * 2;
+    for (int i = l; i < total; i += 4 * ts) {
+        f32x2 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int iu = i + u * ts;
+            v[u] = f32x2{0.f, 0.f};
+            if (iu < total) {
+                const int rb = iu / nch, c = iu - rb * nch;
+                v[u] = *(const f32x2*)(base + ((long)rb * S.nc + c) * 2);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { s += (double)v[u][0]; q += (double)v[u][1]; }
+    }
+}
+// (mean, rstd) from the two totals: the formula of gn_finalize_cols_kernel
+__device__ __forceinline__ void gn_mean_rstd(double s, double q, double n, float eps, float* st) {
+    const double mean = s / n;
+    double var = q / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    st[0] = (float)mean;
+    st[1] = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// SLICED pass 1: `ns` workgroups per (stat, group), each adds one slice of every source's blocks and writes ONE fp64 (sum, sum of
+// squares); the apply launch adds the ns partials in slice order. An across-time GroupNorm at batch 1 has 32 (stat, group) units:
+// gn_finalize_cols_kernel ran it on 32 of 256 CUs, each thread walking ~20 dependent strided loads.
+__global__ __launch_bounds__(256) void gn_slice_sums_kernel(GnSums S, int C, int G, int ns, double* __restrict__ part) {
+    __shared__ double red[4][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int unit = blockIdx.x / ns, k = blockIdx.x - unit * ns;
+    const int stat = unit / G, grp = unit - stat * G;
+    const int cpg = C / G;
+    double s = 0.0, q = 0.0;
+    for (int i = 0; i < S.nsrc; ++i) {
+        const int b0 = (int)((long)k * S.s[i].nb / ns), b1 = (int)((long)(k + 1) * S.s[i].nb / ns);
+        gn_sum_items(S.s[i], stat, b0, b1, grp * cpg, (grp + 1) * cpg, tid, 256, s, q);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        s += __shfl_xor(s, o);
+        q += __shfl_xor(q, o);
+    }
+    if (lane == 0) { red[wave][0] = s; red[wave][1] = q; }
+    __syncthreads();
+    if (tid == 0) {
+        part[(long)blockIdx.x * 2 + 0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];      // fixed order
+        part[(long)blockIdx.x * 2 + 1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+// apply with the statistics formed in the prologue. Workgroup (chunk, frame, channel slice); a slice is G / ncs whole groups.
+//   ns == 0 (FUSED): teams of lanes (8 per group when a workgroup has all 32 groups) reduce the groups of the slice in parallel from the
+//     producers' sums: every workgroup of a statistic runs the same code on the same sums and gets the same bits; nothing is published.
+//   ns > 0 (SLICED): lane g adds the ns fp64 partials of its group in slice order.
+template <typename T, int SPLIT>
+__global__ __launch_bounds__(256) void gn_apply_sums_kernel(const T* __restrict__ x, long ldx, T* __restrict__ y, long ldy,
+                                                            int HW, int C, int G, int fps, int R, int ncs, GnSums S, int ns,
+                                                            const double* __restrict__ part, float eps, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, int act, unsigned long long* sat) {
+    __shared__ float st[64];
+    const int tid = threadIdx.x;
+    const int f = blockIdx.y, stat = f / fps;
+    const int cpg = C / G, gps = G / ncs, g0 = blockIdx.z * gps;
+    const double n = (double)fps * HW * cpg;
+    if (ns == 0) {
+        int ts = 64;
+        while (ts * gps > 256) ts >>= 1;                  // power of two: a team never straddles a wave
+        const int team = tid / ts, l = tid - team * ts;
+        double s = 0.0, q = 0.0;
+        if (team < gps) {
+            const int g = g0 + team;
+            for (int i = 0; i < S.nsrc; ++i) gn_sum_items(S.s[i], stat, 0, S.s[i].nb, g * cpg, (g + 1) * cpg, l, ts, s, q);
+        }
+        for (int o = 1; o < ts; o <<= 1) {                // fixed xor tree inside the team
+            s += __shfl_xor(s, o);
+            q += __shfl_xor(q, o);
+        }
+        if (team < gps && l == 0) gn_mean_rstd(s, q, n, eps, st + (g0 + team) * 2);
+    } else if (tid < gps) {
+        const int g = g0 + tid;
+        const double* pp = part + ((long)stat * G + g) * ns * 2;
+        double s = 0.0, q = 0.0;
+        for (int k = 0; k < ns; ++k) { s += pp[k * 2]; q += pp[k * 2 + 1]; }
+        gn_mean_rstd(s, q, n, eps, st + g * 2);
+    }
+    __syncthreads();
+    constexpr int EPC = Elem<T>::EPC;
+    gn_apply_body<T, SPLIT>(x, ldx, y, ldy, HW, C, G, R, st, gamma, beta, act, blockIdx.x, f, sat, g0 * cpg / EPC, (g0 + gps) * cpg / EPC);
 }
 
 // ---- LayerNorm: one wave per row, row held in registers ------------------------------------
@@ -387,18 +503,154 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     for (int c = tid; c < cols; c += 256) Elem<T>::st(yr + c, __expf(xr[c] * scale - m) * inv);
 }
 
+// ---- which launches a GroupNorm runs: one pure host function, shared by geo4d_groupnorm_plan (the query) and the launch -----------
+// FUSED only pays where the sums a launch re-reads are small (profiles/groupnorm_one_launch.md, tools/norm_bench.py --sweep): every workgroup of a
+// statistic reads that statistic's sums, so the launch reads (workgroups per statistic) x (all sums) from L2 - measured ~0.1 us per MB on top of
+// the apply - and what it saves is one ~2.5 us launch. The plan takes the tallest workgroups that still leave the launch GN_MIN_WORKGROUPS
+// (sums <= 1/8 of a workgroup's payload, else <= 1/4) and fuses while the re-read sums stay below GN_FUSE_MAX_TRAFFIC.
+constexpr float GN_FUSE_FRACTIONS[2] = {0.125f, 0.25f};
+constexpr int GN_MIN_WORKGROUPS = 1024;      // (or as many as the default chunks give: the small levels have 160 .. 640)
+constexpr size_t GN_FUSE_MAX_TRAFFIC = (size_t)12 << 20;
+constexpr int GN_MAX_STAT_SLICES = 64;
+
+inline int gn_stat_slices(int nstat, int G) {
+    int ns = (256 + nstat * G - 1) / (nstat * G);
+    return ns < 1 ? 1 : ns > GN_MAX_STAT_SLICES ? GN_MAX_STAT_SLICES : ns;
+}
+inline size_t gn_workspace_partial(int F, int HW, int G, int fps) {
+    const int R = gn_rows_per_chunk(HW, F);
+    const int nchunk = (HW + R - 1) / R;
+    return ((size_t)F * nchunk * G * 3 + (size_t)(F / fps) * G * 2) * sizeof(float);
+}
+
+int gn_plan(const geo4d_groupnorm2_t& q, geo4d_groupnorm_plan_t& o) {
+    const geo4d_groupnorm_t& p = q.base;
+    o = geo4d_groupnorm_plan_t{};
+    if (p.dtype < 0 || p.dtype > 2) { geo4d_set_error("groupnorm: bad dtype"); return GEO4D_EINVAL; }
+    const int esz = p.dtype == GEO4D_F32 ? 4 : 2, epc = 16 / esz;
+    if (p.F <= 0 || p.HW <= 0 || p.C <= 0 || p.groups <= 0 || p.groups > 32 || p.C % p.groups || p.C % epc) {
+        geo4d_set_error("groupnorm: need C % groups == 0, C % (16 B) == 0, groups <= 32");
+        return GEO4D_EINVAL;
+    }
+    if (p.frames_per_stat <= 0 || p.F % p.frames_per_stat) { geo4d_set_error("groupnorm: F % frames_per_stat"); return GEO4D_EINVAL; }
+    const int yesz = p.split_out == 2 ? 2 : esz;       // (split_out 2: f16 rows from f32 input)
+    if ((p.ldx * esz) % 16 || (p.ldy * yesz) % 16 || ((uintptr_t)p.x % 16) || ((uintptr_t)p.y % 16)) { geo4d_set_error("groupnorm: alignment"); return GEO4D_EINVAL; }
+    if (p.F > 65535) { geo4d_set_error("groupnorm: too many frames"); return GEO4D_EINVAL; }
+    if (p.split_out && (p.dtype != GEO4D_F32 || (p.C % 8) || p.split_out > 2 || p.split_out < 0)) { geo4d_set_error("groupnorm: split_out (1 = bf16 hi | lo, 2 = plain f16 rows) is a producer format for f32 input, C % 8 == 0"); return GEO4D_EINVAL; }
+    if (q.nsrc < 0 || q.nsrc > 2 || q.path < 0 || q.path > GEO4D_GN_PATH_SLICED || !(q.fuse_fraction >= 0.f) || q.min_workgroups < 0) {
+        geo4d_set_error("groupnorm: bad nsrc / path / fuse_fraction / min_workgroups");
+        return GEO4D_EINVAL;
+    }
+    const long stat_rows = (long)p.frames_per_stat * p.HW;
+    int cnext = 0;
+    size_t sum_bytes = 0;       // of one statistic
+    int max_nb = 1;
+    for (int i = 0; i < q.nsrc; ++i) {
+        const geo4d_groupnorm_src_t& r = q.src[i];
+        if (!r.colsum || ((uintptr_t)r.colsum % 8) || r.rows <= 0 || (stat_rows % r.rows)) {      // blocks must not straddle two statistics
+            geo4d_set_error("groupnorm: colsum needs (frames_per_stat x HW) % colsum_rows == 0");
+            return GEO4D_EINVAL;
+        }
+        if (r.c0 != cnext || r.channels <= 0) { geo4d_set_error("groupnorm: the sum sources must tile the channels in order"); return GEO4D_EINVAL; }
+        cnext += r.channels;
+        const int nb = (int)(stat_rows / r.rows);
+        sum_bytes += (size_t)nb * r.channels * 8;
+        if (nb > max_nb) max_nb = nb;
+    }
+    if (q.nsrc && cnext != p.C) { geo4d_set_error("groupnorm: the sum sources must tile the channels in order"); return GEO4D_EINVAL; }
+    if (!q.nsrc && (q.path == GEO4D_GN_PATH_FUSED || q.path == GEO4D_GN_PATH_SLICED)) { geo4d_set_error("groupnorm: this path needs column sums"); return GEO4D_EINVAL; }
+
+    const int G = p.groups, cpg = p.C / G, nstat = p.F / p.frames_per_stat;
+    const int R0 = gn_rows_per_chunk(p.HW, p.F), nchunk0 = (p.HW + R0 - 1) / R0;
+    o.rows_per_wg = R0; o.nchunk = nchunk0; o.channel_slices = 1; o.stat_slices = 0;
+    if (!q.nsrc || q.path == GEO4D_GN_PATH_PARTIAL || (q.path == GEO4D_GN_PATH_COLS && q.nsrc != 1)) {
+        o.path = GEO4D_GN_PATH_PARTIAL; o.launches = 3;
+        o.workspace_bytes = gn_workspace_partial(p.F, p.HW, G, p.frames_per_stat);
+        return GEO4D_OK;
+    }
+    if (q.path == GEO4D_GN_PATH_COLS) {
+        o.path = GEO4D_GN_PATH_COLS; o.launches = 2;
+        o.workspace_bytes = gn_workspace_partial(p.F, p.HW, G, p.frames_per_stat);     // (stats keep their place behind the partials)
+        return GEO4D_OK;
+    }
+    if (q.path != GEO4D_GN_PATH_SLICED) {
+        // FUSED: a workgroup reads all sums of its groups, so they have to be small beside the rows it normalises. (sum bytes : payload bytes)
+        // of a workgroup = sum_bytes / (R x C x (in + out bytes)) whatever its channel slice: raise R until it is below the fraction, then
+        // cut the channels into slices of whole groups until the launch has its workgroups back.
+        const long minwg = q.min_workgroups > 0 ? q.min_workgroups : GN_MIN_WORKGROUPS;
+        const long floor_wg = (long)p.F * nchunk0 < minwg ? (long)p.F * nchunk0 : minwg;
+        const double row_bytes = (double)p.C * (esz + yesz);
+        const long HWr = ((long)p.HW + 3) / 4 * 4;
+        const int nfrac = q.fuse_fraction > 0.f ? 1 : 2;
+        for (int fi = 0; fi < nfrac; ++fi) {
+            const float frac = q.fuse_fraction > 0.f ? q.fuse_fraction : GN_FUSE_FRACTIONS[fi];
+            long R = (long)((double)sum_bytes / ((double)frac * row_bytes) + 0.999999);
+            if (R < R0) R = R0;
+            R = (R + 3) / 4 * 4;
+            if (R > HWr && R != R0) continue;
+            const int nchunk = (int)((p.HW + R - 1) / R);
+            // (a forced path or a caller's own fraction - tools/norm_bench.py - is not held to the traffic bound)
+            if (!q.path && !(q.fuse_fraction > 0.f) && (size_t)p.F * nchunk * sum_bytes > GN_FUSE_MAX_TRAFFIC) continue;
+            for (int ncs = 1; ncs <= G; ++ncs) {
+                if (G % ncs) continue;
+                const int cslice = G / ncs * cpg;
+                if (cslice % epc || (ncs > 1 && cslice * esz < 256)) continue;      // whole 16-byte chunks, rows of >= 256 contiguous bytes
+                if ((long)p.F * nchunk * ncs < floor_wg) continue;
+                o.path = GEO4D_GN_PATH_FUSED; o.launches = 1;
+                o.rows_per_wg = (int)R; o.nchunk = nchunk; o.channel_slices = ncs;
+                o.workspace_bytes = 0;
+                return GEO4D_OK;
+            }
+        }
+        if (q.path == GEO4D_GN_PATH_FUSED) {      // forced: the default chunks, every workgroup reads all sums
+            o.path = GEO4D_GN_PATH_FUSED; o.launches = 1; o.workspace_bytes = 0;
+            return GEO4D_OK;
+        }
+    }
+    if (!q.path && q.nsrc == 1 && gn_stat_slices(nstat, G) == 1) {
+        // one source and already a workgroup per CU in gn_finalize_cols (per-frame statistics): the sliced form is the same work plus an fp64
+        // round trip (measured 0.3 - 0.9 us slower); the two-launch sequence stays
+        o.path = GEO4D_GN_PATH_COLS; o.launches = 2;
+        o.workspace_bytes = gn_workspace_partial(p.F, p.HW, G, p.frames_per_stat);
+        return GEO4D_OK;
+    }
+    o.path = GEO4D_GN_PATH_SLICED; o.launches = 2;
+    o.stat_slices = gn_stat_slices(nstat, G);
+    if (o.stat_slices > max_nb) o.stat_slices = max_nb;
+    o.workspace_bytes = (size_t)nstat * G * o.stat_slices * 2 * sizeof(double);
+    if ((uintptr_t)p.workspace % 8) { geo4d_set_error("groupnorm: workspace alignment"); return GEO4D_EINVAL; }
+    return GEO4D_OK;
+}
+
 template <typename T, int SPLIT>
-int groupnorm_typed(const geo4d_groupnorm_t& p, hipStream_t s) {
+int groupnorm_typed(const geo4d_groupnorm2_t& q, const geo4d_groupnorm_plan_t& pl, hipStream_t s) {
     constexpr int EPC = Elem<T>::EPC;
-    int R = gn_rows_per_chunk(p.HW, p.F);
-    int nchunk = (p.HW + R - 1) / R;
+    const geo4d_groupnorm_t& p = q.base;
+    const int nstat = p.F / p.frames_per_stat;
+    unsigned long long* sat = SPLIT == 2 ? p.sat_count : nullptr;
+    if (pl.path == GEO4D_GN_PATH_FUSED || pl.path == GEO4D_GN_PATH_SLICED) {
+        GnSums S{};
+        S.nsrc = q.nsrc;
+        for (int i = 0; i < q.nsrc; ++i)
+            S.s[i] = GnSrc{q.src[i].colsum, (int)(((long)p.frames_per_stat * p.HW) / q.src[i].rows), q.src[i].c0, q.src[i].channels};
+        double* part = (double*)p.workspace;
+        if (pl.path == GEO4D_GN_PATH_SLICED) {
+            hipLaunchKernelGGL(gn_slice_sums_kernel, dim3(nstat * p.groups * pl.stat_slices), dim3(256), 0, s, S, p.C, p.groups, pl.stat_slices, part);
+            GEO4D_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL((gn_apply_sums_kernel<T, SPLIT>), dim3(pl.nchunk, p.F, pl.channel_slices), dim3(256), 0, s, (const T*)p.x, (long)p.ldx,
+                           (T*)p.y, (long)p.ldy, p.HW, p.C, p.groups, p.frames_per_stat, pl.rows_per_wg, pl.channel_slices, S, pl.stat_slices,
+                           part, p.eps, p.gamma, p.beta, p.act, sat);
+        GEO4D_CHECK_LAUNCH();
+        return GEO4D_OK;
+    }
+    const int R = pl.rows_per_wg, nchunk = pl.nchunk;
     float* part = (float*)p.workspace;
     const size_t smem = (size_t)256 * 2 * EPC * 4 + (size_t)2 * p.C * 4;
-    const int nstat = p.F / p.frames_per_stat;
     float* stats = part + (size_t)p.F * nchunk * p.groups * 3;
-    if (p.colsum) {     // statistics already summed per block of `colsum_rows` rows by the producing GEMM's epilogue: no pass over x
-        const int crows = p.colsum_rows > 0 ? p.colsum_rows : 32;
-        hipLaunchKernelGGL(gn_finalize_cols_kernel, dim3(nstat * p.groups), dim3(256), 0, s, p.colsum, (p.frames_per_stat * p.HW) / crows,
+    if (pl.path == GEO4D_GN_PATH_COLS) {     // statistics already summed per block of `rows` rows by the producing GEMM's epilogue: no pass over x
+        const int crows = q.src[0].rows;
+        hipLaunchKernelGGL(gn_finalize_cols_kernel, dim3(nstat * p.groups), dim3(256), 0, s, q.src[0].colsum, (p.frames_per_stat * p.HW) / crows,
                            p.C, p.groups, p.eps, stats, nstat, crows);
         GEO4D_CHECK_LAUNCH();
     } else {
@@ -410,7 +662,7 @@ int groupnorm_typed(const geo4d_groupnorm_t& p, hipStream_t s) {
         GEO4D_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL((gn_apply_kernel<T, SPLIT>), dim3(nchunk, p.F), dim3(256), 0, s, (const T*)p.x, (long)p.ldx, (T*)p.y, (long)p.ldy, p.HW,
-                       p.C, p.groups, p.frames_per_stat, R, stats, p.gamma, p.beta, p.act, SPLIT == 2 ? p.sat_count : nullptr);
+                       p.C, p.groups, p.frames_per_stat, R, stats, p.gamma, p.beta, p.act, sat);
     GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
 }
@@ -447,39 +699,50 @@ int layernorm_typed(const void* x, long ldx, void* y, long ldy, int M, int C, fl
 }  // namespace
 
 extern "C" size_t geo4d_groupnorm_workspace(int F, int HW, int groups, int frames_per_stat) {
-    const int R = gn_rows_per_chunk(HW, F);
-    const int nchunk = (HW + R - 1) / R;
-    return ((size_t)F * nchunk * groups * 3 + (size_t)(F / frames_per_stat) * groups * 2) * sizeof(float);
+    // the three-pass path's partials + statistics, or the SLICED path's fp64 partials (the paths share the buffer: a launch runs one of them)
+    const size_t a = gn_workspace_partial(F, HW, groups, frames_per_stat);
+    const size_t b = (size_t)(F / frames_per_stat) * groups * gn_stat_slices(F / frames_per_stat, groups) * 2 * sizeof(double);
+    return a > b ? a : b;
+}
+
+extern "C" int geo4d_groupnorm_plan(const geo4d_groupnorm2_t* q, geo4d_groupnorm_plan_t* plan) {
+    if (!q || !plan) return GEO4D_EINVAL;
+    return gn_plan(*q, *plan);
+}
+
+extern "C" int geo4d_groupnorm2(const geo4d_groupnorm2_t* qq, void* stream) {
+    if (!qq) return GEO4D_EINVAL;
+    const geo4d_groupnorm2_t& q = *qq;
+    const geo4d_groupnorm_t& p = q.base;
+    geo4d_groupnorm_plan_t pl;
+    const int rc = gn_plan(q, pl);
+    if (rc != GEO4D_OK) return rc;
+    if (p.workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !p.workspace)) { geo4d_set_error("groupnorm: workspace too small"); return GEO4D_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    switch (p.dtype) {
+        case GEO4D_F32: return p.split_out == 2 ? groupnorm_typed<float, 2>(q, pl, s) : p.split_out ? groupnorm_typed<float, 1>(q, pl, s) : groupnorm_typed<float, 0>(q, pl, s);
+        case GEO4D_BF16: return groupnorm_typed<bf16_t, 0>(q, pl, s);
+        default: return groupnorm_typed<f16_t, 0>(q, pl, s);
+    }
 }
 
 extern "C" int geo4d_groupnorm(const geo4d_groupnorm_t* pp, void* stream) {
     if (!pp) return GEO4D_EINVAL;
-    const geo4d_groupnorm_t& p = *pp;
-    const int esz = p.dtype == GEO4D_F32 ? 4 : 2, epc = 16 / esz;
-    if (p.dtype < 0 || p.dtype > 2) { geo4d_set_error("groupnorm: bad dtype"); return GEO4D_EINVAL; }
-    if (p.F <= 0 || p.HW <= 0 || p.C <= 0 || p.groups <= 0 || p.groups > 32 || p.C % p.groups || p.C % epc) {
-        geo4d_set_error("groupnorm: need C % groups == 0, C % (16 B) == 0, groups <= 32");
+    geo4d_groupnorm2_t q{};
+    q.base = *pp;
+    if (pp->colsum) {
+        q.nsrc = 1;
+        q.src[0] = geo4d_groupnorm_src_t{pp->colsum, pp->colsum_rows > 0 ? pp->colsum_rows : 32, 0, pp->C};
+    }
+    if (pp->workspace_bytes < geo4d_groupnorm_workspace(pp->F > 0 ? pp->F : 1, pp->HW > 0 ? pp->HW : 1, pp->groups > 0 ? pp->groups : 1,
+                                                        pp->frames_per_stat > 0 ? pp->frames_per_stat : 1)) {
+        geo4d_groupnorm_plan_t pl;        // (argument errors are reported before the workspace's size)
+        const int rc = gn_plan(q, pl);
+        if (rc != GEO4D_OK) return rc;
+        geo4d_set_error("groupnorm: workspace too small");
         return GEO4D_EINVAL;
     }
-    if (p.frames_per_stat <= 0 || p.F % p.frames_per_stat) { geo4d_set_error("groupnorm: F % frames_per_stat"); return GEO4D_EINVAL; }
-    const int yesz = p.split_out == 2 ? 2 : esz;       // (split_out 2: f16 rows from f32 input)
-    if ((p.ldx * esz) % 16 || (p.ldy * yesz) % 16 || ((uintptr_t)p.x % 16) || ((uintptr_t)p.y % 16)) { geo4d_set_error("groupnorm: alignment"); return GEO4D_EINVAL; }
-    if (p.workspace_bytes < geo4d_groupnorm_workspace(p.F, p.HW, p.groups, p.frames_per_stat)) { geo4d_set_error("groupnorm: workspace too small"); return GEO4D_EINVAL; }
-    if (p.F > 65535) { geo4d_set_error("groupnorm: too many frames"); return GEO4D_EINVAL; }
-    {
-        const int crows = p.colsum_rows > 0 ? p.colsum_rows : 32;      // blocks must not straddle two statistics
-        if (p.colsum && ((((long)p.frames_per_stat * p.HW) % crows) || ((uintptr_t)p.colsum % 8))) {
-            geo4d_set_error("groupnorm: colsum needs (frames_per_stat x HW) % colsum_rows == 0");
-            return GEO4D_EINVAL;
-        }
-    }
-    if (p.split_out && (p.dtype != GEO4D_F32 || (p.C % 8) || p.split_out > 2 || p.split_out < 0)) { geo4d_set_error("groupnorm: split_out (1 = bf16 hi | lo, 2 = plain f16 rows) is a producer format for f32 input, C % 8 == 0"); return GEO4D_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    switch (p.dtype) {
-        case GEO4D_F32: return p.split_out == 2 ? groupnorm_typed<float, 2>(p, s) : p.split_out ? groupnorm_typed<float, 1>(p, s) : groupnorm_typed<float, 0>(p, s);
-        case GEO4D_BF16: return groupnorm_typed<bf16_t, 0>(p, s);
-        default: return groupnorm_typed<f16_t, 0>(p, s);
-    }
+    return geo4d_groupnorm2(&q, stream);
 }
 
 extern "C" int geo4d_layernorm(const void* x, long ldx, void* y, long ldy, int M, int C, float eps, const float* gamma,

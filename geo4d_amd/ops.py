@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, ConvGemm, GroupNorm
+from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, ConvGemm, GroupNorm2, GroupNormPlan
 from .precision import resolve as _resolve_precision
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -201,6 +201,8 @@ def _env_level(name, default):
 
 
 GN_FUSED_STATS = _env_level("GEO4D_GN_FUSED", 1)
+GN_ONE_LAUNCH = _env_level("GEO4D_GN_ONE_LAUNCH", 1)     # 0: a GroupNorm with producer sums runs gn_finalize_cols + gn_apply and a concatenated input its own statistics pass (the launch sequence before the fused / sliced forms); 3 / 4: force _lib.GN_PATH_FUSED / GN_PATH_SLICED (tests, tools/norm_bench.py)
+GN_TUNE = (0.0, 0)     # tools/norm_bench.py: (fuse_fraction, min_workgroups) overrides of the library's defaults; 0 = default
 SPLITK_COLSUM = _env_level("GEO4D_SPLITK_COLSUM", 1)     # 0: split-K launches leave the GroupNorm statistics to the GroupNorm (the state before round 6)
 TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)     # tools/tune_gemm.py: measure a pre-split launch under its OWN key instead of borrowing the raw-activation entry of the same shape
 TUNE_LOG = []          # (key, chosen (tile, split), ms per launch, finalists) of every shape autotuned in this process (tools/tune_gemm.py prints it)
@@ -502,9 +504,71 @@ def batched_gemm(a, b, out, *, batch, M, N, K, a_bs, b_bs, o_bs, bias=None, bias
 _gn_ws = {}
 
 
-def groupnorm(x, gamma, beta, *, F, HW, eps, groups=32, frames_per_stat=1, silu=False, out=None, split_out=False):
+def _gn_sums(t, stat_rows):
+    """-> (colsum tensor, rows per entry) a GEMM launch left on this very tensor object, or None: absent, stale (the tensor was modified in
+    place or re-viewed after the GEMM wrote it) or with blocks that straddle two statistics."""
+    cs = getattr(t, "_gn_colsum", None)
+    if cs is None or getattr(t, "_gn_colsum_tag", None) != (t.data_ptr(), t._version):
+        return None
+    rows = getattr(t, "_gn_colsum_rows", 32)
+    if stat_rows % rows or tuple(cs.shape) != (t.shape[0] // rows, t.shape[1], 2):
+        return None
+    return cs, rows
+
+
+def concat_parts(buf, left, right):
+    """Record on a channel-concatenation buffer the two column views its producers write (FUSED_CONCAT): the GroupNorm that reads `buf`
+    takes its statistics from the sums the two producing GEMM launches leave on those view objects."""
+    buf._gn_parts = (left, right)
+
+
+def _gn_sources(x, stat_rows):
+    one = _gn_sums(x, stat_rows)
+    if one is not None:
+        return [(one[0], one[1], 0, x.shape[1])]
+    parts = getattr(x, "_gn_parts", None)
+    if not parts or not GN_ONE_LAUNCH:
+        return []
+    src, c0 = [], 0
+    for v in parts:     # the views must still be the columns of x, in order, and carry fresh sums
+        if v.dim() != 2 or v.shape[0] != x.shape[0] or v.stride() != x.stride() or v.data_ptr() != x.data_ptr() + c0 * x.element_size():
+            return []
+        sums = _gn_sums(v, stat_rows)
+        if sums is None:
+            return []
+        src.append((sums[0], sums[1], c0, v.shape[1]))
+        c0 += v.shape[1]
+    return src if c0 == x.shape[1] else []
+
+
+def _gn_descriptor(x, out, gamma, beta, *, F, HW, eps, groups, frames_per_stat, silu, split_out, sources, path):
+    q = GroupNorm2()
+    p = q.base
+    p.x, p.y, p.gamma, p.beta = x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+    p.ldx, p.ldy = _ld(x), (_ld(out) // 2 if split_out == 1 else _ld(out))
+    p.split_out = int(split_out)
+    p.sat_count = _ptr(SAT_COUNTER) if split_out == 2 else 0
+    p.F, p.HW, p.C, p.groups, p.frames_per_stat = F, HW, x.shape[1], groups, frames_per_stat
+    p.act, p.dtype, p.eps = int(silu), dt_code(x.dtype), eps
+    q.nsrc = len(sources)
+    for i, (cs, rows, c0, nc) in enumerate(sources):
+        q.src[i].colsum, q.src[i].rows, q.src[i].c0, q.src[i].channels = cs.data_ptr(), rows, c0, nc
+    q.path = path
+    q.fuse_fraction, q.min_workgroups = GN_TUNE
+    return q
+
+
+def groupnorm_plan(q):
+    """What geo4d_groupnorm2 would launch for this descriptor (_lib.GroupNormPlan); raises where the launch would refuse it."""
+    plan = GroupNormPlan()
+    _lib.check(_lib.load().geo4d_groupnorm_plan(C.byref(q), C.byref(plan)), "geo4d_groupnorm_plan")
+    return plan
+
+
+def groupnorm(x, gamma, beta, *, F, HW, eps, groups=32, frames_per_stat=1, silu=False, out=None, split_out=False, path=None):
     """`split_out` (f32 input of the bf16x3 mode): y is returned as a SplitAct, the pre-split A operand of the conv that follows -
-    True / "bf16": bf16 hi | lo (three-pass bf16x3 consumer); "f16": f16 hi | lo (two-pass f16 consumer, pack.split_f16 weights)."""
+    True / "bf16": bf16 hi | lo (three-pass bf16x3 consumer); "f16": f16 hi | lo (two-pass f16 consumer, pack.split_f16 weights).
+    `path` (tests, tools): one of _lib.GN_PATH_*; default: GN_ONE_LAUNCH decides (the library's plan, or the two-launch sequence)."""
     lib = _lib.load()
     _dev(x, "x")
     assert not isinstance(x, SplitAct), "GroupNorm reads plain activations"
@@ -518,23 +582,18 @@ def groupnorm(x, gamma, beta, *, F, HW, eps, groups=32, frames_per_stat=1, silu=
         assert x.dtype == torch.float32, "the GEMM-operand producer formats are written from f32 activations"
     if split_out == 1:
         _split_out_ok(out, F * HW)
-    need = lib.geo4d_groupnorm_workspace(F, HW, groups, frames_per_stat)
-    ws = torch.empty(need, device=x.device, dtype=torch.uint8)
-    p = GroupNorm()
-    p.x, p.y, p.gamma, p.beta = x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-    p.workspace, p.workspace_bytes = ws.data_ptr(), need
-    p.ldx, p.ldy = _ld(x), (_ld(out) // 2 if split_out == 1 else _ld(out))
-    p.split_out = int(split_out)
-    p.sat_count = _ptr(SAT_COUNTER) if split_out == 2 else 0
-    p.F, p.HW, p.C, p.groups, p.frames_per_stat = F, HW, Cc, groups, frames_per_stat
-    p.act, p.dtype, p.eps = int(silu), dt_code(x.dtype), eps
-    cs = getattr(x, "_gn_colsum", None)     # column sums left on this very tensor object by the GEMM that produced it
-    if cs is not None and getattr(x, "_gn_colsum_tag", None) != (x.data_ptr(), x._version):
-        cs = None                            # the tensor was modified in place (or re-viewed) after the GEMM wrote it: stale sums
-    rows = getattr(x, "_gn_colsum_rows", 32)
-    ok = cs is not None and (frames_per_stat * HW) % rows == 0 and tuple(cs.shape) == (F * HW // rows, Cc, 2)
-    p.colsum, p.colsum_rows = (cs.data_ptr(), rows) if ok else (0, 0)
-    _lib.check(lib.geo4d_groupnorm(C.byref(p), _stream()), "geo4d_groupnorm")
+    if path is None:
+        path = {0: _lib.GN_PATH_COLS, 3: _lib.GN_PATH_FUSED, 4: _lib.GN_PATH_SLICED}.get(int(GN_ONE_LAUNCH), _lib.GN_PATH_AUTO)
+    sources = _gn_sources(x, frames_per_stat * HW)
+    if not sources:
+        path = _lib.GN_PATH_PARTIAL
+    q = _gn_descriptor(x, out, gamma, beta, F=F, HW=HW, eps=eps, groups=groups, frames_per_stat=frames_per_stat, silu=silu,
+                       split_out=split_out, sources=sources, path=path)
+    need = groupnorm_plan(q).workspace_bytes          # the same host function the launch runs: they cannot disagree
+    if need:
+        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+        q.base.workspace, q.base.workspace_bytes = ws.data_ptr(), need
+    _lib.check(lib.geo4d_groupnorm2(C.byref(q), _stream()), "geo4d_groupnorm2")
     return out
 
 

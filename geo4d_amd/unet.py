@@ -596,6 +596,7 @@ class UNetModel(ParamTree):
         # previous output block's (or the middle block's) last launch into columns [0, Ch). Same kernels, same operands: same bits.
         n_in = len(inputs)
         cats = {}                                             # index of the consuming output block -> its concatenated input buffer
+        halves = {}                                           # (block index, left half?) -> the column view handed to that half's producer
 
         def half(j, left):
             """-> function(rows) returning the [rows, C] view of output block j's input that a producer fills."""
@@ -609,7 +610,11 @@ class UNetModel(ParamTree):
                     buf = cats[j] = torch.empty((rows, ccat), device=x.device, dtype=dt)
                 assert buf.shape[0] == rows, "latent height/width must be multiples of 8"
                 cs = skip_ch[n_in - 1 - j]
-                return buf[:, :ccat - cs] if left else buf[:, ccat - cs:]
+                v = buf[:, :ccat - cs] if left else buf[:, ccat - cs:]
+                halves[(j, left)] = v                        # the producer leaves its GroupNorm column sums on this view object
+                if (j, True) in halves and (j, False) in halves:
+                    ops.concat_parts(buf, halves[(j, True)], halves[(j, False)])      # block j's first GroupNorm reads them from both
+                return v
             return view
         skip_ch = [blk[-1].cout if blk[-1].kind != "temporal" and blk[-1].kind != "spatial" else blk[-1].cin for blk in inputs]
         o0 = half(n_in - 1, False)

@@ -129,6 +129,44 @@ typedef struct geo4d_groupnorm_t {
 size_t geo4d_groupnorm_workspace(int F, int HW, int groups, int frames_per_stat);
 int geo4d_groupnorm(const geo4d_groupnorm_t* p, void* stream);
 
+/* The same GroupNorm with up to TWO sources of column sums (a channel concatenation whose halves were written by two GEMM launches,
+ * each with its own rows per entry) and a choice of launch sequence. `base.colsum` / `base.colsum_rows` are ignored here: the sums
+ * come from `src`. geo4d_groupnorm(p) == geo4d_groupnorm2 with one source {p->colsum, p->colsum_rows, 0, C} (or none) and path 0. */
+typedef struct geo4d_groupnorm_src_t {
+    const float* colsum; /* [F*HW/rows][channels][2] (sum, sum of squares), as geo4d_conv_gemm_t.gn_colsum of the producing launch        */
+    int rows;            /* rows per entry; (frames_per_stat x HW) % rows == 0                                                            */
+    int c0, channels;    /* the columns [c0, c0 + channels) of x this source covers: the sources tile [0, C) in order                     */
+} geo4d_groupnorm_src_t;
+typedef struct geo4d_groupnorm2_t {
+    geo4d_groupnorm_t base;
+    geo4d_groupnorm_src_t src[2];
+    int nsrc;            /* 0 (statistics pass over x), 1 or 2                                                                            */
+    int path;            /* 0 = the library decides (geo4d_groupnorm_plan); GEO4D_GN_PATH_* forces one (A/B, tests, tools/norm_bench.py)  */
+    float fuse_fraction; /* 0 = default (1/8, else 1/4, while the launch re-reads <= 12 MiB of sums); else the largest (sum bytes :
+                            payload bytes) per workgroup at which path 0 still fuses, with no bound on the re-read sums (sweeps)          */
+    int min_workgroups;  /* 0 = default; else the fewest workgroups path 0 lets a fused launch have                                       */
+} geo4d_groupnorm2_t;
+enum {
+    GEO4D_GN_PATH_PARTIAL = 1,  /* gn_partial + gn_finalize + gn_apply: what runs without sums                                            */
+    GEO4D_GN_PATH_COLS = 2,     /* gn_finalize_cols + gn_apply (one full-width source only; else PARTIAL): the two-launch sequence; path 0
+                                   keeps it for per-frame statistics whose sums are too large to fuse                                     */
+    GEO4D_GN_PATH_FUSED = 3,    /* ONE launch: every workgroup of gn_apply reduces its statistic's sums in its prologue                  */
+    GEO4D_GN_PATH_SLICED = 4    /* gn_slice_sums (stat_slices workgroups per (statistic, group)) + gn_apply combining the partials       */
+};
+typedef struct geo4d_groupnorm_plan_t {
+    int path;            /* GEO4D_GN_PATH_* that a launch with these arguments runs                                                       */
+    int launches;
+    int rows_per_wg;     /* rows of one frame per workgroup of the apply launch, and chunks per frame                                     */
+    int nchunk;
+    int channel_slices;  /* FUSED: workgroups across the channels (each a whole number of groups), so that fewer, taller workgroups
+                            read fewer sums each while the launch keeps its workgroup count                                              */
+    int stat_slices;     /* SLICED: partial sums per (statistic, group)                                                                   */
+    size_t workspace_bytes; /* what the chosen path writes; <= geo4d_groupnorm_workspace(F, HW, groups, frames_per_stat)                  */
+} geo4d_groupnorm_plan_t;
+/* pure host function: validates `p` exactly as geo4d_groupnorm2 does (except the workspace size) and says what it would launch */
+int geo4d_groupnorm_plan(const geo4d_groupnorm2_t* p, geo4d_groupnorm_plan_t* plan);
+int geo4d_groupnorm2(const geo4d_groupnorm2_t* p, void* stream);
+
 /* LayerNorm over the last dim; replaces nn.LayerNorm (attention.py:225-227). */
 int geo4d_layernorm(const void* x, long ldx, void* y, long ldy, int M, int C, float eps, const float* gamma,
                     const float* beta, int dtype, void* stream);
