@@ -144,6 +144,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "geo4d_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
                                   C.c_void_p]),
+    "geo4d_philox_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                    C.c_void_p]),
+    "geo4d_ddim_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int,
+                                      C.c_float, C.c_void_p]),
     "geo4d_cfg_combine_workspace": (C.c_size_t, [C.c_int]),
     "geo4d_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_float,
                                     C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -4,6 +4,7 @@
 //   timestep_embedding sinusoidal embedding [cos | sin] (utils_diffusion.py:8-28)
 //   linear_small       time_embed / fps_embedding / ResBlock emb_layers (openaimodel3d.py:367-384, 166-172): M = batch rows
 //   ddim_step          v-prediction DDIM update with dynamic rescale (ddim.py:206-279; ddpm3d.py:278-290)
+//   philox_fill / ddim_step_rng   counter-based Gaussian noise (Philox4x32-10) on its own and inside the DDIM update (eta > 0)
 #include "common.h"
 #include "geo4d_hip.h"
 
@@ -119,20 +120,141 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const float* __restri
 }
 
 // coef row (6 floats): sqrt(ac_t), sqrt(1-ac_t), scale_prev/scale_t, sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma
+struct DdimCoef {
+    float sa, s1, rs, sp, dc, sg;
+};
+__device__ __forceinline__ DdimCoef ddim_coef(const float* __restrict__ coef, const int* __restrict__ step_index) {
+    const float* c = coef + (long)(*step_index) * 6;
+    return DdimCoef{c[0], c[1], c[2], c[3], c[4], c[5]};
+}
+
+// The DDIM update of ONE element, shared by ddim_step_kernel and ddim_step_rng_kernel. Every rounding is spelled out (no contraction
+// left to the compiler), so the kernels that inline it agree bit for bit whatever surrounds the call; the two fused multiply-adds are the
+// ones ddim_step_kernel has always executed.
+__device__ __forceinline__ float ddim_update(const DdimCoef& c, float xi, float vi, bool has_noise, float nz, float& x0) {
+#pragma clang fp contract(off)
+    const float e_t = __builtin_fmaf(c.s1, xi, c.sa * vi);   // predict_eps_from_z_and_v
+    x0 = (c.sa * xi - c.s1 * vi) * c.rs;                      // predict_start_from_z_and_v, dynamic rescale
+    float xp = c.sp * x0 + c.dc * e_t;
+    if (has_noise) xp = __builtin_fmaf(c.sg, nz, xp);
+    return xp;
+}
+
 __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, const float* __restrict__ v, const float* __restrict__ noise,
                                                         float* __restrict__ pred_x0, const float* __restrict__ coef,
                                                         const int* __restrict__ step_index, long n) {
-    const float* c = coef + (long)(*step_index) * 6;
-    const float sa = c[0], s1 = c[1], rs = c[2], sp = c[3], dc = c[4], sg = c[5];
+    const DdimCoef c = ddim_coef(coef, step_index);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float xi = x[i], vi = v[i];
-        const float e_t = sa * vi + s1 * xi;     // predict_eps_from_z_and_v
-        float x0 = sa * xi - s1 * vi;            // predict_start_from_z_and_v
-        x0 *= rs;                                // dynamic rescale
-        float xp = sp * x0 + dc * e_t;
-        if (noise) xp += sg * noise[i];
+        float x0;
+        const float xp = ddim_update(c, x[i], v[i], noise != nullptr, noise ? noise[i] : 0.f, x0);
         x[i] = xp;
         if (pred_x0) pred_x0[i] = x0;
+    }
+}
+
+// ---- counter-based Gaussian noise: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) -----------------
+// key = the sample's 64-bit seed (low word, high word), counter = (q, step, stream, draw) with q = element / 4: the noise of an element is a
+// pure function of (seed, step, stream, draw, element) - no generator state, nothing host-side, independent of grid, batch and launch order.
+// The four output words of one call serve elements 4q .. 4q+3: words (0, 1) and (2, 3) are two Box-Muller pairs (DESIGN.md section 15;
+// geo4d_amd/noise.py restates all of it in numpy).
+constexpr int NOISE_STREAM_XT = 0, NOISE_STREAM_STEP = 1;
+
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+        c = u32x4{(unsigned)(p1 >> 32) ^ c[1] ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c[3] ^ k1, (unsigned)p0};
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+__device__ __forceinline__ u32x4 noise_words(long seed, unsigned q, int step, int stream_id, int draw) {
+    const unsigned long long k = (unsigned long long)seed;
+    return philox4x32_10(u32x4{q, (unsigned)step, (unsigned)stream_id, (unsigned)draw}, (unsigned)k, (unsigned)(k >> 32));
+}
+
+// u1 = ((a >> 8) + 1) 2^-24 in (0, 1], u2 = (b >> 8) 2^-24 in [0, 1): both exact in fp32, so logf never sees 0; |z| <= sqrt(48 ln 2)
+__device__ __forceinline__ void box_muller(unsigned a, unsigned b, float scale, float& even, float& odd) {
+    const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f, u2 = (float)(b >> 8) * 0x1p-24f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float s, c;
+    sincospif(2.0f * u2, &s, &c);
+    even = rad * c * scale;
+    odd = rad * s * scale;
+}
+
+__device__ __forceinline__ f32x4 noise_normals4(long seed, unsigned q, int step, int stream_id, int draw, float scale) {
+    const u32x4 r = noise_words(seed, q, step, stream_id, draw);
+    float z0, z1, z2, z3;
+    box_muller(r[0], r[1], scale, z0, z1);
+    box_muller(r[2], r[3], scale, z2, z3);
+    return f32x4{z0, z1, z2, z3};
+}
+
+// the normal of ONE element (rows whose length is no multiple of 4): the same call, the pair of its lane, the lane
+__device__ __forceinline__ float noise_normal1(long seed, long i, int step, int stream_id, int draw, float scale) {
+    const u32x4 r = noise_words(seed, (unsigned)(i >> 2), step, stream_id, draw);
+    const int lane = (int)(i & 3);
+    float even, odd;
+    box_muller(lane < 2 ? r[0] : r[2], lane < 2 ? r[1] : r[3], scale, even, odd);
+    return (lane & 1) ? odd : even;
+}
+
+// out[b][i]: kind 0 = normal * scale (fp32), kind 1 = the raw word of the element. VEC: rows are whole 16-byte quads (n % 4 == 0, base aligned)
+template <bool VEC>
+__global__ __launch_bounds__(256) void philox_fill_kernel(void* __restrict__ out, int kind, const long* __restrict__ seeds, long total, long n,
+                                                          const int* __restrict__ step_index, int step_value, int stream_id, int draw, float scale) {
+    const int step = step_index ? *step_index : step_value;
+    if (VEC) {
+        const long nq = n >> 2;             // total counts quads
+        for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long)gridDim.x * 256) {
+            const long b = g / nq;
+            const unsigned q = (unsigned)(g - b * nq);
+            if (kind == 0) ((f32x4*)out)[g] = noise_normals4(seeds[b], q, step, stream_id, draw, scale);
+            else ((u32x4*)out)[g] = noise_words(seeds[b], q, step, stream_id, draw);
+        }
+    } else {
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+            const long b = e / n, i = e - b * n;
+            if (kind == 0) ((float*)out)[e] = noise_normal1(seeds[b], i, step, stream_id, draw, scale);
+            else ((unsigned*)out)[e] = noise_words(seeds[b], (unsigned)(i >> 2), step, stream_id, draw)[(int)(i & 3)];
+        }
+    }
+}
+
+// ddim_step_kernel with noise[i] = the stream-1 normal of (seeds[b], *step_index, i, draw) * noise_scale, made in registers
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddim_step_rng_kernel(float* __restrict__ x, const float* __restrict__ v, float* __restrict__ pred_x0,
+                                                            const float* __restrict__ coef, const int* __restrict__ step_index,
+                                                            const long* __restrict__ seeds, long total, long n, int draw, float noise_scale) {
+    const int step = *step_index;
+    const DdimCoef c = ddim_coef(coef, step_index);
+    if (VEC) {
+        const long nq = n >> 2;
+        for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long)gridDim.x * 256) {
+            const long b = g / nq;
+            const f32x4 z = noise_normals4(seeds[b], (unsigned)(g - b * nq), step, NOISE_STREAM_STEP, draw, noise_scale);
+            const f32x4 xi = ((const f32x4*)x)[g], vi = ((const f32x4*)v)[g];
+            f32x4 xp, x0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float p;
+                xp[k] = ddim_update(c, xi[k], vi[k], true, z[k], p);
+                x0[k] = p;
+            }
+            ((f32x4*)x)[g] = xp;
+            if (pred_x0) ((f32x4*)pred_x0)[g] = x0;
+        }
+    } else {
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+            const long b = e / n;
+            float x0;
+            const float xp = ddim_update(c, x[e], v[e], true, noise_normal1(seeds[b], e - b * n, step, NOISE_STREAM_STEP, draw, noise_scale), x0);
+            x[e] = xp;
+            if (pred_x0) pred_x0[e] = x0;
+        }
     }
 }
 
@@ -306,6 +428,56 @@ extern "C" int geo4d_ddim_step(float* x, const float* v, const float* noise, flo
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ddim_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, v, noise, pred_x0, coef,
                        step_index, n);
+    GEO4D_CHECK_LAUNCH();
+    return GEO4D_OK;
+}
+
+// rows of n elements are addressed as 16-byte quads when every row starts on one; one Philox call then serves one quad
+static bool noise_rows_are_quads(long n, const void* a, const void* b, const void* c) {
+    return n % 4 == 0 && !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15);
+}
+static unsigned noise_blocks(long work) {
+    const long blocks = (work + 255) / 256;
+    return (unsigned)(blocks > 4096 ? 4096 : blocks);
+}
+
+extern "C" int geo4d_philox_fill(void* out, int kind, const long* seeds, int B, long n_per_sample, const int* step_index, int step_value,
+                                 int stream_id, int draw, float scale, void* stream) {
+    if (!out || !seeds || B <= 0 || n_per_sample <= 0 || n_per_sample > (1L << 34) || kind < 0 || kind > 1 || ((uintptr_t)out & 3)) {
+        geo4d_set_error("philox_fill: null pointer, non-positive size, more than 2^34 elements per sample or unknown kind");
+        return GEO4D_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (noise_rows_are_quads(n_per_sample, out, nullptr, nullptr)) {
+        const long total = (long)B * (n_per_sample / 4);
+        hipLaunchKernelGGL(philox_fill_kernel<true>, dim3(noise_blocks(total)), dim3(256), 0, s, out, kind, seeds, total, n_per_sample, step_index,
+                           step_value, stream_id, draw, scale);
+    } else {
+        const long total = (long)B * n_per_sample;
+        hipLaunchKernelGGL(philox_fill_kernel<false>, dim3(noise_blocks(total)), dim3(256), 0, s, out, kind, seeds, total, n_per_sample, step_index,
+                           step_value, stream_id, draw, scale);
+    }
+    GEO4D_CHECK_LAUNCH();
+    return GEO4D_OK;
+}
+
+extern "C" int geo4d_ddim_step_rng(float* x, const float* v, float* pred_x0, const float* coef, const int* step_index, const long* seeds, int B,
+                                   long n_per_sample, int draw, float noise_scale, void* stream) {
+    if (!x || !v || !coef || !step_index || !seeds || B <= 0 || n_per_sample <= 0 || n_per_sample > (1L << 34) ||
+        (((uintptr_t)x | (uintptr_t)v | (uintptr_t)pred_x0) & 3)) {
+        geo4d_set_error("ddim_step_rng: null pointer, non-positive size or more than 2^34 elements per sample");
+        return GEO4D_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (noise_rows_are_quads(n_per_sample, x, v, pred_x0)) {
+        const long total = (long)B * (n_per_sample / 4);
+        hipLaunchKernelGGL(ddim_step_rng_kernel<true>, dim3(noise_blocks(total)), dim3(256), 0, s, x, v, pred_x0, coef, step_index, seeds, total,
+                           n_per_sample, draw, noise_scale);
+    } else {
+        const long total = (long)B * n_per_sample;
+        hipLaunchKernelGGL(ddim_step_rng_kernel<false>, dim3(noise_blocks(total)), dim3(256), 0, s, x, v, pred_x0, coef, step_index, seeds, total,
+                           n_per_sample, draw, noise_scale);
+    }
     GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
 }

@@ -6,7 +6,9 @@ What changes is how a step is executed. The reference's ``p_sample_ddim`` (ddim.
 [gather t from a device table] + [U-Net kernels] + [one fused DDIM-update kernel reading its coefficients from a device
 table indexed by a device-side step counter] + [counter -= 1]; nothing in it depends on host state, so the step is
 captured ONCE into a hipGraph and replayed S times (``use_graph=True``, default when eta == 0; with classifier-free
-guidance the 2 (or 3, ``multicond``) U-Net evaluations and their combination are part of the captured step).
+guidance the 2 (or 3, ``multicond``) U-Net evaluations and their combination are part of the captured step). eta > 0 with the
+default ``torch.randn`` step noise runs eagerly (the draw is host-driven); with ``noise_seeds`` the update kernel makes its own
+counter-based noise (``geo4d_amd.noise``) and the stochastic step is captured like the deterministic one.
 """
 import os
 
@@ -137,7 +139,14 @@ class DDIMSampler(object):
         model): ``noise_generator`` — a device ``torch.Generator`` for x_T (when not given) and the eta > 0 step noise, so a
         window's result does not depend on what ran before it; ``strict_rng`` — draw one ``randn`` per step even at eta == 0
         like ``noise_like`` in ddim.py:271 does (keeps the global RNG stream aligned with the reference across calls; forces
-        the eager path). ``precision`` is accepted and ignored (the compute mode is a property of the model here)."""
+        the eager path). ``precision`` is accepted and ignored (the compute mode is a property of the model here).
+
+        ``noise_seeds`` (an int, B ints or an int64 tensor [B]; popped like the two above) switches the noise to the counter-based
+        device generator of ``geo4d_amd.noise``: row b's step noise is a pure function of (noise_seeds[b], ddim index, element,
+        ``noise_draw``), made inside the fused update kernel, and x_T (when not given) is that generator's stream 0. The step then
+        holds nothing host-dependent, so eta > 0 is captured and replayed like eta == 0, rows of a batch are independent by
+        construction, and graph and eager runs agree bit for bit. An int seeds every row alike. ``noise_draw`` = the variant index of
+        ``n_samples``. Without ``noise_seeds`` nothing changes."""
         if score_corrector is not None or quantize_x0 or noise_dropout > 0.:
             raise NotImplementedError("score_corrector / quantize_x0 / noise_dropout are not used by Geo4D "
                                       "inference (test_geo4d.py:212-227) and have no HIP path")
@@ -147,13 +156,22 @@ class DDIMSampler(object):
             raise NotImplementedError("only the v-parameterisation of configs/inference_geo4d.yaml:43 is built")
         gen = kwargs.pop("noise_generator", None)
         strict_rng = bool(kwargs.pop("strict_rng", False))
+        noise_seeds, noise_draw = kwargs.pop("noise_seeds", None), int(kwargs.pop("noise_draw", 0))
+        rng = noise_seeds is not None
+        if rng and strict_rng:
+            raise ValueError("strict_rng keeps the global torch RNG stream aligned with the reference; noise_seeds replaces that stream")
         self.make_schedule(ddim_num_steps=S, ddim_discretize=timestep_spacing, ddim_eta=eta, verbose=schedule_verbose)
         size = (batch_size,) + tuple(shape)
         dev = self.model.device
+        if rng:
+            seeds = torch.as_tensor(noise_seeds, dtype=torch.int64)
+            seeds = seeds.expand(batch_size) if seeds.dim() == 0 else seeds.reshape(-1)
+            if seeds.numel() != batch_size:
+                raise ValueError(f"noise_seeds: one int or {batch_size} of them (batch_size), got {seeds.numel()}")
         cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         total = len(self.ddim_timesteps)
         clean_cond = bool(kwargs.pop("clean_cond", False))
-        graph_ok = (self.use_graph and eta == 0. and not strict_rng and callback is None and img_callback is None and total > 2
+        graph_ok = (self.use_graph and (eta == 0. or rng) and not strict_rng and callback is None and img_callback is None and total > 2
                     and mask is None)
         # 3-way guidance of ddim_multiplecond.py:229-234 (image yes / text "" as a third evaluation)
         uc_img = kwargs.get("unconditional_conditioning_img_nonetext") if (self.multicond and cfg) else None
@@ -168,7 +186,8 @@ class DDIMSampler(object):
         key = (size, S, timestep_spacing, sig(conditioning),
                (sig(unconditional_conditioning), sig(uc_img), float(unconditional_guidance_scale), float(cfg_img),
                 float(guidance_rescale)) if cfg else (),
-               None if fs is None else (tuple(fs.shape), fs.dtype), tuple(sorted(kwargs)))
+               None if fs is None else (tuple(fs.shape), fs.dtype), tuple(sorted(kwargs)),
+               ("rng", float(temperature), int(noise_draw)) if rng else ())      # (not eta: sigma_t lives in the coefficient table)
         st = self._static if (graph_ok and self._graph_key == key) else None
         if st is not None:
             self._copy_cond(st["cond"], conditioning)
@@ -192,6 +211,7 @@ class DDIMSampler(object):
                   "uc_img": (self._clone_cond(uc_img) if own else uc_img) if cfg else None,
                   "fs": None if fs is None else (fs.detach().clone() if own else fs)}
             st["pred_x0"] = torch.empty_like(st["img"])
+            st["seeds"] = torch.empty((batch_size,), dtype=torch.int64, device=dev) if rng else None
             st["cat"] = None
             parts = [c for c in (st["cond"], st["uc"], st["uc_img"]) if c is not None]
             if cfg and self.batch_cfg and all(isinstance(c, dict) and set(c) == set(parts[0]) for c in parts):
@@ -204,7 +224,12 @@ class DDIMSampler(object):
         mkw = dict(kwargs)
         if "unconditional_conditioning_img_nonetext" in mkw and c_img is not None:
             mkw["unconditional_conditioning_img_nonetext"] = c_img   # forwarded (and ignored) like ddim.py:217 does
-        img.copy_(torch.randn(size, device=dev, generator=gen) if x_T is None else x_T.to(dev).float())
+        if rng:
+            st["seeds"].copy_(seeds)             # static like the conditioning: a replayed step reads this window's seeds
+        if rng and x_T is None:
+            ops.philox_fill(img, st["seeds"], step=0, stream_id=ops.NOISE_STREAM_XT, draw=noise_draw)
+        else:
+            img.copy_(torch.randn(size, device=dev, generator=gen) if x_T is None else x_T.to(dev).float())
         idx.fill_(total - 1)
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
 
@@ -227,7 +252,11 @@ class DDIMSampler(object):
         def step(noise=None):
             ops.gather_timestep(idx, self.ts_table, ts)
             v = model_out()
-            ops.ddim_step(img, v.float().contiguous(), self.coef, idx, noise=noise, pred_x0=pred_x0)
+            if rng:      # noise made in the kernel from (seed, *idx, element, draw); sigma_t = 0 at eta == 0 adds nothing
+                ops.ddim_step_rng(img, v.float().contiguous(), self.coef, idx, st["seeds"], draw=noise_draw, noise_scale=temperature,
+                                  pred_x0=pred_x0)
+            else:
+                ops.ddim_step(img, v.float().contiguous(), self.coef, idx, noise=noise, pred_x0=pred_x0)
             ops.advance_index(idx, -1)
 
         def log(i):          # ddim.py:195-197: index = total - i - 1
@@ -266,7 +295,7 @@ class DDIMSampler(object):
                     img_orig = x0d if clean_cond else self.model.q_sample(x0d, t_now, noise=torch.randn(x0d.shape, device=dev, generator=gen))
                     img.copy_(img_orig * md + (1. - md) * img)
                 noise = None
-                if eta > 0.:
+                if eta > 0. and not rng:
                     noise = torch.randn(size, device=dev, generator=gen) * temperature
                 elif strict_rng:
                     torch.randn(size, device=dev, generator=gen)          # drawn and multiplied by sigma = 0 in the reference

@@ -859,6 +859,43 @@ def ddim_step(x, v, coef, step_index, noise=None, pred_x0=None):
     return x
 
 
+NOISE_STREAM_XT, NOISE_STREAM_STEP = 0, 1      # Philox counter word 2 (geo4d_amd/noise.py): initial noise x_T / DDIM step noise
+
+
+def _seeds(seeds, B, dev):
+    assert seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.numel() == B and seeds.device == dev, \
+        f"seeds: int64 [{B}] on {dev} expected"
+
+
+def philox_fill(out, seeds, *, step, stream_id, draw=0, scale=1.0, raw=False):
+    """out [B, ...] (fp32: normals * scale; ``raw``: int32, the 32-bit words) <- the counter-based noise of geo4d_amd/noise.py, row b keyed by
+    seeds[b] (int64 [B] on the device). ``step``: an int, or an int32 [1] device tensor read by the kernel (capturable)."""
+    lib = _lib.load()
+    _dev(out, "out")
+    assert out.is_contiguous() and out.dtype == (torch.int32 if raw else torch.float32)
+    B = out.shape[0]
+    _seeds(seeds, B, out.device)
+    on_dev = isinstance(step, torch.Tensor)
+    assert not on_dev or (step.dtype == torch.int32 and step.device == out.device)
+    _lib.check(lib.geo4d_philox_fill(out.data_ptr(), int(raw), seeds.data_ptr(), B, out.numel() // B, step.data_ptr() if on_dev else None,
+                                     0 if on_dev else int(step), int(stream_id), int(draw), float(scale), _stream()), "geo4d_philox_fill")
+    return out
+
+
+def ddim_step_rng(x, v, coef, step_index, seeds, *, draw=0, noise_scale=1.0, pred_x0=None):
+    """ddim_step with the noise of row b made in the kernel: the stream-1 normals of (seeds[b], *step_index, element, draw) * noise_scale."""
+    lib = _lib.load()
+    _dev(x, "x")
+    assert x.dtype == torch.float32 and v.dtype == torch.float32 and x.is_contiguous() and v.is_contiguous() and v.shape == x.shape
+    assert coef.dtype == torch.float32 and step_index.dtype == torch.int32
+    assert pred_x0 is None or (pred_x0.dtype == torch.float32 and pred_x0.is_contiguous() and pred_x0.shape == x.shape)
+    B = x.shape[0]
+    _seeds(seeds, B, x.device)
+    _lib.check(lib.geo4d_ddim_step_rng(x.data_ptr(), v.data_ptr(), _ptr(pred_x0), coef.data_ptr(), step_index.data_ptr(), seeds.data_ptr(),
+                                       B, x.numel() // B, int(draw), float(noise_scale), _stream()), "geo4d_ddim_step_rng")
+    return x
+
+
 def cfg_combine(e_c, e_u, e_i=None, *, scale, cfg_img=None, guidance_rescale=0.0):
     """Classifier-free guidance on fp32 U-Net outputs [B, ...]: 2-way, or 3-way with e_i (image yes / text ""), + rescale_noise_cfg."""
     lib = _lib.load()

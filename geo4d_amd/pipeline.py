@@ -115,11 +115,17 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     image tokens of a zero image, geo4d_amd/encoders.py). ``c_concat`` is taken from ``cond`` if present, otherwise computed
     from ``videos`` [B,3,T,H,W] by the VAE encoder like the reference does. ``multiple_cond_cfg`` selects the 3-way guidance
     sampler. Returns [B, n_samples, 11, T, H, W] like the reference; with ``decode=False`` the denoised latents
-    [B, n_samples, 16, T, h, w] instead (the caller decodes them, e.g. frame-sharded across GPUs)."""
+    [B, n_samples, 16, T, h, w] instead (the caller decodes them, e.g. frame-sharded across GPUs).
+
+    Classifier-free guidance (``unconditional_guidance_scale != 1``): when the context is built here, the unconditional dicts are
+    built here too (test_geo4d.py:171-197) unless the caller passes them; with a caller-supplied ``cond`` they must be passed.
+    ``noise_seeds`` (keyword, forwarded to the sampler) selects the counter-based device noise; variant j of ``n_samples`` then
+    samples with ``noise_draw = j``."""
     if loop or interp:
         raise NotImplementedError("loop / interp raise in the reference too (test_geo4d.py:161-162)")
     batch_size = noise_shape[0]
     fs_t = torch.tensor([fs] * batch_size, dtype=torch.long, device=model.device)
+    own_ctx = None                                  # the context, when it was built here: what the unconditional dicts derive from
     if cond is None:
         # test_geo4d.py:124-158: text prompts are blanked unless text_input; the image branch embeds a ZERO image unless
         # model.cross_attention (then every frame). Built lazily from geo4d_amd.encoders and cached: constant across windows.
@@ -136,6 +142,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                 cache.clear()
                 cache[key] = ctx
         cond = {"c_crossattn": [ctx]}
+        own_ctx = ctx
     if "c_concat" not in cond and model.model.conditioning_key == "hybrid":
         cond = dict(cond, c_concat=[get_latent_z(model, videos)])       # test_geo4d.py:159-170 (modality != img_vidpc)
     def with_latent(c):
@@ -143,15 +150,42 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         if isinstance(c, dict) and "c_concat" not in c and "c_concat" in cond:
             c = dict(c, c_concat=cond["c_concat"])
         return c
+    parts = {}
+    def uncond_parts():
+        """test_geo4d.py:171-183: (text embedding of "" | zeros, Resampler over the image tower's tokens of a ZERO image, the conditional
+        image tokens). Computed once per call, and only when a dict has to be built."""
+        if not parts:
+            if model.cross_attention:
+                b, c, t, h, w = videos.shape
+                emb = model.embedder(torch.zeros((b * t, c, h, w), device=videos.device, dtype=videos.dtype))
+                uc_img_emb = model.image_proj_model(emb.reshape(b, t, emb.shape[1], emb.shape[2]))
+            else:
+                uc_img_emb = model.image_proj_model(model.embedder(torch.zeros_like(videos[:, :, 0])))
+            n_text = own_ctx.shape[1] - uc_img_emb.shape[1]
+            if model.uncond_type == "empty_seq":
+                uc_emb = model.get_learned_conditioning([""] * batch_size).to(uc_img_emb.device)
+            elif model.uncond_type == "zero_embed":
+                uc_emb = torch.zeros_like(own_ctx[:, :n_text])
+            else:
+                raise NotImplementedError(f"uncond_type = {model.uncond_type!r}")
+            parts.update(uc_emb=uc_emb, uc_img_emb=uc_img_emb, img_emb=own_ctx[:, n_text:])
+        return parts
     uc = None
     if unconditional_guidance_scale != 1.0:
         uc = kwargs.pop("unconditional_conditioning", None)
         if uc is None:
-            raise NotImplementedError("CFG needs precomputed unconditional conditioning (front-end is N3)")
+            if own_ctx is None:
+                raise NotImplementedError("CFG with a caller-supplied `cond` needs the unconditional conditioning passed as well")
+            p = uncond_parts()
+            uc = {"c_crossattn": [torch.cat([p["uc_emb"], p["uc_img_emb"]], dim=1)]}
         uc = with_latent(uc)
     if multiple_cond_cfg and cfg_img != 1.0 and uc is not None:
         if kwargs.get("unconditional_conditioning_img_nonetext") is None:
-            raise NotImplementedError("multiple_cond_cfg needs precomputed unconditional_conditioning_img_nonetext (front-end is N3)")
+            if own_ctx is None:
+                raise NotImplementedError("multiple_cond_cfg with a caller-supplied `cond` needs unconditional_conditioning_img_nonetext "
+                                          "passed as well")
+            p = uncond_parts()      # image yes, text "" (test_geo4d.py:191-195)
+            kwargs["unconditional_conditioning_img_nonetext"] = {"c_crossattn": [torch.cat([p["uc_emb"], p["img_emb"]], dim=1)]}
         kwargs["unconditional_conditioning_img_nonetext"] = with_latent(kwargs["unconditional_conditioning_img_nonetext"])
     else:
         kwargs.update({"unconditional_conditioning_img_nonetext": None})
@@ -162,7 +196,9 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     if sampler is None:
         sampler = cache[cls] = cls(model)
     variants = []
-    for _ in range(n_samples):
+    for j in range(n_samples):
+        if kwargs.get("noise_seeds") is not None:
+            kwargs["noise_draw"] = j
         samples, _ = sampler.sample(S=ddim_steps, conditioning=cond, batch_size=batch_size, shape=noise_shape[1:], verbose=False,
                                     unconditional_guidance_scale=unconditional_guidance_scale, unconditional_conditioning=uc,
                                     eta=ddim_eta, cfg_img=cfg_img, mask=None, x0=None, fs=fs_t, x_T=x_T,
@@ -175,7 +211,8 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
 def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_length=16, seed=123, ddim_steps=50, ddim_eta=0.0,
              unconditional_guidance_scale=1.0, fs=24, timestep_spacing="uniform_trailing", guidance_rescale=0.7,
              prompts=("Output a video that assigns each 3D location in the world a consistent color.",),
-             synthesize=None, gather=True, with_cameras=False, decode="local", decoder=None, window_batch=1, **kwargs):
+             synthesize=None, gather=True, with_cameras=False, decode="local", decoder=None, window_batch=1, step_noise="torch",
+             **kwargs):
     """The window loop of ``run_inference`` (test_geo4d.py:396-443), data-parallel over windows.
 
     ``videos_all`` [1,3,T,H,W] in [-1,1]; ``context`` = cross-attention context [1, 77+16*video_length, D] (the OpenCLIP /
@@ -195,13 +232,23 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
     (decode_modalities_sharded), which keeps all GPUs busy in a ragged last round (14 windows on 8 GPUs) and for a single window.
     Every rank ends up with every window either way.
 
-    ``window_batch`` (round 6): a rank denoises this many of ITS windows as ONE batch (eta = 0 only). Windows are independent, and at B = 1
+    ``window_batch`` (round 6): a rank denoises this many of ITS windows as ONE batch (eta = 0, or any eta with step_noise="device"). Windows are independent, and at B = 1
     the U-Net's levels 1-3 leave most of the 256 CUs idle (tiles < CUs): two windows per DDIM step take 1.64x the time of one on an
     MI355X (profiles/r06_window_batch.md: 7.78 vs 6.52 denoised frames/s). Noise, VAE-encode sampling and conditioning stay seeded /
     computed PER WINDOW, so a window's result does not depend on what it was batched with beyond fp32 round-off (GEMM tile choice follows M).
-    In the sharded-decode mode a round then covers world x window_batch windows, rank r owning the r-th run of window_batch."""
+    In the sharded-decode mode a round then covers world x window_batch windows, rank r owning the r-th run of window_batch.
+
+    ``step_noise``: "torch" - the eta > 0 step noise is drawn by ``torch.randn`` from a per-window device generator (eager steps, one
+    window at a time); "device" - it is made inside the fused update kernel by the counter-based generator of ``geo4d_amd.noise``, keyed
+    by the same per-window seed (``noise_seeds``): the stochastic step is captured into the hipGraph like the deterministic one,
+    ``window_batch`` applies at eta > 0, and a window's noise cannot depend on what it was batched with. x_T stays the per-window CPU
+    draw in both."""
     from . import dist as gdist
     synthesize = synthesize or image_guided_synthesis
+    if step_noise not in ("torch", "device"):
+        raise ValueError(f"run_clip: step_noise={step_noise!r} (expected 'torch' or 'device')")
+    if step_noise == "device":
+        kwargs.pop("noise_generator", None)
     B, C, T, H, W = videos_all.shape
     if B != 1:
         raise ValueError("run_clip: one clip at a time (the reference asserts bs == 1, test_geo4d.py:354-356)")
@@ -220,10 +267,12 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
         videos = videos_all[:, :, slices[wi]].clone()
         wseed = (int(seed) * 1000003 + wi) % (2 ** 63 - 1)
         x_T = torch.randn(noise_shape, generator=torch.Generator().manual_seed(wseed)).to(videos_all.device)
-        if ddim_eta > 0.0 and videos_all.is_cuda:   # per-window device stream for the stochastic step noise (eta > 0)
+        extra = {} if decode_here else {"decode": False}
+        if step_noise == "device":                  # the step noise is a function of (wseed, step, element): nothing to carry
+            extra["noise_seeds"] = [wseed]
+        elif ddim_eta > 0.0 and videos_all.is_cuda:   # per-window device stream for the stochastic step noise (eta > 0)
             kwargs["noise_generator"] = torch.Generator(device=videos_all.device).manual_seed(wseed)
         ctx = context(videos) if callable(context) else context
-        extra = {} if decode_here else {"decode": False}
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(wseed)                                   # posterior sampling noise of the VAE encode
             maps = synthesize(model, list(prompts), videos, noise_shape, n_samples=1, ddim_steps=ddim_steps, ddim_eta=ddim_eta,
@@ -233,16 +282,17 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
         assert maps.shape[1] == 1, "only support variants size = 1"
         return maps[:, 0]
 
-    wb = 1 if ddim_eta > 0.0 else max(1, int(window_batch))
+    wb = 1 if (ddim_eta > 0.0 and step_noise != "device") else max(1, int(window_batch))
 
     def window_group(wis, decode_here):
         """Several of this rank's windows as ONE batch through the sampler (and the decoder): [len(wis), 11 | 16, T, ...]."""
         if len(wis) == 1:
             return one_window(wis[0], decode_here)
-        vids, xs, zs, ctxs = [], [], [], []
+        vids, xs, zs, ctxs, wseeds = [], [], [], [], []
         for wi in wis:
             videos = videos_all[:, :, slices[wi]].clone()
             wseed = (int(seed) * 1000003 + wi) % (2 ** 63 - 1)
+            wseeds.append(wseed)
             xs.append(torch.randn(noise_shape, generator=torch.Generator().manual_seed(wseed)))
             ctxs.append(context(videos) if callable(context) else context)
             if model.model.conditioning_key == "hybrid":
@@ -254,6 +304,8 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
         if zs:
             cond["c_concat"] = [torch.cat(zs, 0)]
         extra = {} if decode_here else {"decode": False}
+        if step_noise == "device":
+            extra["noise_seeds"] = wseeds
         maps = synthesize(model, list(prompts) * len(wis), torch.cat(vids, 0), [len(wis)] + noise_shape[1:], n_samples=1, ddim_steps=ddim_steps,
                           ddim_eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale, fs=fs, timestep_spacing=timestep_spacing,
                           guidance_rescale=guidance_rescale, pointmap_vae=pointmap_vae, cond=cond, x_T=torch.cat(xs, 0).to(videos_all.device),

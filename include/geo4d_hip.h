@@ -253,6 +253,21 @@ int geo4d_linear_small(const float* x, long ldx, const float* w, long ldw, const
  * replaces DDIMSampler.p_sample_ddim arithmetic (ddim.py:232-277) + DDPM.predict_* (ddpm3d.py:278-290). */
 int geo4d_ddim_step(float* x, const float* v, const float* noise, float* pred_x0, const float* coef, const int* step_index,
                     long n, void* stream);
+/* Counter-based Gaussian noise (Philox4x32-10, Salmon et al. SC'11; DESIGN.md section 15, restated in numpy by geo4d_amd/noise.py).
+ * The value of element i of sample b is a pure function of (seeds[b], step, stream_id, draw, i): key = (seed low word, seed high word),
+ * counter = (i / 4, step, stream_id, draw), element i takes output word i % 4; words (0, 1) and (2, 3) are two Box-Muller pairs with
+ * u1 = ((w_a >> 8) + 1) 2^-24, u2 = (w_b >> 8) 2^-24, even word: sqrt(-2 ln u1) cos(2 pi u2), odd word: sqrt(-2 ln u1) sin(2 pi u2);
+ * never NaN / Inf, |z| <= 5.768. stream_id: 0 = initial noise x_T, 1 = DDIM step noise (2 reserved). seeds: int64 [B] in DEVICE memory;
+ * step = *step_index when step_index != NULL (device int, so a captured launch follows the step counter), else step_value.
+ * kind 0: out = fp32 [B][n_per_sample] normals * scale; kind 1: out = uint32 [B][n_per_sample] raw words (scale ignored).
+ * n_per_sample <= 2^34. Rows that are whole 16-byte quads (n_per_sample % 4 == 0, aligned base) take one Philox call per quad. */
+int geo4d_philox_fill(void* out, int kind, const long* seeds, int B, long n_per_sample, const int* step_index, int step_value,
+                      int stream_id, int draw, float scale, void* stream);
+/* The DDIM update above on x / v / pred_x0 = [B][n_per_sample] with noise[b][i] = the stream-1 normal of (seeds[b], *step_index, i, draw)
+ * * noise_scale made in registers: same bits as the fill (kind 0, scale = noise_scale) into a buffer passed as `noise` to the update above.
+ * The stochastic (eta > 0) step then holds nothing host-dependent: capturable, and a sample's noise does not depend on its batch. */
+int geo4d_ddim_step_rng(float* x, const float* v, float* pred_x0, const float* coef, const int* step_index, const long* seeds, int B,
+                        long n_per_sample, int draw, float noise_scale, void* stream);
 /* Classifier-free guidance on fp32 [B][n] U-Net outputs:
  *   out = e_u + cfg_img (e_i - e_u) + scale (e_c - e_i)          (e_i == NULL: out = e_u + scale (e_c - e_u))
  *   guidance_rescale > 0: out = r * out * std(e_c)/std(out) + (1 - r) * out, unbiased std per batch sample over the n other elements
