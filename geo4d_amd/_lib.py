@@ -80,6 +80,11 @@ class Attention(C.Structure):
     ]
 
 
+class AttentionPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("nseg", C.c_int), ("qb", C.c_int), ("occ", C.c_int), ("ps", C.c_int), ("rows_per_wg", C.c_int),
+                ("grid", C.c_uint * 3), ("variant", C.c_int)]
+
+
 class Align(C.Structure):
     _fields_ = [
         ("pred", C.c_void_p), ("conf", C.c_void_p), ("logdepth", C.c_void_p), ("cams", C.c_void_p), ("slot_trf", C.c_void_p),
@@ -126,6 +131,7 @@ SIGNATURES = {
                                      C.c_void_p]),
     "geo4d_softmax_rows_causal": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_float, C.c_int,
                                             C.c_int, C.c_void_p]),
+    "geo4d_attention_plan": (C.c_int, [C.POINTER(Attention), C.POINTER(AttentionPlan)]),
     "geo4d_attention": (C.c_int, [C.POINTER(Attention), C.c_void_p]),
     "geo4d_temporal_attention": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                            C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,

@@ -19,6 +19,7 @@
 //     Tokens stay in frame-major order [T, HW, C]; the kernel gathers the T rows of a pixel itself.
 #include "common.h"
 #include "geo4d_hip.h"
+#include "attention_plan.h"
 
 namespace {
 
@@ -794,99 +795,68 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const T* __restrict_
     }
 }
 
+// Every instantiation that is built, keyed by what the plan names: (dtype, kernel, nseg, qb, occ, ps). The compiler emits the kernels in
+// the order of this table (the order the launch function first named them in before the planner), and with another order it allocated the
+// registers of the two flash_attn2_kernel<bf16x3_t, true, ..> builds differently: keep the order, add new rows at the end.
+using AttnKernel = void (*)(const geo4d_attention_t);
+struct AttnInstance {
+    int dtype, kernel, nseg, qb, occ, ps;
+    AttnKernel fn;
+};
+const AttnInstance ATTN_INSTANCES[] = {
+    {GEO4D_BF16, 2, 1, 2, 2, 0, flash_attn2_kernel<bf16_t, false, 2>},
+    {GEO4D_F16, 2, 1, 2, 2, 0, flash_attn2_kernel<f16_t, false, 2>},
+    {GEO4D_BF16X3, 2, 1, 2, 1, 1, flash_attn2_kernel<bf16x3_t, true, 1>},
+    {GEO4D_BF16X3, 2, 1, 2, 2, 1, flash_attn2_kernel<bf16x3_t, true, 2>},
+    {GEO4D_F32, 1, 2, 1, 1, 0, flash_attn_kernel<float, 2, 1, 1>},
+    {GEO4D_F32, 1, 1, 2, 2, 0, flash_attn_kernel<float, 1, 2, 2>},
+    {GEO4D_F32, 1, 1, 1, 1, 0, flash_attn_kernel<float, 1, 1, 1>},
+    {GEO4D_BF16X3, 1, 1, 2, 2, 1, flash_attn_kernel<bf16x3_t, 1, 2, 2, true>},
+    {GEO4D_BF16X3, 1, 1, 1, 1, 1, flash_attn_kernel<bf16x3_t, 1, 1, 1, true>},
+    {GEO4D_BF16X3, 1, 2, 1, 1, 0, flash_attn_kernel<bf16x3_t, 2, 1, 1>},
+    {GEO4D_BF16X3, 1, 1, 2, 2, 0, flash_attn_kernel<bf16x3_t, 1, 2, 2>},
+    {GEO4D_BF16X3, 1, 1, 1, 1, 0, flash_attn_kernel<bf16x3_t, 1, 1, 1>},
+    {GEO4D_BF16, 1, 1, 1, 4, 0, flash_attn_kernel<bf16_t, 1, 1, 4>},
+    {GEO4D_BF16, 1, 2, 1, 1, 0, flash_attn_kernel<bf16_t, 2, 1, 1>},
+    {GEO4D_BF16, 1, 1, 2, 2, 0, flash_attn_kernel<bf16_t, 1, 2, 2>},
+    {GEO4D_BF16, 1, 1, 1, 1, 0, flash_attn_kernel<bf16_t, 1, 1, 1>},
+    {GEO4D_F16, 1, 1, 1, 4, 0, flash_attn_kernel<f16_t, 1, 1, 4>},
+    {GEO4D_F16, 1, 2, 1, 1, 0, flash_attn_kernel<f16_t, 2, 1, 1>},
+    {GEO4D_F16, 1, 1, 2, 2, 0, flash_attn_kernel<f16_t, 1, 2, 2>},
+    {GEO4D_F16, 1, 1, 1, 1, 0, flash_attn_kernel<f16_t, 1, 1, 1>},
+};
+
+// validate + resolve: the one path to a plan, for the query and for the launch
+int attention_plan(const geo4d_attention_t* p, geo4d_attn::AttnPlan& pl) {
+    if (!p) return GEO4D_EINVAL;
+    pl = geo4d_attn::validate(*p);
+    if (!pl.error) pl = geo4d_attn::resolve(*p);
+    if (pl.error) geo4d_set_error(pl.error);
+    return pl.rc;
+}
+
 }  // namespace
 
-extern "C" int geo4d_attention(const geo4d_attention_t* pp, void* stream) {
-    if (!pp) return GEO4D_EINVAL;
-    const geo4d_attention_t& p = *pp;
-    const int esz = (p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3) ? 4 : 2;
-    if (p.dtype < 0 || p.dtype > 3 || p.B <= 0 || p.H <= 0 || p.Nq <= 0 || p.nseg < 1 || p.nseg > 2) { geo4d_set_error("attention: bad arguments"); return GEO4D_EINVAL; }
-    if (p.head_dim != 64) { geo4d_set_error("attention: only d_head = 64 is built (yaml num_head_channels: 64)"); return GEO4D_ENOTSUP; }
-    if ((p.ldq * esz) % 16 || (p.ldo * esz) % 16 || ((uintptr_t)p.q % 16) || ((uintptr_t)p.o % 16)) { geo4d_set_error("attention: q/o alignment"); return GEO4D_EINVAL; }
-    for (int s = 0; s < p.nseg; ++s) {
-        if (p.Nk[s] <= 0 || p.kv_div[s] <= 0 || !p.k[s] || !p.vt[s] || (p.ldk[s] * esz) % 16 || (p.ldvt[s] * esz) % 16 || (p.vt_bs[s] * esz) % 16 ||
-            ((uintptr_t)p.k[s] % 16) || ((uintptr_t)p.vt[s] % 16) || p.ldvt[s] * (16 / esz) < 0 || ((p.Nk[s] + 16 / esz - 1) / (16 / esz)) * (16 / esz) > p.ldvt[s]) {
-            geo4d_set_error("attention: bad key/value segment");
-            return GEO4D_EINVAL;
-        }
-    }
-    if (!p.zeros || ((uintptr_t)p.zeros % 16)) { geo4d_set_error("attention: `zeros` must point at 16 zero bytes"); return GEO4D_EINVAL; }
-    if (p.H > 65535 || p.B > 65535) { geo4d_set_error("attention: grid too large"); return GEO4D_EINVAL; }
-    if (p.split_out && esz != 4) { geo4d_set_error("attention: split_out is the producer format of the 4-byte storage modes (f32 / bf16x3)"); return GEO4D_EINVAL; }
-    if (p.qkv_split) {
-        if (p.dtype != GEO4D_BF16X3 || p.nseg != 1 || (p.Nk[0] % 8) || (p.ldq % 8) || (p.ldk[0] % 8) || (p.ldvt[0] % 8) || (p.vt_bs[0] % 8) ||
-            ((uintptr_t)p.q % 32) || ((uintptr_t)p.k[0] % 32) || ((uintptr_t)p.vt[0] % 32)) {
-            geo4d_set_error("attention: qkv_split needs dtype bf16x3, one key/value set, Nk % 8 == 0, leading dimensions % 8 == 0 and 32-byte aligned bases");
-            return GEO4D_EINVAL;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // variant: 0 = host default; explicit: 1 = 128 rows / workgroup at 3 waves per SIMD (round-1 kernel), 2 = the same at 4 waves
-    // per SIMD (128-VGPR budget), 3 = 256 rows / workgroup, two query blocks per wave (self-attention only)
-    int variant = p.variant;
-    if (variant < 0 || variant > 5) { geo4d_set_error("attention: unknown variant"); return GEO4D_EINVAL; }
-    // 4 / 5 = flash_attn2_kernel (round 4: skewed query blocks, matrix work beside every softmax): one key/value set, 16-bit types
-    // (4) and bf16x3 on pre-split inputs (4 = one wave per SIMD with the whole register file, 5 = two waves per SIMD).
-    // Default since round 4 wherever it applies and a 256-row workgroup is not mostly empty (measured, profiles/r04_attention.md:
-    // bf16 N = 2560 199.9 -> 189.9 us, N = 640 33.6 -> 31.4; pre-split bf16x3 N = 2560 524 -> 443 us, N = 640 76.3 -> 67.8)
-    // (bf16x3: the two-waves-per-SIMD build wins on the long level-0 sequences once the workgroups of a (frame, head) share an XCD:
-    // N = 2560 467 us (variant 4) vs 443 us (variant 5); N = 640 67.8 vs 70.3 us)
-    // (round 5: that kernel stages K / V^T through 2 GB buffer windows with 32-bit offsets: one (batch, head)'s keys and V^T rows must
-    // fit one - they do by orders of magnitude at every size of BASELINE.json; otherwise the pointer-staged kernels below serve the call)
-    const long esz_w = (p.dtype == GEO4D_BF16 || p.dtype == GEO4D_F16) ? 2 : 4;
-    const bool window_ok = p.nseg == 1 && ((long)(p.Nk[0] + 64) * p.ldk[0] + 64) * esz_w < (1L << 31) && (64L * p.ldvt[0] + p.Nk[0] + 64) * esz_w < (1L << 31);
-    if (variant == 0 && p.nseg == 1 && p.Nq >= 256 && window_ok &&
-        (p.dtype == GEO4D_BF16 || p.dtype == GEO4D_F16 || (p.dtype == GEO4D_BF16X3 && p.qkv_split)))
-        variant = (p.dtype == GEO4D_BF16X3 && p.Nq >= 1024) ? 5 : 4;
-    if (variant >= 4) {
-        const bool ok16 = (p.dtype == GEO4D_BF16 || p.dtype == GEO4D_F16) && variant == 4;
-        const bool okx3 = p.dtype == GEO4D_BF16X3 && p.qkv_split;
-        if (p.nseg != 1 || !(ok16 || okx3)) { geo4d_set_error("attention: variants 4 / 5 take one key/value set in bf16 / f16 (4) or pre-split bf16x3"); return GEO4D_EINVAL; }
-        if (!window_ok) { geo4d_set_error("attention: variants 4 / 5 need one (batch, head)'s keys and V^T rows inside a 2 GB window"); return GEO4D_EINVAL; }
-        const dim3 grid2((p.Nq + 255) / 256, p.H, p.B);
-        if (p.dtype == GEO4D_BF16) hipLaunchKernelGGL((flash_attn2_kernel<bf16_t, false, 2>), grid2, dim3(256), 0, st, p);
-        else if (p.dtype == GEO4D_F16) hipLaunchKernelGGL((flash_attn2_kernel<f16_t, false, 2>), grid2, dim3(256), 0, st, p);
-        else if (variant == 4) hipLaunchKernelGGL((flash_attn2_kernel<bf16x3_t, true, 1>), grid2, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((flash_attn2_kernel<bf16x3_t, true, 2>), grid2, dim3(256), 0, st, p);
+extern "C" int geo4d_attention_plan(const geo4d_attention_t* p, geo4d_attention_plan_t* plan) {
+    geo4d_attn::AttnPlan pl;
+    if (!plan) return GEO4D_EINVAL;
+    const int rc = attention_plan(p, pl);
+    if (rc == GEO4D_OK) *plan = pl;
+    return rc;
+}
+
+extern "C" int geo4d_attention(const geo4d_attention_t* p, void* stream) {
+    geo4d_attn::AttnPlan pl;
+    const int rc = attention_plan(p, pl);
+    if (rc != GEO4D_OK) return rc;
+    for (const AttnInstance& k : ATTN_INSTANCES) {
+        if (k.dtype != p->dtype || k.kernel != pl.kernel || k.nseg != pl.nseg || k.qb != pl.qb || k.occ != pl.occ || k.ps != pl.ps) continue;
+        hipLaunchKernelGGL(k.fn, dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(256), 0, (hipStream_t)stream, *p);
         GEO4D_CHECK_LAUNCH();
         return GEO4D_OK;
     }
-    // default (measured, profiles/r02_attention_variants.md): two query blocks per wave for 16-bit self-attention (bf16 N = 2560:
-    // 245 -> 199 us), one for the 4-byte storage modes (their two-block build spills: bf16x3 523 -> 563 us)
-    if (variant == 0) variant = (p.nseg == 1 && (p.dtype == GEO4D_BF16 || p.dtype == GEO4D_F16)) ? 3 : 1;
-    if (p.nseg == 2 || p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3) {
-        if (variant == 3 && p.nseg == 2) variant = 1;     // dual-KV cross attention: one query block per wave
-        if (variant == 2 && (p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3)) variant = 1;   // 4-byte storage needs > 128 VGPRs
-    }
-    const int rows = variant == 3 ? 256 : 128;
-    const dim3 grid((p.Nq + rows - 1) / rows, p.H, p.B);
-#define ATT_LAUNCH(TT, NS, QB_, OCC_) hipLaunchKernelGGL((flash_attn_kernel<TT, NS, QB_, OCC_>), grid, dim3(256), 0, st, p)
-#define ATT_TYPED(TT)                                                        \
-    do {                                                                     \
-        if (p.nseg == 2) { ATT_LAUNCH(TT, 2, 1, 1); }                        \
-        else if (variant == 3) { ATT_LAUNCH(TT, 1, 2, 2); }                  \
-        else { ATT_LAUNCH(TT, 1, 1, 1); }                                    \
-    } while (0)
-    switch (p.dtype) {
-        case GEO4D_F32: ATT_TYPED(float); break;
-        case GEO4D_BF16X3:
-            if (p.qkv_split && variant == 3) hipLaunchKernelGGL((flash_attn_kernel<bf16x3_t, 1, 2, 2, true>), grid, dim3(256), 0, st, p);
-            else if (p.qkv_split) hipLaunchKernelGGL((flash_attn_kernel<bf16x3_t, 1, 1, 1, true>), grid, dim3(256), 0, st, p);
-            else ATT_TYPED(bf16x3_t);
-            break;
-        case GEO4D_BF16:
-            if (p.nseg == 1 && variant == 2) ATT_LAUNCH(bf16_t, 1, 1, 4);
-            else ATT_TYPED(bf16_t);
-            break;
-        default:
-            if (p.nseg == 1 && variant == 2) ATT_LAUNCH(f16_t, 1, 1, 4);
-            else ATT_TYPED(f16_t);
-            break;
-    }
-#undef ATT_TYPED
-#undef ATT_LAUNCH
-    GEO4D_CHECK_LAUNCH();
-    return GEO4D_OK;
+    geo4d_set_error("attention: the plan names an instantiation that is not built");
+    return GEO4D_ENOTSUP;
 }
 
 extern "C" int geo4d_temporal_attention(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,

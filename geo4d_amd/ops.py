@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, ConvGemm, GroupNorm2, GroupNormPlan
+from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, AttentionPlan, ConvGemm, GroupNorm2, GroupNormPlan
 from .precision import resolve as _resolve_precision
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -643,58 +643,50 @@ def softmax_rows(x, scale, out_dtype, out=None, causal_period=0):
 ATTN_VARIANT = int(_os.environ.get("GEO4D_ATTN_VARIANT", "0"))   # 0 = library default; 1..3 = A/B builds (include/geo4d_hip.h)
 
 
+def attention_descriptor(q, kv, *, B, H, Nq, scale, out=None, x3=False, variant=None, split_out=False, qkv_split=False):
+    """(geo4d_attention_t of the launch `attention` makes for these arguments, its output tensor)."""
+    if qkv_split:
+        assert len(kv) == 1 and all(isinstance(t, SplitAct) for t in (q, kv[0][0], kv[0][1])), "qkv_split takes SplitAct q / k / vt of one key/value set"
+        assert q.dtype == torch.bfloat16
+    per = 2 if qkv_split else 1       # a SplitAct holds 2 bf16 per element: torch's strides count bf16, the library's ld* / vt_bs elements
+    _dev(q, "q", qkv_split)
+    if out is None:
+        out = new_split(B * Nq, H * 64, q.device) if split_out else torch.empty((B * Nq, H * 64), device=q.device, dtype=torch.float32 if qkv_split else q.dtype)
+    split_out = isinstance(out, SplitAct)
+    if split_out:
+        _split_out_ok(out, B * Nq)
+    p = Attention()
+    p.q, p.o, p.ldq, p.ldo = q.data_ptr(), out.data_ptr(), _ld(q) // per, (_ld(out) // 2 if split_out else _ld(out))
+    p.split_out, p.qkv_split = int(split_out), int(qkv_split)
+    assert 1 <= len(kv) <= 2
+    for i, (k, vt, nk, div, vt_bs) in enumerate(kv):
+        assert k.dtype == q.dtype and vt.dtype == q.dtype
+        _dev(k, "k", qkv_split); _dev(vt, "vt", qkv_split)
+        assert all(n % per == 0 for n in (_ld(q), _ld(k), _ld(vt), vt_bs))
+        p.k[i], p.vt[i], p.ldk[i], p.ldvt[i], p.vt_bs[i], p.Nk[i], p.kv_div[i] = k.data_ptr(), vt.data_ptr(), _ld(k) // per, _ld(vt) // per, vt_bs // per, nk, div
+    p.zeros = workspace(q.device)[1].data_ptr()
+    if x3 and not qkv_split:
+        assert q.dtype == torch.float32, "x3 attention runs on f32 q / k / v^T"
+    code = BF16X3 if (x3 or qkv_split) else dt_code(q.dtype)
+    p.B, p.H, p.Nq, p.nseg, p.head_dim, p.dtype, p.scale = B, H, Nq, len(kv), 64, code, scale
+    p.variant = ATTN_VARIANT if variant is None else variant
+    return p, out
+
+
+def attention_plan(p):
+    """What geo4d_attention would launch for this descriptor (_lib.AttentionPlan); raises where the launch would refuse it."""
+    plan = AttentionPlan()
+    _lib.check(_lib.load().geo4d_attention_plan(C.byref(p), C.byref(plan)), "geo4d_attention_plan")
+    return plan
+
+
 def attention(q, kv, *, B, H, Nq, scale, out=None, x3=False, variant=None, split_out=False, qkv_split=False):
     """q [B*Nq, >=H*64] view; kv = list of (k, vt, Nk, kv_div, vt_bs): k [(B/kv_div)*Nk, >=H*64] view, vt = V TRANSPOSED
     as a [>=H*64, ld] view (row = channel, column = key) whose batch b' starts vt_bs elements after batch b'-1.
     `qkv_split` (bf16x3, one key/value set): q, k and vt are SplitAct views (bf16, 2 per element: what the projections wrote with
     split_out=True), strides / vt_bs in bf16 elements as torch reports them."""
     lib = _lib.load()
-    if qkv_split:
-        assert len(kv) == 1 and all(isinstance(t, SplitAct) for t in (q, kv[0][0], kv[0][1])), "qkv_split takes SplitAct q / k / vt of one key/value set"
-        return _attention_presplit(lib, q, kv[0], B=B, H=H, Nq=Nq, scale=scale, out=out, variant=variant, split_out=split_out)
-    _dev(q, "q")
-    if out is None:
-        out = new_split(B * Nq, H * 64, q.device) if split_out else torch.empty((B * Nq, H * 64), device=q.device, dtype=q.dtype)
-    split_out = isinstance(out, SplitAct)
-    if split_out:
-        _split_out_ok(out, B * Nq)
-    p = Attention()
-    p.q, p.o, p.ldq, p.ldo = q.data_ptr(), out.data_ptr(), _ld(q), (_ld(out) // 2 if split_out else _ld(out))
-    p.split_out = int(split_out)
-    assert 1 <= len(kv) <= 2
-    for i, (k, vt, nk, div, vt_bs) in enumerate(kv):
-        assert k.dtype == q.dtype and vt.dtype == q.dtype
-        _dev(k, "k"); _dev(vt, "vt")
-        p.k[i], p.vt[i], p.ldk[i], p.ldvt[i], p.vt_bs[i], p.Nk[i], p.kv_div[i] = k.data_ptr(), vt.data_ptr(), _ld(k), _ld(vt), vt_bs, nk, div
-    p.zeros = workspace(q.device)[1].data_ptr()
-    code = dt_code(q.dtype)
-    if x3:
-        assert q.dtype == torch.float32, "x3 attention runs on f32 q / k / v^T"
-        code = BF16X3
-    p.B, p.H, p.Nq, p.nseg, p.head_dim, p.dtype, p.scale = B, H, Nq, len(kv), 64, code, scale
-    p.variant = ATTN_VARIANT if variant is None else variant
-    _launch_attention(lib, p)
-    return out
-
-
-def _attention_presplit(lib, q, kv0, *, B, H, Nq, scale, out, variant, split_out):
-    k, vt, nk, div, vt_bs = kv0
-    for t, nm in ((q, "q"), (k, "k"), (vt, "vt")):
-        _dev(t, nm, True)
-        assert t.dtype == torch.bfloat16 and _ld(t) % 2 == 0
-    if out is None:
-        out = new_split(B * Nq, H * 64, q.device) if split_out else torch.empty((B * Nq, H * 64), device=q.device, dtype=torch.float32)
-    split_out = isinstance(out, SplitAct)
-    if split_out:
-        _split_out_ok(out, B * Nq)
-    assert vt_bs % 2 == 0
-    p = Attention()
-    p.q, p.o, p.ldq, p.ldo = q.data_ptr(), out.data_ptr(), _ld(q) // 2, (_ld(out) // 2 if split_out else _ld(out))
-    p.split_out, p.qkv_split = int(split_out), 1
-    p.k[0], p.vt[0], p.ldk[0], p.ldvt[0], p.vt_bs[0], p.Nk[0], p.kv_div[0] = k.data_ptr(), vt.data_ptr(), _ld(k) // 2, _ld(vt) // 2, vt_bs // 2, nk, div
-    p.zeros = workspace(q.device)[1].data_ptr()
-    p.B, p.H, p.Nq, p.nseg, p.head_dim, p.dtype, p.scale = B, H, Nq, 1, 64, BF16X3, scale
-    p.variant = ATTN_VARIANT if variant is None else variant
+    p, out = attention_descriptor(q, kv, B=B, H=H, Nq=Nq, scale=scale, out=out, x3=x3, variant=variant, split_out=split_out, qkv_split=qkv_split)
     _launch_attention(lib, p)
     return out
 

@@ -210,6 +210,18 @@ typedef struct geo4d_attention_t {
                             count 4-byte elements and must be multiples of 8, bases 32-byte aligned, Nk % 8 == 0. Same results, bit
                             for bit, as the raw-f32 inputs (the split is the same arithmetic, done once by the producer). */
 } geo4d_attention_t;
+typedef struct geo4d_attention_plan_t {
+    int kernel;          /* 1 = flash_attn_kernel, 2 = flash_attn2_kernel (skewed query blocks)                                           */
+    int nseg;            /* key/value sets the instantiation is compiled for                                                              */
+    int qb;              /* 32-row query blocks per wave                                                                                  */
+    int occ;             /* waves per SIMD the instantiation is compiled for                                                              */
+    int ps;              /* the instantiation reads pre-split q / k / vt (qkv_split)                                                      */
+    int rows_per_wg;     /* query rows per workgroup: 128 or 256                                                                          */
+    unsigned grid[3];    /* {ceil(Nq / rows_per_wg), H, B} workgroups of 256 threads                                                      */
+    int variant;         /* the `variant` that runs, after defaults and fall-backs: a launch with it set explicitly runs the same kernel  */
+} geo4d_attention_plan_t;
+/* pure host function: validates `p` exactly as geo4d_attention does and says what it would launch */
+int geo4d_attention_plan(const geo4d_attention_t* p, geo4d_attention_plan_t* plan);
 int geo4d_attention(const geo4d_attention_t* p, void* stream);
 
 /* Self-attention over T <= 16 frames for every (batch, pixel, head); tokens stay frame-major [B*T][HW][C].

@@ -186,6 +186,24 @@ def test_attention_cross_two_sets_and_rescale(dev):
     check("attn spike", o1, _sdpa(q1, k1, v1, 0.125), scale=2.0)
 
 
+@pytest.mark.parametrize("N", [248, 256, 1016, 1024])
+def test_attention_default_launch_is_the_planned_one(dev, N, monkeypatch):
+    """ops.attention_plan answers what the default launch runs on pre-split q / k / V^T: below 256 rows the first kernel, from 256 the
+    second at one wave per SIMD, from 1024 at two; the default (variant 0) is bit-equal to a launch that names the plan's variant."""
+    from geo4d_amd import ops, pack
+    monkeypatch.setattr(ops, "ATTN_VARIANT", 0)
+    q, k, v = rnd((N, 64), dev, 36), rnd((N, 64), dev, 37), rnd((N, 64), dev, 38)
+    qs, ks, vs = (ops.SplitAct.wrap(pack.split_bf16(t)) for t in (q, k, v.t().contiguous()))
+    args, kw = (qs, [(ks, vs, N, 1, 64 * 2 * N)]), dict(B=1, H=1, Nq=N, scale=0.125, x3=True, qkv_split=True)
+    plan = ops.attention_plan(ops.attention_descriptor(*args, **kw)[0])
+    want = (1, 1, 1, 1, 128) if N < 256 else (2, 4, 2, 1, 256) if N < 1024 else (2, 5, 2, 2, 256)
+    assert (plan.kernel, plan.variant, plan.qb, plan.occ, plan.rows_per_wg) == want and plan.ps == 1
+    assert tuple(plan.grid) == ((N + want[4] - 1) // want[4], 1, 1)
+    out = ops.attention(*args, **kw)
+    assert torch.equal(out, ops.attention(*args, variant=plan.variant, **kw))
+    check(f"attn planned N={N}", out, _sdpa(q, k, v, 0.125), scale=2.0)
+
+
 def test_x3_kernels_are_deterministic_on_a_full_chip(dev):
     """Same race screen as tests/test_kernels_gpu.py::test_lds_dma_pipelines_are_race_free, for the x3 instantiations."""
     from geo4d_amd import ops, pack

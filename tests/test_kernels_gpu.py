@@ -304,6 +304,38 @@ def test_attention_online_softmax_rescale(dev, dtype):
         check("attn spike (variant 4)", out, _sdpa(q.float(), k.float(), v.float(), 0.125), dtype, scale=2.0)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("N", [248, 256])
+def test_attention_default_launch_is_the_planned_one(dev, dtype, N, monkeypatch):
+    """ops.attention_plan answers what the default launch runs: on both sides of the 256-row threshold between the two flash kernels the
+    default (variant 0) is bit-equal to a launch that names the plan's variant."""
+    from geo4d_amd import ops
+    monkeypatch.setattr(ops, "ATTN_VARIANT", 0)
+    q, k, v = rnd((N, 64), dev, dtype, 36), rnd((N, 64), dev, dtype, 37), rnd((N, 64), dev, dtype, 38)
+    args, kw = (q, [(k, _vt(v, 1, N), N, 1, N)]), dict(B=1, H=1, Nq=N, scale=0.125)
+    plan = ops.attention_plan(ops.attention_descriptor(*args, **kw)[0])
+    assert (plan.kernel, plan.variant, plan.qb, plan.occ, plan.rows_per_wg, tuple(plan.grid)) == ((1, 3, 2, 2, 256, (1, 1, 1)) if N < 256 else (2, 4, 2, 2, 256, (1, 1, 1)))
+    out = ops.attention(*args, **kw)
+    assert torch.equal(out, ops.attention(*args, variant=plan.variant, **kw))
+    check(f"attn planned N={N}", out, _sdpa(q.float(), k.float(), v.float(), 0.125), dtype, scale=2.0)
+
+
+def test_attention_default_launch_is_the_planned_one_two_sets(dev, monkeypatch):
+    """The same for dual-KV cross attention (77 + 16 keys), which stays on the first kernel with one query block per wave at any Nq."""
+    from geo4d_amd import ops
+    monkeypatch.setattr(ops, "ATTN_VARIANT", 0)
+    dtype, N = torch.bfloat16, 256
+    q = rnd((N, 64), dev, dtype, 31)
+    kt, vt, ki, vi = (rnd((n, 64), dev, dtype, 32 + i) for i, n in enumerate((77, 77, 16, 16)))
+    args, kw = (q, [(kt, _vt(vt, 1, 77, pad=80), 77, 1, 64 * 80), (ki, _vt(vi, 1, 16), 16, 1, 16)]), dict(B=1, H=1, Nq=N, scale=0.125)
+    plan = ops.attention_plan(ops.attention_descriptor(*args, **kw)[0])
+    assert (plan.kernel, plan.nseg, plan.variant, plan.qb, plan.occ, plan.rows_per_wg, tuple(plan.grid)) == (1, 2, 1, 1, 1, 128, (2, 1, 1))
+    out = ops.attention(*args, **kw)
+    assert torch.equal(out, ops.attention(*args, variant=plan.variant, **kw))
+    ref = _sdpa(q.float(), kt.float(), vt.float(), 0.125) + _sdpa(q.float(), ki.float(), vi.float(), 0.125)
+    check("attn planned cross", out, ref, dtype, scale=2.0)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("T", [16, 5])
 def test_temporal_attention(dev, dtype, T):

@@ -12,8 +12,8 @@ for name in (sys.argv[1:] or ["bf16"]):
     passes = 3 if x3 else 1
     for variant in (1, 2, 3, 4, "1ps", "3ps", "4ps", "5ps"):
         ps = isinstance(variant, str)                  # bf16x3 only: q | k and V^T in the producers' pre-split format (qkv_split, round 4)
-        if (variant == 2 and dt == torch.float32) or (ps and not x3) or (variant == 4 and dt == torch.float32):
-            continue                                   # 4 / 5 = flash_attn2_kernel (round 4): 16-bit types and pre-split bf16x3 only
+        if ps and not x3:
+            continue
         vnum = int(variant[0]) if ps else variant
         tot_ms = 0
         for F_, H, N, cnt in LEVELS:
@@ -23,9 +23,17 @@ for name in (sys.argv[1:] or ["bf16"]):
             if ps:
                 from geo4d_amd import pack
                 qs, vs = ops.SplitAct.wrap(pack.split_bf16(qk)), ops.SplitAct.wrap(pack.split_bf16(vt))
-                fn = lambda: ops.attention(qs[:, :2 * C_], [(qs[:, 2 * C_:], vs, N, 1, C_ * 2 * N)], B=F_, H=H, Nq=N, scale=0.125, x3=True, variant=vnum, qkv_split=True)
+                args = (qs[:, :2 * C_], [(qs[:, 2 * C_:], vs, N, 1, C_ * 2 * N)])
             else:
-                fn = lambda: ops.attention(qk[:, :C_], [(qk[:, C_:], vt, N, 1, C_ * N)], B=F_, H=H, Nq=N, scale=0.125, x3=x3, variant=variant)
+                args = (qk[:, :C_], [(qk[:, C_:], vt, N, 1, C_ * N)])
+            kw = dict(B=F_, H=H, Nq=N, scale=0.125, x3=x3, variant=vnum, qkv_split=ps)
+            try:                                       # the library's own plan says whether this (dtype, variant, pre-split) is built
+                plan = ops.attention_plan(ops.attention_descriptor(*args, **kw)[0])
+            except RuntimeError:
+                break
+            if plan.variant != vnum:                   # a fall-back to another variant's build: measured under that variant's own name
+                break
+            fn = lambda: ops.attention(*args, **kw)
             for _ in range(3): fn()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -34,5 +42,6 @@ for name in (sys.argv[1:] or ["bf16"]):
             us = e0.elapsed_time(e1) * 1e3 / 20
             fl = 4.0 * F_ * H * N * N * 64
             tot_ms += us * cnt / 1e3
-            print(f"{name} v{variant} self-attn F*H={F_*H:4d} N={N:5d}: {us:8.1f} us  {fl/us/1e6:7.1f} algorithmic TF/s  ({passes*fl/us/1e6/2500*100:4.1f}% of bf16 MFMA peak issued)  x{cnt}")
-        print(f"{name} v{variant}: spatial self-attention per U-Net forward: {tot_ms:.2f} ms", flush=True)
+            print(f"{name} v{variant} self-attn F*H={F_*H:4d} N={N:5d}: {us:8.1f} us  {fl/us/1e6:7.1f} algorithmic TF/s  ({passes*fl/us/1e6/2500*100:4.1f}% of bf16 MFMA peak issued)  x{cnt}  kernel {plan.kernel} qb {plan.qb} occ {plan.occ}")
+        else:
+            print(f"{name} v{variant}: spatial self-attention per U-Net forward: {tot_ms:.2f} ms", flush=True)
