@@ -41,6 +41,16 @@ class ConvGemm(C.Structure):
     ]
 
 
+class ConvGemmPlan(C.Structure):
+    _fields_ = [("tile_hint", C.c_int), ("generation", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("wm", C.c_int), ("wn", C.c_int),
+                ("splits", C.c_int), ("hot", C.c_int), ("osplit", C.c_int), ("colsum_rows", C.c_int)]
+
+
+class ConvGemmTile(C.Structure):
+    _fields_ = [("tile_hint", C.c_int), ("generation", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("wm", C.c_int), ("wn", C.c_int),
+                ("geglu", C.c_int)]
+
+
 class GroupNorm(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -118,6 +128,8 @@ class AlignSmall(C.Structure):
 # name -> (restype, argtypes); checked against include/geo4d_hip.h by tests/test_host_logic.py::test_c_abi_exports_every_declared_symbol
 SIGNATURES = {
     "geo4d_conv_gemm": (C.c_int, [C.POINTER(ConvGemm), C.c_void_p]),
+    "geo4d_conv_gemm_plan": (C.c_int, [C.POINTER(ConvGemm), C.POINTER(ConvGemmPlan)]),
+    "geo4d_conv_gemm_tiles": (C.c_int, [C.POINTER(ConvGemmTile), C.c_int]),
     "geo4d_conv_gemm_colsum_rows": (C.c_int, [C.POINTER(ConvGemm)]),
     "geo4d_groupnorm_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "geo4d_groupnorm": (C.c_int, [C.POINTER(GroupNorm), C.c_void_p]),
@@ -240,4 +252,4 @@ def load():
 def check(rc, what):
     if rc != 0:
         msg = load().geo4d_last_error()
-        raise RuntimeError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+        raise Geo4DNativeError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")

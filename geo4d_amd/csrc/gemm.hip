@@ -14,10 +14,10 @@
 // Activations are channels-last tokens [F, H*W, C]; weights are packed [N][taps*Cin] (K-major, tap-major).
 // out[m][n] = epilogue(alpha * sum_k A_gather[m][k] * W[n][k])
 //
-// Host side: this file validates the descriptor, gemm_plan.h resolves it - ONE tile table (every hint of the three kernel generations:
-// gemm_kernel.h, gemm_kernel_v2.h, gemm_kernel_v3.h) and ONE function, resolve(), that applies defaults, redirects, fall-backs, split-K,
-// the operand-layout variant and the gn_colsum granularity - and the generation's translation unit launches the plan's tile.
-// geo4d_conv_gemm_colsum_rows answers from the same plan.
+// Host side: gemm_plan.h validates the descriptor and resolves it - ONE tile table (every hint of the three kernel generations:
+// gemm_kernel.h, gemm_kernel_v2.h, gemm_kernel_v3.h), validate() and ONE function, resolve(), that applies defaults, redirects, fall-backs,
+// split-K, the operand-layout variant and the gn_colsum granularity - and the generation's translation unit launches the plan's tile.
+// geo4d_conv_gemm_plan, geo4d_conv_gemm_tiles and geo4d_conv_gemm_colsum_rows answer from the same plan and table.
 //
 // Structure of the first-generation kernel (template in gemm_kernel.h; 4, 5, 8 or 10 waves, tile BM x BN x 128 B of K per stage; tiles
 // 128x128, 128x64, 64x128, 64x64, 128x32, 256x128, 256x256, 160x320, 160x160 picked per problem by the host's measured table):
@@ -63,54 +63,25 @@ static int launch_v23(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t 
 }  // namespace geo4d_gemm
 using namespace geo4d_gemm;
 
+static_assert(MAX_TAPS == MAXTAP, "gemm_plan.h validates the tap count the kernels' gather tables hold");
+
+// validate + resolve: the one path to a plan, for the query and for the launch
+static int conv_gemm_plan(const geo4d_conv_gemm_t* p, Plan& plan) {
+    if (!p) return GEO4D_EINVAL;
+    const char* error = validate(*p);
+    if (!error) {
+        plan = resolve(*p);
+        error = plan.error;
+    }
+    if (error) geo4d_set_error(error);
+    return error ? GEO4D_EINVAL : GEO4D_OK;
+}
+
 extern "C" int geo4d_conv_gemm(const geo4d_conv_gemm_t* pp, void* stream) {
-    if (!pp) return GEO4D_EINVAL;
+    Plan plan;
+    const int rc = conv_gemm_plan(pp, plan);
+    if (rc != GEO4D_OK) return rc;
     const geo4d_conv_gemm_t& p = *pp;
-    const int esz = (p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3 || p.dtype == GEO4D_F16X2) ? 4 : 2;
-    const int bk = KSLAB_BYTES / esz;
-    if (p.dtype < 0 || p.dtype > 4 || p.out_dtype < 0 || p.out_dtype > 2) { geo4d_set_error("conv_gemm: bad dtype"); return GEO4D_EINVAL; }
-    if (p.dtype != GEO4D_BF16X3 && p.dtype != GEO4D_F16X2 && (p.a_split || p.w_split)) { geo4d_set_error("conv_gemm: a_split / w_split are bf16x3 / f16x2 (dtype 3 / 4) options"); return GEO4D_EINVAL; }
-    // two-pass f16: plain f16 activation rows x a pre-split f16 weight, f32 rows (or, o_split = 2, plain f16 rows) out, second / third
-    // generation tiles (0 = a default per shape)
-    if (p.dtype == GEO4D_F16X2 && (p.a_split != 2 || !p.w_split || (p.o_split != 0 && p.o_split != 2) || p.out_nchw || p.out_dtype != GEO4D_F32 || (p.tile_hint != 0 && generation(p.tile_hint) == 1))) {
-        geo4d_set_error("conv_gemm: f16x2 (dtype 4) needs a_split = 2 (plain f16 activation rows) and w_split, a row-major output (f32 rows, or o_split = 2: plain f16 rows), and tile hint 0 or >= 22");
-        return GEO4D_EINVAL;
-    }
-    if (p.o_split) {
-        const int nst = p.act == 2 ? p.N / 2 : p.N;
-        if ((p.dtype != GEO4D_BF16X3 && p.dtype != GEO4D_F16X2) || (p.dtype == GEO4D_BF16X3 && p.o_split != 1) || p.out_dtype != GEO4D_F32 || !p.a_split || !p.w_split || p.split_k > 1 || p.out_nchw || p.gn_colsum ||
-            (nst % 8) || (p.ldo % 8) || (p.o_bs % 8) || ((uintptr_t)p.O % (p.o_split == 2 ? 16 : 32))) {
-            geo4d_set_error("conv_gemm: o_split needs a pre-split x pre-split bf16x3 launch, f32 row-major output, stored columns % 8 == 0, 32-byte aligned rows, no split-K");
-            return GEO4D_EINVAL;
-        }
-    }
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.batch <= 0) { geo4d_set_error("conv_gemm: empty problem"); return GEO4D_EINVAL; }
-    if (p.KT <= 0 || p.KH <= 0 || p.KW <= 0 || p.KT * p.KH * p.KW > MAXTAP) { geo4d_set_error("conv_gemm: at most 9 taps"); return GEO4D_EINVAL; }
-    if (p.Cin % bk || p.K != p.Cin * p.KT * p.KH * p.KW) { geo4d_set_error("conv_gemm: Cin must be a multiple of the 128-byte K slab and K = taps*Cin"); return GEO4D_EINVAL; }
-    const int esz_a = p.dtype == GEO4D_F16X2 ? 2 : esz;      // (dtype 4: the activation is plain f16 rows)
-    if ((p.lda * esz_a) % 16 || (p.ldw * esz) % 16 || ((uintptr_t)p.A % 16) || ((uintptr_t)p.W % 16) || (p.a_bs * esz_a) % 16 || (p.w_bs * esz) % 16) {
-        geo4d_set_error("conv_gemm: operands must be 16-byte aligned");
-        return GEO4D_EINVAL;
-    }
-    if (p.T <= 0 || p.Hout <= 0 || p.Wout <= 0 || p.Hin <= 0 || p.Win <= 0 || p.M % (p.Hout * p.Wout)) { geo4d_set_error("conv_gemm: bad geometry"); return GEO4D_EINVAL; }
-    if ((p.M / (p.Hout * p.Wout)) % p.T) { geo4d_set_error("conv_gemm: frames not a multiple of T"); return GEO4D_EINVAL; }
-    if ((long)(p.M / (p.Hout * p.Wout)) * p.Hin * p.Win > 2147483647L) { geo4d_set_error("conv_gemm: more than 2^31 input pixels"); return GEO4D_EINVAL; }
-    if (p.ups != 1 && p.ups != 2) { geo4d_set_error("conv_gemm: ups must be 1 or 2"); return GEO4D_EINVAL; }
-    if (p.act == 2 && (p.N % 64 || p.out_nchw || p.R)) { geo4d_set_error("conv_gemm: GEGLU needs N % 64 == 0, row-major output, no residual"); return GEO4D_EINVAL; }
-    if (p.act < 0 || p.act > 3) { geo4d_set_error("conv_gemm: act must be 0 (none), 1 (SiLU), 2 (GEGLU) or 3 (GELU)"); return GEO4D_EINVAL; }
-    if (p.act == 3) {   // GELU lives in the vectorised epilogue only (the scalar NCTHW / odd-shape path stays small enough to unroll)
-        const int oesz = p.out_dtype == GEO4D_F32 ? 4 : 2;
-        if (p.out_nchw || p.R || (p.N % 8) || ((p.ldo * oesz) % 16) || ((uintptr_t)p.O % 16) || ((p.o_bs * oesz) % 16)) {
-            geo4d_set_error("conv_gemm: GELU needs a row-major output with N % 8 == 0, 16-byte aligned rows and no residual");
-            return GEO4D_EINVAL;
-        }
-    }
-    if (p.rowbias && p.rowbias_div <= 0) { geo4d_set_error("conv_gemm: rowbias_div"); return GEO4D_EINVAL; }
-    if (p.batch > 65535) { geo4d_set_error("conv_gemm: batch too large"); return GEO4D_EINVAL; }
-    if (!p.zeros || ((uintptr_t)p.zeros % 16)) { geo4d_set_error("conv_gemm: `zeros` must point at 16 zero bytes (16-byte aligned) in device memory"); return GEO4D_EINVAL; }
-    if (p.workspace && ((uintptr_t)p.workspace % 16)) { geo4d_set_error("conv_gemm: workspace alignment"); return GEO4D_EINVAL; }
-    const Plan plan = resolve(p);
-    if (plan.error) { geo4d_set_error(plan.error); return GEO4D_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const bool gen1 = generation(plan.hint) == 1;
     switch (p.dtype) {
@@ -122,10 +93,27 @@ extern "C" int geo4d_conv_gemm(const geo4d_conv_gemm_t* pp, void* stream) {
     }
 }
 
-// Rows of the output that ONE gn_colsum entry of the launch `*pp` describes covers (tile_hint / split_k as they will be launched;
-// the gn_colsum field itself is ignored): 32 for the first-generation tiles, the wave tile's rows for the second / third generation,
-// 0 = this launch cannot emit the sums or would be refused (the caller then leaves gn_colsum null and the GroupNorm runs its own
-// statistics pass). The answer is the launch's own plan.
+extern "C" int geo4d_conv_gemm_plan(const geo4d_conv_gemm_t* pp, geo4d_conv_gemm_plan_t* out) {
+    Plan plan;
+    if (!out) return GEO4D_EINVAL;
+    const int rc = conv_gemm_plan(pp, plan);
+    if (rc != GEO4D_OK) return rc;
+    const Tile& t = *find_tile(plan.hint);
+    *out = {t.hint, generation(t.hint), t.bm, t.bn, t.wm, t.wn, plan.splits, plan.hot, plan.osplit, plan.colsum_rows};
+    return GEO4D_OK;
+}
+
+extern "C" int geo4d_conv_gemm_tiles(geo4d_conv_gemm_tile_t* out, int cap) {
+    int n = 0;
+    for (const Tile& t : TILES) {
+        if (out && n < cap) out[n] = {t.hint, generation(t.hint), t.bm, t.bn, t.wm, t.wn, t.geglu()};
+        ++n;
+    }
+    return n;
+}
+
+// The colsum_rows of the launch's own plan WITHOUT the descriptor checks (see geo4d_hip.h): 0 = this launch cannot emit the sums or
+// resolve() refuses it (the caller then leaves gn_colsum null and the GroupNorm runs its own statistics pass).
 extern "C" int geo4d_conv_gemm_colsum_rows(const geo4d_conv_gemm_t* pp) {
     if (!pp || pp->Hout <= 0 || pp->Wout <= 0) return 0;      // (the plan divides by a frame's rows)
     return resolve(*pp).colsum_rows;

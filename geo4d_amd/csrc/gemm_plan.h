@@ -1,6 +1,7 @@
-// geo4d_amd/csrc/gemm_plan.h — the host-side planner of geo4d_conv_gemm: ONE tile table and ONE function, resolve(), that turns a
-// launch descriptor into the kernel variant that runs it. geo4d_conv_gemm launches what the plan says, geo4d_conv_gemm_colsum_rows
-// answers from the same plan, so the two cannot disagree. Host code only: no HIP call, no allocation, no device code.
+// geo4d_amd/csrc/gemm_plan.h — the host-side planner of geo4d_conv_gemm: ONE tile table, validate() with the descriptor checks and ONE
+// function, resolve(), that turns a (validated) launch descriptor into the kernel variant that runs it. geo4d_conv_gemm launches what the
+// plan says, geo4d_conv_gemm_plan and geo4d_conv_gemm_colsum_rows answer from the same plan, so they cannot disagree. Host code only: no
+// HIP call, no allocation, no device code. Include after common.h (dtype and return codes).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -9,6 +10,7 @@
 namespace geo4d_gemm {
 
 constexpr int KSLAB_BYTES = 128;      // K bytes per operand row and pipeline stage (8 x 16-byte chunks) in every generation
+constexpr int MAX_TAPS = 9;           // KT x KH x KW at most: a row of the kernels' gather tables (their MAXTAP; gemm.hip asserts the two agree)
 
 // The hint number space: first generation (gemm_kernel.h) below 21, second (gemm_kernel_v2.h) 21..70, third (gemm_kernel_v3.h) from 71.
 constexpr int generation(int hint) { return hint >= 71 ? 3 : hint >= 21 ? 2 : 1; }
@@ -149,6 +151,47 @@ inline bool score_tiles(const geo4d_conv_gemm_t& p, int nslab, int& hint, int& s
     hint = TILES[best].hint;
     splits = best_split;
     return true;
+}
+
+// The descriptor checks of geo4d_conv_gemm, in the order they have always been made (callers match on the messages): the message of the
+// first one that fails, or nullptr. Every refusal, here and in resolve(), returns GEO4D_EINVAL.
+inline const char* validate(const geo4d_conv_gemm_t& p) {
+    const int esz = (p.dtype == GEO4D_F32 || p.dtype == GEO4D_BF16X3 || p.dtype == GEO4D_F16X2) ? 4 : 2;
+    const int bk = KSLAB_BYTES / esz;
+    if (p.dtype < 0 || p.dtype > 4 || p.out_dtype < 0 || p.out_dtype > 2) return "conv_gemm: bad dtype";
+    if (p.dtype != GEO4D_BF16X3 && p.dtype != GEO4D_F16X2 && (p.a_split || p.w_split)) return "conv_gemm: a_split / w_split are bf16x3 / f16x2 (dtype 3 / 4) options";
+    // two-pass f16: plain f16 activation rows x a pre-split f16 weight, f32 rows (or, o_split = 2, plain f16 rows) out, second / third
+    // generation tiles (0 = a default per shape)
+    if (p.dtype == GEO4D_F16X2 && (p.a_split != 2 || !p.w_split || (p.o_split != 0 && p.o_split != 2) || p.out_nchw || p.out_dtype != GEO4D_F32 || (p.tile_hint != 0 && generation(p.tile_hint) == 1)))
+        return "conv_gemm: f16x2 (dtype 4) needs a_split = 2 (plain f16 activation rows) and w_split, a row-major output (f32 rows, or o_split = 2: plain f16 rows), and tile hint 0 or >= 22";
+    if (p.o_split) {
+        const int nst = p.act == 2 ? p.N / 2 : p.N;
+        if ((p.dtype != GEO4D_BF16X3 && p.dtype != GEO4D_F16X2) || (p.dtype == GEO4D_BF16X3 && p.o_split != 1) || p.out_dtype != GEO4D_F32 || !p.a_split || !p.w_split || p.split_k > 1 || p.out_nchw || p.gn_colsum ||
+            (nst % 8) || (p.ldo % 8) || (p.o_bs % 8) || ((uintptr_t)p.O % (p.o_split == 2 ? 16 : 32)))
+            return "conv_gemm: o_split needs a pre-split x pre-split bf16x3 launch, f32 row-major output, stored columns % 8 == 0, 32-byte aligned rows, no split-K";
+    }
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.batch <= 0) return "conv_gemm: empty problem";
+    if (p.KT <= 0 || p.KH <= 0 || p.KW <= 0 || p.KT * p.KH * p.KW > MAX_TAPS) return "conv_gemm: at most 9 taps";
+    if (p.Cin % bk || p.K != p.Cin * p.KT * p.KH * p.KW) return "conv_gemm: Cin must be a multiple of the 128-byte K slab and K = taps*Cin";
+    const int esz_a = p.dtype == GEO4D_F16X2 ? 2 : esz;      // (dtype 4: the activation is plain f16 rows)
+    if ((p.lda * esz_a) % 16 || (p.ldw * esz) % 16 || ((uintptr_t)p.A % 16) || ((uintptr_t)p.W % 16) || (p.a_bs * esz_a) % 16 || (p.w_bs * esz) % 16)
+        return "conv_gemm: operands must be 16-byte aligned";
+    if (p.T <= 0 || p.Hout <= 0 || p.Wout <= 0 || p.Hin <= 0 || p.Win <= 0 || p.M % (p.Hout * p.Wout)) return "conv_gemm: bad geometry";
+    if ((p.M / (p.Hout * p.Wout)) % p.T) return "conv_gemm: frames not a multiple of T";
+    if ((long)(p.M / (p.Hout * p.Wout)) * p.Hin * p.Win > 2147483647L) return "conv_gemm: more than 2^31 input pixels";
+    if (p.ups != 1 && p.ups != 2) return "conv_gemm: ups must be 1 or 2";
+    if (p.act == 2 && (p.N % 64 || p.out_nchw || p.R)) return "conv_gemm: GEGLU needs N % 64 == 0, row-major output, no residual";
+    if (p.act < 0 || p.act > 3) return "conv_gemm: act must be 0 (none), 1 (SiLU), 2 (GEGLU) or 3 (GELU)";
+    if (p.act == 3) {   // GELU lives in the vectorised epilogue only (the scalar NCTHW / odd-shape path stays small enough to unroll)
+        const int oesz = p.out_dtype == GEO4D_F32 ? 4 : 2;
+        if (p.out_nchw || p.R || (p.N % 8) || ((p.ldo * oesz) % 16) || ((uintptr_t)p.O % 16) || ((p.o_bs * oesz) % 16))
+            return "conv_gemm: GELU needs a row-major output with N % 8 == 0, 16-byte aligned rows and no residual";
+    }
+    if (p.rowbias && p.rowbias_div <= 0) return "conv_gemm: rowbias_div";
+    if (p.batch > 65535) return "conv_gemm: batch too large";
+    if (!p.zeros || ((uintptr_t)p.zeros % 16)) return "conv_gemm: `zeros` must point at 16 zero bytes (16-byte aligned) in device memory";
+    if (p.workspace && ((uintptr_t)p.workspace % 16)) return "conv_gemm: workspace alignment";
+    return nullptr;
 }
 
 // The kernel variant the (validated) descriptor `p` becomes, or why it cannot run. The gn_colsum pointer only decides whether a launch

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, AttentionPlan, ConvGemm, GroupNorm2, GroupNormPlan
+from ._lib import BF16, BF16X3, F16, F16X2, F32, Attention, AttentionPlan, ConvGemm, ConvGemmPlan, ConvGemmTile, GroupNorm2, GroupNormPlan
 from .precision import resolve as _resolve_precision
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -168,26 +168,31 @@ _CANDIDATES = [(1, 1), (2, 1), (3, 1), (4, 1), (11, 1), (13, 1), (16, 1), (17, 1
                # Splits that do not divide the K slabs evenly run on the second-generation twin inside the library.
                (71, 1), (72, 1), (73, 1), (74, 1), (71, 2), (72, 2), (73, 2), (74, 2), (71, 3), (72, 3), (73, 3), (74, 3), (71, 4), (73, 4), (74, 4),
                (71, 5), (73, 5), (74, 5), (73, 6), (74, 6), (73, 8), (74, 8), (73, 10), (74, 10)]
-# One row per tile hint of the library (include/geo4d_hip.h; the library's own table is csrc/gemm_plan.h): hint -> (kernel generation,
-# the nearest tile whose wave tiles are a multiple of 64 columns wide - where a GEGLU that writes f16 rows goes; itself if it is one or
-# the generation has no such launch)
-_TILES = {1: (1, 1), 2: (1, 2), 3: (1, 3), 4: (1, 4), 5: (1, 5), 11: (1, 11), 13: (1, 13), 16: (1, 16), 17: (1, 17),
-          22: (2, 25), 23: (2, 25), 25: (2, 25), 27: (2, 27), 28: (2, 27),
-          71: (3, 71), 72: (3, 71), 73: (3, 74), 74: (3, 74)}
-assert {t for t, _ in _CANDIDATES} == set(_TILES)
-_VALID_HINTS = set(_TILES) | {0}
+_TILE_ROWS = None
+
+
+def _tiles():
+    """{tile hint: its row (_lib.ConvGemmTile) of the library's tile table (csrc/gemm_plan.h)}, read once, on first use: importing this
+    module does not load the library."""
+    global _TILE_ROWS
+    if _TILE_ROWS is None:
+        rows = (ConvGemmTile * 64)()
+        n = _lib.load().geo4d_conv_gemm_tiles(rows, len(rows))
+        _TILE_ROWS = {t.tile_hint: t for t in rows[:n]}
+        assert {t for t, _ in _CANDIDATES} == set(_TILE_ROWS)
+    return _TILE_ROWS
 
 
 def _generation(tile_hint):
     """1, 2 or 3; hint 0 (the library's own choice) and hints without a row count as the first generation."""
-    return _TILES.get(tile_hint, (1, tile_hint))[0]
+    t = _tiles().get(tile_hint)
+    return t.generation if t is not None else 1
 
 
+# GEO4D_AUTOTUNE=0: shapes missing from the tuning table run on the library's own tile choice instead of being measured on first eager use
 AUTOTUNE = _os.environ.get("GEO4D_AUTOTUNE", "1") != "0"
-# GEMM epilogues can emit the next GroupNorm's column sums (gn_stats=True call sites), which removes that GroupNorm's statistics pass
-# over the tensor. 1 (default since round 4): where the second / third generation's fast epilogue does it per wave-tile row range at
-# ~0.3 us per tile (f32 rows, i.e. the bf16x3 mode: same-box A/B +1.2 % frames/s, decode -2.5 %, profiles/r04_gn_fused_stats.md);
-# 2: also on the first-generation tiles (round 2: measured slower there: -3.5 % bf16x3, -7 % bf16); 0: off.
+
+
 def _env_level(name, default):
     """0 / 1 / 2 ... or the usual words: off / false / no -> 0, on / true / yes (and anything else that is not a number) -> 1."""
     v = _os.environ.get(name)
@@ -200,17 +205,36 @@ def _env_level(name, default):
         return 0 if v in ("off", "false", "no", "none") else 1
 
 
+# GEMM epilogues can emit the next GroupNorm's column sums (gn_stats=True call sites), which removes that GroupNorm's statistics pass
+# over the tensor. 1 (default since round 4): where the second / third generation's fast epilogue does it per wave-tile row range at
+# ~0.3 us per tile (f32 rows, i.e. the bf16x3 mode: same-box A/B +1.2 % frames/s, decode -2.5 %, profiles/r04_gn_fused_stats.md);
+# 2: also on the first-generation tiles (round 2: measured slower there: -3.5 % bf16x3, -7 % bf16); 0: off.
 GN_FUSED_STATS = _env_level("GEO4D_GN_FUSED", 1)
-GN_ONE_LAUNCH = _env_level("GEO4D_GN_ONE_LAUNCH", 1)     # 0: a GroupNorm with producer sums runs gn_finalize_cols + gn_apply and a concatenated input its own statistics pass (the launch sequence before the fused / sliced forms); 3 / 4: force _lib.GN_PATH_FUSED / GN_PATH_SLICED (tests, tools/norm_bench.py)
+# 0: a GroupNorm with producer sums runs gn_finalize_cols + gn_apply and a concatenated input its own statistics pass (the launch
+# sequence before the fused / sliced forms); 3 / 4: force _lib.GN_PATH_FUSED / GN_PATH_SLICED (tests, tools/norm_bench.py)
+GN_ONE_LAUNCH = _env_level("GEO4D_GN_ONE_LAUNCH", 1)
 GN_TUNE = (0.0, 0)     # tools/norm_bench.py: (fuse_fraction, min_workgroups) overrides of the library's defaults; 0 = default
-SPLITK_COLSUM = _env_level("GEO4D_SPLITK_COLSUM", 1)     # 0: split-K launches leave the GroupNorm statistics to the GroupNorm (the state before round 6)
-TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)     # tools/tune_gemm.py: measure a pre-split launch under its OWN key instead of borrowing the raw-activation entry of the same shape
-TUNE_LOG = []          # (key, chosen (tile, split), ms per launch, finalists) of every shape autotuned in this process (tools/tune_gemm.py prints it)
+# 0: split-K launches leave the GroupNorm statistics to the GroupNorm (the state before round 6, when their reduce launch learned to emit the sums)
+SPLITK_COLSUM = _env_level("GEO4D_SPLITK_COLSUM", 1)
+# tools/tune_gemm.py: measure a pre-split launch under its OWN key instead of borrowing the raw-activation entry of the same shape
+TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)
+# (key, chosen (tile, split), ms per launch, finalists) of every shape autotuned in this process (tools/tune_gemm.py prints it)
+TUNE_LOG = []
 DEBUG_ABLATE = _env_level("GEO4D_DEBUG_ABLATE", 0)       # tests / A-B runs: 2 = three persistent workgroups; 16 + g = tile order with GROUP_M = g (17 = column-fastest)
 GEMM_TIMELINE = None   # set to a list to have conv_gemm bracket every launch with HIP events: (flops, start, end, MFMA passes per product)
 ATTN_TIMELINE = None   # the same for the spatial self-attention launches (one key/value set) of ops.attention
 SAT_COUNTER = None     # debug: an int64 [1] device tensor -> every f16-clamping store (GroupNorm / LayerNorm / GEGLU epilogue writing the two-pass
                        # GEMM's f16 operand) adds the lanes it clamped (|x| > 65504); tests assert 0 at full size. None in production.
+
+
+def _on_timeline(timeline, launch, flops, passes):
+    """bench.py's per-launch HIP-event timelines (GEMM_TIMELINE / ATTN_TIMELINE; never on while capturing): run `launch()` between two
+    events and append (flops, start, end, MFMAs issued per product)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    timeline.append((flops, e0, e1, passes))
 
 
 def _tune_table():
@@ -219,7 +243,7 @@ def _tune_table():
         _TUNE = {}
         if _os.path.exists(_TUNE_PATH):
             with open(_TUNE_PATH) as f:
-                _TUNE = {k: tuple(v) for k, v in _json.load(f).items() if v[0] in _VALID_HINTS}     # (entries naming a retired tile hint are re-tuned)
+                _TUNE = {k: tuple(v) for k, v in _json.load(f).items() if v[0] == 0 or v[0] in _tiles()}     # (entries naming a retired tile hint are re-tuned)
     return _TUNE
 
 
@@ -238,16 +262,18 @@ def _time_launches(launch, tile, split, n):
     return e0.elapsed_time(e1) / n
 
 
-def _autotune(launch, key):
+def _autotune(launch, key, takes):
     """Two stages (round 4: a single 3-launch sample per candidate mis-ranked candidates that differ by 30-40 % when re-measured in
-    isolation, profiles/r04_gemm_retune.md): (1) every candidate, 4 launches after a warm-up; (2) the 6 fastest re-measured in three
-    interleaved rounds of 12 launches, ranked by their best round (the chip's clock moves under load: the minimum is the least noisy
-    estimate of what a launch costs inside a replayed graph)."""
+    isolation, profiles/r04_gemm_retune.md): (1) every candidate the plan accepts (`takes(tile, split)`), 4 launches after a warm-up;
+    (2) the 6 fastest re-measured in three interleaved rounds of 12 launches, ranked by their best round (the chip's clock moves under
+    load: the minimum is the least noisy estimate of what a launch costs inside a replayed graph)."""
     stage1 = []
     for tile, split in _CANDIDATES:
+        if not takes(tile, split):
+            continue
         try:
             launch(tile, split)
-        except RuntimeError:
+        except RuntimeError:       # (a launch error of an accepted plan: the launchers can return GEO4D_EIO)
             continue
         stage1.append((_time_launches(launch, tile, split, 4), tile, split))
     if not stage1:
@@ -288,11 +314,15 @@ def _tuned_config(table, key, code, a_split, w_split, o_split, may_measure):
     return cfg
 
 
+# the nearest tile of the same generation that takes a GEGLU (wave tiles a multiple of 64 columns wide); a hint maps to itself unless listed
+_GEGLU_NEIGHBOUR = {22: 25, 23: 25, 28: 27, 72: 71, 73: 74}
+
+
 def _f16_rows_config(cfg, act):
     """The f16-row epilogue (o_split = 2) has no split-K, and its GEGLU form lives on the tiles whose wave tiles are a multiple of 64
     columns wide: a tile measured on, or borrowed from, another launch goes to its nearest such neighbour."""
     tile_hint, split_k = cfg
-    return (_TILES.get(tile_hint, (1, tile_hint))[1] if act == 2 else tile_hint), min(split_k, 1)
+    return (_GEGLU_NEIGHBOUR.get(tile_hint, tile_hint) if act == 2 else tile_hint), min(split_k, 1)
 
 
 def workspace(device):
@@ -304,18 +334,14 @@ def workspace(device):
     return ws
 
 
-def conv_gemm(a, w, out, *, M, N, K, Cin, lda, ldw, ldo, T=1, Hin=1, Win=1, Hout=1, Wout=1, KT=1, KH=1, KW=1,
-              pt=0, ph=0, pw=0, stride=1, ups=1, bias=None, bias_per_row=False, rowbias=None, rowbias_div=0,
-              residual=None, ldr=0, act=0, out_nchw=False, alpha=1.0, batch=1, a_bs=0, w_bs=0, o_bs=0, r_bs=0,
-              tile_hint=0, split_k=0, x3=False, gn_stats=False):
-    """`lda` / `ldw` / `a_bs` / `w_bs` are strides of the tensors as passed (torch elements). bf16x3 mode is selected by the
+def conv_gemm_descriptor(a, w, out, *, M, N, K, Cin, lda, ldw, ldo, T=1, Hin=1, Win=1, Hout=1, Wout=1, KT=1, KH=1, KW=1,
+                         pt=0, ph=0, pw=0, stride=1, ups=1, bias=None, bias_per_row=False, rowbias=None, rowbias_div=0,
+                         residual=None, ldr=0, act=0, out_nchw=False, alpha=1.0, batch=1, a_bs=0, w_bs=0, o_bs=0, r_bs=0,
+                         tile_hint=0, split_k=0, x3=False):
+    """The geo4d_conv_gemm_t of the launch `conv_gemm` makes for these arguments (gn_colsum null: conv_gemm offers the sums itself).
+    `lda` / `ldw` / `a_bs` / `w_bs` are strides of the tensors as passed (torch elements). bf16x3 mode is selected by the
     operands: f32 activations against a pre-split bf16 weight (either side), or two f32 operands with `x3=True`."""
-    lib = _lib.load()
     _dev(a, "A", True); _dev(w, "W", True); _dev(out, "out", True)
-    if getattr(out, "_gn_colsum", None) is not None:       # sums of an EARLIER launch into this tensor object: this launch either sets fresh ones or leaves none
-        out._gn_colsum = None
-        out._gn_colsum_rows = 32
-        out._gn_colsum_tag = None
     for opt, nm in ((bias, "bias"), (rowbias, "rowbias"), (residual, "residual")):
         if opt is not None:
             _dev(opt, nm)
@@ -383,54 +409,85 @@ def conv_gemm(a, w, out, *, M, N, K, Cin, lda, ldw, ldo, T=1, Hin=1, Win=1, Hout
     p.sat_count = _ptr(SAT_COUNTER) if p.o_split == 2 else 0
     ws, zeros = workspace(a.device)
     p.workspace, p.workspace_bytes, p.zeros = ws.data_ptr(), ws.numel(), zeros.data_ptr()
+    return p
+
+
+def conv_gemm_plan(p):
+    """What geo4d_conv_gemm would launch for this descriptor (_lib.ConvGemmPlan); raises where the launch would refuse it."""
+    plan = ConvGemmPlan()
+    _lib.check(_lib.load().geo4d_conv_gemm_plan(C.byref(p), C.byref(plan)), "geo4d_conv_gemm_plan")
+    return plan
+
+
+def _plan_on(p, tile_hint, split_k):
+    """The plan of `p` launched on (tile_hint, split_k), or None where the library refuses that."""
+    p.tile_hint, p.split_k = tile_hint, split_k
+    plan = ConvGemmPlan()
+    return plan if _lib.load().geo4d_conv_gemm_plan(C.byref(p), C.byref(plan)) == 0 else None
+
+
+def _launch_config(p, launch):
+    """(tile_hint, split_k) of a launch that names neither: the tuning table's entry (own or borrowed), else measured now where that is
+    allowed, else (0, 0) = the library's choice."""
+    def may_measure():
+        return AUTOTUNE and not torch.cuda.is_current_stream_capturing()
+    key = f"{p.dtype}/{p.out_dtype}|{p.M}x{p.N}x{p.K}|c{p.Cin}|t{p.KT}{p.KH}{p.KW}s{p.stride}u{p.ups}|a{p.act}r{int(bool(p.R))}n{p.out_nchw}|b{p.batch}"
+    if p.dtype in (BF16X3, F16X2):
+        key += f"|x{int(bool(p.a_split))}{p.w_split}" + ("o" if p.o_split else "")       # (dtype 4's "o" = its f16 rows)
+    cfg = _tuned_config(_tune_table(), key, p.dtype, p.a_split, p.w_split, p.o_split, may_measure)
+    if cfg is None and may_measure():
+        cfg = _autotune(launch, key, lambda tile, split: _plan_on(p, tile, split) is not None)
+    cfg = cfg if cfg is not None else (0, 0)
+    return _f16_rows_config(cfg, p.act) if p.o_split == 2 else cfg
+
+
+def _offer_colsums(p, out, tile_hint, split_k):
+    """The consumer GroupNorm's statistics pass, for free: per row block and column (sum, sum of squares) from the epilogue. The plan says
+    how many rows one entry of THIS launch covers (32 for the first generation, the wave tile's rows for the second / third; 0 = this
+    configuration cannot emit them - split-K, activations, unaligned rows: the GroupNorm then runs its own pass). Attaches the sums to
+    `out` and `p` where the launch emits them; returns the (tile_hint, split_k) to launch."""
+    def rows_on(tile, split):       # (a refused configuration offers nothing: the launch reports the refusal)
+        return getattr(_plan_on(p, tile, split), "colsum_rows", 0)
+    # what decides is the generation of the hint ASKED for (hint 0, the library's choice, counts as the first), not of the tile the plan runs
+    rows = rows_on(tile_hint, split_k) if (_generation(tile_hint) > 1 or int(GN_FUSED_STATS) >= 2) else 0
+    if split_k > 1 and not SPLITK_COLSUM:      # (A/B switch: round 6 lets a split-K launch's reduce kernel emit the sums)
+        rows = 0
+    if rows == 0 and int(GN_FUSED_STATS) >= 2:
+        # mode 2 (A/B, tests): a tuned configuration that cannot emit the sums (split-K; a second / third generation tile on 16-bit rows)
+        # gives way to an un-split first-generation launch, as this path did before round 4
+        first = (tile_hint if _generation(tile_hint) == 1 else 0), 1
+        rows = rows_on(*first)
+        if rows > 0:
+            tile_hint, split_k = first
+    if rows > 0:
+        split_k = split_k or 1           # (the library's own tile choice may not split a launch that emits the sums)
+        cs = torch.empty((p.M // rows, p.N, 2), device=out.device, dtype=torch.float32)
+        p.gn_colsum = cs.data_ptr()
+        out._gn_colsum, out._gn_colsum_rows = cs, rows
+        out._gn_colsum_tag = (out.data_ptr(), out._version)      # groupnorm() ignores the sums if the buffer was rewritten by torch since
+    return tile_hint, split_k
+
+
+def conv_gemm(a, w, out, *, tile_hint=0, split_k=0, gn_stats=False, **problem):
+    """out = epilogue(alpha * gather(a) . w^T): `problem` = the keyword arguments of conv_gemm_descriptor. `tile_hint` / `split_k` both 0:
+    the tuning table decides. `gn_stats`: offer the consumer GroupNorm this launch's column sums (out._gn_colsum)."""
+    lib = _lib.load()
+    p = conv_gemm_descriptor(a, w, out, tile_hint=tile_hint, split_k=split_k, **problem)
+    if getattr(out, "_gn_colsum", None) is not None:       # sums of an EARLIER launch into this tensor object: this launch either sets fresh ones or leaves none
+        out._gn_colsum, out._gn_colsum_rows, out._gn_colsum_tag = None, 32, None
 
     def launch(tile, split):
         p.tile_hint, p.split_k = tile, split
         _lib.check(lib.geo4d_conv_gemm(C.byref(p), _stream()), "geo4d_conv_gemm")
 
     if tile_hint == 0 and split_k == 0:
-        key = f"{p.dtype}/{p.out_dtype}|{M}x{N}x{K}|c{Cin}|t{KT}{KH}{KW}s{stride}u{ups}|a{act}r{int(residual is not None)}n{int(out_nchw)}|b{batch}"
-        if code in (BF16X3, F16X2):
-            key += f"|x{int(bool(a_split))}{int(w_split)}" + ("o" if p.o_split else "")       # (dtype 4's "o" = its f16 rows)
-
-        def may_measure():
-            return AUTOTUNE and not torch.cuda.is_current_stream_capturing()
-        cfg = _tuned_config(_tune_table(), key, code, a_split, w_split, p.o_split, may_measure)
-        if cfg is None and may_measure():
-            cfg = _autotune(launch, key)
-        tile_hint, split_k = cfg if cfg is not None else (0, 0)
-        if p.o_split == 2:
-            tile_hint, split_k = _f16_rows_config((tile_hint, split_k), act)
-    if gn_stats and GN_FUSED_STATS and not p.o_split and batch == 1 and out.dim() == 2 and out.shape[0] == M:
-        # the consumer GroupNorm's statistics pass, for free: per row block and column (sum, sum of squares) from the epilogue. The library
-        # says how many rows one entry of THIS launch covers (32 for the first generation, the wave tile's rows for the second / third; 0 =
-        # this configuration cannot emit them - split-K, activations, unaligned rows: the GroupNorm then runs its own pass)
-        p.tile_hint, p.split_k = tile_hint, split_k
-        rows = lib.geo4d_conv_gemm_colsum_rows(C.byref(p)) if (_generation(tile_hint) > 1 or int(GN_FUSED_STATS) >= 2) else 0
-        if split_k > 1 and not SPLITK_COLSUM:      # (A/B switch: round 6 lets a split-K launch's reduce kernel emit the sums)
-            rows = 0
-        if rows == 0 and int(GN_FUSED_STATS) >= 2:
-            # mode 2 (A/B, tests): a tuned configuration that cannot emit the sums (split-K; a second / third generation tile on 16-bit rows)
-            # gives way to an un-split first-generation launch, as this path did before round 4
-            p.tile_hint, p.split_k = (tile_hint if _generation(tile_hint) == 1 else 0), 1
-            rows = lib.geo4d_conv_gemm_colsum_rows(C.byref(p))
-            if rows > 0:
-                tile_hint, split_k = p.tile_hint, 1
-        if rows > 0:
-            split_k = split_k or 1           # (the library's own tile choice may not split a launch that emits the sums)
-            cs = torch.empty((M // rows, N, 2), device=out.device, dtype=torch.float32)
-            p.gn_colsum = cs.data_ptr()
-            out._gn_colsum = cs
-            out._gn_colsum_rows = rows
-            out._gn_colsum_tag = (out.data_ptr(), out._version)      # groupnorm() ignores the sums if the buffer was rewritten by torch since
-    if GEMM_TIMELINE is not None:     # bench.py's per-launch HIP-event timeline of the dominant kernel (never on while capturing)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        tile_hint, split_k = _launch_config(p, launch)
+    if gn_stats and GN_FUSED_STATS and not p.o_split and p.batch == 1 and out.dim() == 2 and out.shape[0] == p.M:
+        tile_hint, split_k = _offer_colsums(p, out, tile_hint, split_k)
+    if GEMM_TIMELINE is None:
         launch(tile_hint, split_k)
-        e1.record()
-        GEMM_TIMELINE.append((2.0 * M * N * K * batch, e0, e1, {BF16X3: 3, F16X2: 2}.get(code, 1)))    # (flops, events, MFMAs issued per product)
-        return out
-    launch(tile_hint, split_k)
+    else:
+        _on_timeline(GEMM_TIMELINE, lambda: launch(tile_hint, split_k), 2.0 * p.M * p.N * p.K * p.batch, {BF16X3: 3, F16X2: 2}.get(p.dtype, 1))
     return out
 
 
@@ -692,14 +749,12 @@ def attention(q, kv, *, B, H, Nq, scale, out=None, x3=False, variant=None, split
 
 
 def _launch_attention(lib, p):
-    if ATTN_TIMELINE is not None and p.nseg == 1:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    def launch():
         _lib.check(lib.geo4d_attention(C.byref(p), _stream()), "geo4d_attention")
-        e1.record()
-        ATTN_TIMELINE.append((4.0 * p.B * p.H * p.Nq * p.Nk[0] * 64, e0, e1, 3 if p.dtype == BF16X3 else 1))     # (flops, events, MFMAs issued per product)
-        return
-    _lib.check(lib.geo4d_attention(C.byref(p), _stream()), "geo4d_attention")
+    if ATTN_TIMELINE is not None and p.nseg == 1:
+        _on_timeline(ATTN_TIMELINE, launch, 4.0 * p.B * p.H * p.Nq * p.Nk[0] * 64, 3 if p.dtype == BF16X3 else 1)
+    else:
+        launch()
 
 
 def linear_t_batched(w, x, batch, rows, dtype_align=None, split_out=False):

@@ -99,10 +99,30 @@ typedef struct geo4d_conv_gemm_t {
                             (wave, store) lanes whose value lay beyond the finite f16 range and was clamped. Tests assert it stays 0. */
 } geo4d_conv_gemm_t;
 int geo4d_conv_gemm(const geo4d_conv_gemm_t* p, void* stream);
-/* Rows of the output that ONE gn_colsum entry of the launch `*p` describes covers (tile_hint / split_k as they will be launched, the
-   gn_colsum field itself ignored): 32 for the first-generation tiles, the wave tile's rows (32..128) for tile hints >= 21 without split-K,
-   32 or 8 for their split-K launches (the reduce launch sums them); 0 = this launch cannot emit the sums. gn_colsum then has
-   [M / rows][N][2] floats. */
+/* What a launch of `*p` becomes: the answer of the host-side planner (csrc/gemm_plan.h) that geo4d_conv_gemm itself launches from. */
+typedef struct geo4d_conv_gemm_plan_t {
+    int tile_hint;       /* the tile that runs, after defaults, redirects and fall-backs: a launch with it set explicitly runs the same kernel */
+    int generation;      /* its kernel generation: 1 (hints below 21), 2 (21..70) or 3 (from 71)                                           */
+    int bm, bn, wm, wn;  /* workgroup tile bm x bn on wm x wn waves                                                                        */
+    int splits;          /* K slices (gridDim.z); > 1 is followed by the reduce launch                                                     */
+    int hot;             /* operand-layout variant compiled in (4-byte types): 0 generic, 1 raw A x split W, 2 split A x split W           */
+    int osplit;          /* 1: the epilogue writes a producer format (o_split 1 / 2)                                                       */
+    int colsum_rows;     /* rows per gn_colsum entry this launch emits (would emit, where gn_colsum is NULL); 0 = it cannot                */
+} geo4d_conv_gemm_plan_t;
+/* pure host function: validates `p` exactly as geo4d_conv_gemm does (gn_colsum included: a launch that cannot emit the sums it is asked
+   for is refused) and says what it would launch; the launch's own return code, geo4d_last_error() set on refusal */
+int geo4d_conv_gemm_plan(const geo4d_conv_gemm_t* p, geo4d_conv_gemm_plan_t* plan);
+/* One row of the planner's tile table per tile hint that exists. */
+typedef struct geo4d_conv_gemm_tile_t {
+    int tile_hint, generation, bm, bn, wm, wn;
+    int geglu;           /* 1: the tile takes act = 2 (wave tiles a multiple of 64 columns wide)                                           */
+} geo4d_conv_gemm_tile_t;
+/* pure host function: writes the first `cap` rows of the tile table to `out` (may be NULL with cap 0) and returns how many there are */
+int geo4d_conv_gemm_tiles(geo4d_conv_gemm_tile_t* out, int cap);
+/* The colsum_rows of the same plan WITHOUT the descriptor checks (the query older than geo4d_conv_gemm_plan, kept for its callers): rows of
+   the output that ONE gn_colsum entry of the launch `*p` covers (tile_hint / split_k as they will be launched, the gn_colsum field itself ignored): 32 for
+   the first-generation tiles, the wave tile's rows (32..128) for tile hints >= 21 without split-K, 32 or 8 for their split-K launches (the
+   reduce launch sums them); 0 = this launch cannot emit the sums, or the planner refuses it. gn_colsum then has [M / rows][N][2] floats. */
 int geo4d_conv_gemm_colsum_rows(const geo4d_conv_gemm_t* p);
 
 /* GroupNorm(groups) [+SiLU] over tokens [F][HW][C]; statistics per (F / frames_per_stat, group) in fp32.

@@ -152,9 +152,11 @@ def test_tuning_table_uses_only_known_tile_hints():
         assert split in (0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 16), (key, split)       # tile hints 71..74 need an EVEN split of the K slabs: 3, 5, 6, 9, 10, 12 occur
         assert re.match(r"^\d/\d\|\d+x\d+x\d+\|c\d+\|t\d{3}s\du\d\|a\dr\dn\d\|b\d+(\|x[01][01]o?)?$", key), key   # |xAW: bf16x3 pre-split operand flags
     assert all(t in documented for t, _ in ops._CANDIDATES)
-    # the Python tile table (generation + GEGLU-capable neighbour per hint) names exactly the header's hints, and so do the candidates
-    assert set(ops._TILES) == documented - {0} == {t for t, _ in ops._CANDIDATES}
-    assert all(ops._TILES[n][0] == g and ops._TILES[n][1] in ops._TILES for n, (g, _) in ops._TILES.items())
+    # the library's tile table (generation per hint; ops reads it instead of keeping its own) names exactly the header's hints, and so do the
+    # candidates; where a GEGLU writing f16 rows goes from each hint is a tile of the table too
+    tiles = ops._tiles()
+    assert set(tiles) == documented - {0} == {t for t, _ in ops._CANDIDATES}
+    assert all(t.tile_hint == n and t.generation == ops._generation(n) and ops._f16_rows_config((n, 1), 2)[0] in tiles for n, t in tiles.items())
     assert [ops._generation(h) for h in (0, 5, 17, 22, 28, 71, 74)] == [1, 1, 1, 2, 2, 3, 3]
 
 

@@ -48,6 +48,26 @@ SHAPES = [
 ]
 
 
+def plan_takes(fn, **kw):
+    """Whether the library's plan accepts the conv_gemm launch that `fn(**kw)` makes. Nothing is launched: ops.conv2d / ops.linear end in
+    ops.conv_gemm, whose arguments go to the descriptor builder and the plan query (ops.conv_gemm_plan) instead."""
+    real, asked = ops.conv_gemm, []
+
+    def only_plan(a, w, out, gn_stats=False, **problem):
+        asked.append(ops.conv_gemm_descriptor(a, w, out, **problem))
+        return out
+    ops.conv_gemm = only_plan
+    try:
+        fn(**kw)
+    finally:
+        ops.conv_gemm = real
+    try:
+        ops.conv_gemm_plan(asked[0])
+    except ops._lib.Geo4DNativeError:
+        return False
+    return True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16", help="bf16 | f16 | f32 | bf16x3 | f16x2 (two-pass f16 of the bf16x3m mode: 3x3 conv rows, pre-split operands)")
@@ -150,20 +170,16 @@ def main():
             res = []
             for tile in (1, 2, 3, 4, 11, 13, 16, 17):
                 for split in (1, 2, 4, 8):
-                    try:
+                    if plan_takes(fn, tile=tile, split=split):
                         res.append((timeit(tile=tile, split=split), tile, split))
-                    except RuntimeError:
-                        pass
             res.sort()
             print("    auto %.1f us | best: %s" % (us, "  ".join("t%d/s%d %.1f" % (t, s2, u) for u, t, s2 in res[:6])))
             us = min(us, res[0][0])
         if args.explore_all:
             res = []
             for tile, split in ops._CANDIDATES:
-                try:
+                if plan_takes(fn, tile=tile, split=split):
                     res.append((timeit(tile=tile, split=split), tile, split))
-                except RuntimeError:
-                    pass
             res.sort()
             fin = {(t, s2): u for u, t, s2 in res[:6]}
             for _ in range(2):
@@ -181,9 +197,9 @@ def main():
             row = []
             for t in args.tiles.split(","):
                 t, _, sp = t.partition("/")          # "71" or "71/2" (tile / split)
-                try:
+                if plan_takes(fn, tile=int(t), split=int(sp or 1)):
                     row.append("t%s%s %.1f" % (t, "/" + sp if sp else "", timeit(tile=int(t), split=int(sp or 1))))
-                except RuntimeError as e:
+                else:
                     row.append("t%s n/a" % t)
             print("    " + "  ".join(row))
         if args.explore2:
@@ -191,10 +207,8 @@ def main():
                 res = []
                 for tile in tiles:
                     for split in (1, 2, 4, 8):
-                        try:
+                        if plan_takes(fn, tile=tile, split=split):
                             res.append((timeit(tile=tile, split=split), tile, split))
-                        except RuntimeError:
-                            pass
                 return sorted(res)
             v1, v2 = sweep((1, 2, 3, 4, 11, 13, 16, 17)), sweep(list(range(21, 30)) + [31, 33, 34, 35, 39])
             tot2 = globals().setdefault("_TOT2", [0.0, 0.0])

@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geo4d_amd import ops, pack  # noqa: E402
+from tools.gemm_bench import plan_takes  # noqa: E402
 
 
 def main():
@@ -41,12 +42,11 @@ def main():
                         xa, wp = x, w.to(dt)
                     so = bool(x3 and act == 2)
                     fn = lambda: ops.linear(xa, wp, b, act=act, tile_hint=tile, split_k=split, split_out=so)
-                    try:
-                        for _ in range(3):
-                            fn()
-                    except RuntimeError:
+                    if not plan_takes(fn):
                         row.append(None)
                         continue
+                    for _ in range(3):
+                        fn()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     for _ in range(a.iters):
