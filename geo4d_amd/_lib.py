@@ -131,6 +131,8 @@ SIGNATURES = {
     "geo4d_conv_gemm_plan": (C.c_int, [C.POINTER(ConvGemm), C.POINTER(ConvGemmPlan)]),
     "geo4d_conv_gemm_tiles": (C.c_int, [C.POINTER(ConvGemmTile), C.c_int]),
     "geo4d_conv_gemm_colsum_rows": (C.c_int, [C.POINTER(ConvGemm)]),
+    "geo4d_conv_gemm_up2": (C.c_int, [C.POINTER(ConvGemm), C.c_int, C.c_int, C.c_void_p]),
+    "geo4d_conv_gemm_up2_plan": (C.c_int, [C.POINTER(ConvGemm), C.c_int, C.c_int, C.POINTER(ConvGemmPlan)]),
     "geo4d_groupnorm_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "geo4d_groupnorm": (C.c_int, [C.POINTER(GroupNorm), C.c_void_p]),
     "geo4d_groupnorm_plan": (C.c_int, [C.POINTER(GroupNorm2), C.POINTER(GroupNormPlan)]),

@@ -54,6 +54,8 @@ extern template int launch_v2_typed<f16x2p_t>(const geo4d_conv_gemm_t&, const Pl
 extern template int launch_v3_typed<bf16_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
 extern template int launch_v3_typed<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
 extern template int launch_v3_typed<f16x2p_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v2_up2<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
+extern template int launch_v3_up2<bf16x3_t>(const geo4d_conv_gemm_t&, const Plan&, hipStream_t);
 
 // the second / third generation's launcher of the plan's tile (resolve() refuses those hints for the other element types)
 template <typename T>
@@ -97,6 +99,36 @@ extern "C" int geo4d_conv_gemm_plan(const geo4d_conv_gemm_t* pp, geo4d_conv_gemm
     Plan plan;
     if (!out) return GEO4D_EINVAL;
     const int rc = conv_gemm_plan(pp, plan);
+    if (rc != GEO4D_OK) return rc;
+    const Tile& t = *find_tile(plan.hint);
+    *out = {t.hint, generation(t.hint), t.bm, t.bn, t.wm, t.wn, plan.splits, plan.hot, plan.osplit, plan.colsum_rows};
+    return GEO4D_OK;
+}
+
+// the same path for the sub-pixel Upsample launch: the descriptor checks, then resolve_up2
+static int conv_gemm_up2_plan(const geo4d_conv_gemm_t* p, int src_w, int phase, Plan& plan) {
+    if (!p) return GEO4D_EINVAL;
+    const char* error = validate(*p);
+    if (!error) {
+        plan = resolve_up2(*p, src_w, phase);
+        error = plan.error;
+    }
+    if (error) geo4d_set_error(error);
+    return error ? GEO4D_EINVAL : GEO4D_OK;
+}
+
+extern "C" int geo4d_conv_gemm_up2(const geo4d_conv_gemm_t* pp, int src_w, int phase, void* stream) {
+    Plan plan;
+    const int rc = conv_gemm_up2_plan(pp, src_w, phase, plan);
+    if (rc != GEO4D_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return generation(plan.hint) == 2 ? launch_v2_up2<bf16x3_t>(*pp, plan, s) : launch_v3_up2<bf16x3_t>(*pp, plan, s);
+}
+
+extern "C" int geo4d_conv_gemm_up2_plan(const geo4d_conv_gemm_t* pp, int src_w, int phase, geo4d_conv_gemm_plan_t* out) {
+    Plan plan;
+    if (!out) return GEO4D_EINVAL;
+    const int rc = conv_gemm_up2_plan(pp, src_w, phase, plan);
     if (rc != GEO4D_OK) return rc;
     const Tile& t = *find_tile(plan.hint);
     *out = {t.hint, generation(t.hint), t.bm, t.bn, t.wm, t.wn, plan.splits, plan.hot, plan.osplit, plan.colsum_rows};

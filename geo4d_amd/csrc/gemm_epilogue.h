@@ -31,6 +31,22 @@ __device__ __forceinline__ EpiDest epi_dest(const geo4d_conv_gemm_t& p, const bo
     return EpiDest{O, partial ? (long)p.N : p.ldo, partial ? 0 : bz * p.o_bs, odt, odt == GEO4D_F32 ? 4 : 2, geglu ? (p.N >> 1) : p.N, geglu};
 }
 
+// ---- sub-pixel Upsample: strided output rows ---------------------------------------------------------------------------------------------
+// A nearest-2x + 3x3 convolution is, per output parity (py, px), a 2x2 convolution on the source grid (geo4d_conv_gemm_up2). Row
+// m = (f, y, x) of phase 2 py + px lands on token row (f, 2y + py, 2x + px) of the [F, 2H, 2W] grid; frames fold into m div W.
+struct Up2Map {
+    int w, phase;        // source width W; 2 py + px
+    __device__ __forceinline__ long row(const int m) const {
+        const int q = m / w;
+        return 4L * w * q + 2 * (m - q * w) + (phase >> 1) * 2 * w + (phase & 1);
+    }
+};
+
+// the kernel argument the sub-pixel Upsample instantiations take after `splits` and `tiles_mn` (the other instantiations take none)
+struct Up2Args { int w, phase; };      // source width; 2 py + px, or -1: the batch index
+__host__ __device__ __forceinline__ Up2Args up2_args() { return Up2Args{0, 0}; }
+__host__ __device__ __forceinline__ Up2Args up2_args(const Up2Args& a) { return a; }
+
 // ---- value ---------------------------------------------------------------------------------------------------------------------------
 // out[m][n] before the residual: ((acc * alpha + brow) + bias[n]) + rowbias[rboff + n], then SiLU / GELU. `brow`: the per-row bias of row
 // m (0.f without one), `rboff`: the row's offset into the row-bias table; `inb`: n < N (a lane past the last column adds no biases).

@@ -16,9 +16,10 @@ constexpr int MAXTAP = 9;
 static_assert(BKC * 16 == KSLAB_BYTES, "gemm_plan.h counts K slabs of BKC 16-byte chunks");
 
 // gather table: source pixel index of (tile row, tap) of row tile tm, -1 where the tap falls into padding (or the row beyond M). The
-// caller places its own barrier between this and the first read.
+// caller places its own barrier between this and the first read. `ph` / `pw`: the top / left padding (the descriptor's, except in the
+// sub-pixel Upsample kernels, where they follow the tile's phase).
 template <int BM, int NT>
-__device__ __forceinline__ void fill_gather_table(const geo4d_conv_gemm_t& p, const int tm, const int ntap, const int hw, int* rowpix, const int tid) {
+__device__ __forceinline__ void fill_gather_table(const geo4d_conv_gemm_t& p, const int tm, const int ntap, const int hw, int* rowpix, const int tid, const int ph, const int pw) {
     const int hlim = p.ups == 2 ? 2 * p.Hin : p.Hin, wlim = p.ups == 2 ? 2 * p.Win : p.Win;
     const int ush = p.ups == 2 ? 1 : 0;
     for (int e = tid; e < BM * ntap; e += NT) {
@@ -30,13 +31,17 @@ __device__ __forceinline__ void fill_gather_table(const geo4d_conv_gemm_t& p, co
             const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
             const int kt = tap / (p.KH * p.KW), r2 = tap - kt * (p.KH * p.KW);
             const int ky = r2 / p.KW, kx = r2 - ky * p.KW;
-            const int iy = oy * p.stride - p.ph + ky, ix = ox * p.stride - p.pw + kx;
+            const int iy = oy * p.stride - ph + ky, ix = ox * p.stride - pw + kx;
             const int tt = (f % p.T) + kt - p.pt;
             if ((unsigned)iy < (unsigned)hlim && (unsigned)ix < (unsigned)wlim && (unsigned)tt < (unsigned)p.T)
                 pix = ((f + kt - p.pt) * p.Hin + (iy >> ush)) * p.Win + (ix >> ush);
         }
         rowpix[e] = pix;
     }
+}
+template <int BM, int NT>
+__device__ __forceinline__ void fill_gather_table(const geo4d_conv_gemm_t& p, const int tm, const int ntap, const int hw, int* rowpix, const int tid) {
+    fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid, p.ph, p.pw);
 }
 // operand layouts of the 4-byte types: fixed at compile time by HOT (1 = raw A x split W, 2 = split A x split W), else read from the descriptor
 template <int HOT> __device__ __forceinline__ bool a_is_split(const geo4d_conv_gemm_t& p) { return HOT ? (HOT == 2) : (p.a_split != 0); }
@@ -619,6 +624,8 @@ int launch_cfg(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream)
 // gemm_v2_*.hip, hints 71..74 (gemm_kernel_v3.h: the same with a phased, counted-wait K loop) in gemm_v3_*.hip
 template <typename T> int launch_v2_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);
 template <typename T> int launch_v3_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);
+template <typename T> int launch_v2_up2(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);     // the sub-pixel Upsample kernels
+template <typename T> int launch_v3_up2(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream);
 
 template <typename T>
 int launch_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {

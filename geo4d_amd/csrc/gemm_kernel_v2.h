@@ -119,16 +119,26 @@ __device__ __forceinline__ float row16_sum(float v) {      // sum over the 16 la
     return v;
 }
 // The wide f32 plain fast path (also the split-K partial), the one that carries gn_colsum and the row biases. Store = StoreF32 or StoreSplit.
-template <int MB, int NB, typename Store>
+// UP2 (the sub-pixel Upsample kernels; column bias only, the planner refuses the rest): row m is stored at row map.row(m) of O, as a byte
+// offset from the wave tile's first mapped row (one division per lane and row block; a wave tile's rows span at most 4 (16 MB + W) + 2 W
+// rows of O, which resolve_up2 keeps inside the 2 GB window); the launch's gn_colsum entries interleave the four phases: [M / rows][4][N][2].
+template <int MB, int NB, typename Store, bool UP2 = false>
 __device__ __forceinline__ void wide_plain(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const EpiDest& d, const bool partial, const bool has_res, const long rbase,
-                                           const int m_w0, const int n_w0, const int lr, const int lq) {
+                                           const int m_w0, const int n_w0, const int lr, const int lq, const Up2Map map = Up2Map{0, 0}) {
     constexpr unsigned OOB = EPI_OOB;
     const long ldo = d.ldo;
     const float alpha = partial ? 1.0f : p.alpha;
     const bool hb = !partial && p.bias != nullptr && !p.bias_per_row;      // bias per output column
     const bool hr = !partial && p.bias != nullptr && p.bias_per_row;       // bias per output row (the operand-swapped V^T projection)
     const bool ht = !partial && p.rowbias != nullptr;                      // row-bias table (the ResBlocks' per-frame emb add): row m / rowbias_div
-    const __amdgpu_buffer_rsrc_t rsO = tile_rsrc((float*)d.O + d.obase + (long)m_w0 * ldo + n_w0);
+    long row0 = m_w0;
+    unsigned offU[MB];                                                              // UP2: byte offset of this lane's mapped row per row block
+    if constexpr (UP2) {
+        row0 = map.row(m_w0);
+#pragma unroll
+        for (int a = 0; a < MB; ++a) offU[a] = (unsigned)((map.row(m_w0 + a * 16 + lr) - row0) * ldo + 4 * lq) * 4u;
+    }
+    const __amdgpu_buffer_rsrc_t rsO = tile_rsrc((float*)d.O + d.obase + row0 * ldo + n_w0);
     const __amdgpu_buffer_rsrc_t rsR = tile_rsrc(has_res ? (const void*)((const float*)p.R + rbase + (long)m_w0 * p.ldr + n_w0) : p.zeros, has_res);
     const int mleft = p.M - m_w0;
     const __amdgpu_buffer_rsrc_t rsB = bias_rsrc(p, hb, n_w0);
@@ -140,7 +150,8 @@ __device__ __forceinline__ void wide_plain(const geo4d_conv_gemm_t& p, const f32
     // (the launcher checked M % (16 MB) == 0 and the fast-path conditions; a wave tile that starts beyond M - the last row tile of a
     // ragged M - has no entry: its chunk index would lie beyond the [M / rows] buffer)
     const bool gn = !partial && p.gn_colsum != nullptr && m_w0 < p.M;
-    const __amdgpu_buffer_rsrc_t rsC = tile_rsrc(gn ? (const void*)(p.gn_colsum + ((long)(m_w0 / (16 * MB)) * p.N + n_w0) * 2) : p.zeros, gn);
+    const long chunk = UP2 ? (long)(m_w0 / (16 * MB)) * 4 + map.phase : (long)(m_w0 / (16 * MB));
+    const __amdgpu_buffer_rsrc_t rsC = tile_rsrc(gn ? (const void*)(p.gn_colsum + (chunk * p.N + n_w0) * 2) : p.zeros, gn);
     unsigned offT[MB];                                                              // byte offset of this lane's row-bias row per row block
 #pragma unroll
     for (int a = 0; a < MB; ++a) offT[a] = 0u;
@@ -181,7 +192,8 @@ __device__ __forceinline__ void wide_plain(const geo4d_conv_gemm_t& p, const f32
             // (row-block offset in the VGPR offset, soffset = 0: with an SGPR soffset hipcc's hazard recognizer assumes a 16-byte buffer
             // store's data registers may be overwritten right away - on gfx950 the last lanes of every 16 then stored the NEXT block's
             // values, tools/dbg_epilogue.py; measured round 4)
-            Store::store(c, rsO, (ok ? offO + a * rowO : OOB) + 64u * b);
+            if constexpr (UP2) Store::store(c, rsO, (ok ? offU[a] : OOB) + 64u * b);
+            else Store::store(c, rsO, (ok ? offO + a * rowO : OOB) + 64u * b);
         }
         if (gn) {                        // [chunk][n][2]: lane lr == 0 of every 16-lane row writes its 4 columns' (sum, sum of squares)
 #pragma unroll
@@ -278,10 +290,13 @@ __device__ __forceinline__ void generic_rows(const geo4d_conv_gemm_t& p, const f
 // The dispatcher. T: the element type (4-byte types never take the 16-bit-row fast paths; the two-pass f16 type's OSPLIT output,
 // o_split = 2, is PLAIN f16 rows instead of bf16 hi | lo halves); VECONLY: the host checked the vector-store conditions (no scalar
 // fallback code).
-template <typename T, int MB, int NB, bool OSPLIT, bool VECONLY = false>
+template <typename T, int MB, int NB, bool OSPLIT, bool VECONLY = false, bool UP2 = false>
 __device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const int m_w0, const int n_w0,
-                                             const long e_bz, const int e_kz, const bool partial, const int lr, const int lq) {
+                                             const long e_bz, const int e_kz, const bool partial, const int lr, const int lq, const Up2Map map = Up2Map{0, 0}) {
     const EpiDest d = epi_dest(p, partial, e_kz, e_bz);
+    if constexpr (UP2) {      // resolve_up2 admits plain f32 rows with a column bias only: no split-K, residual, row biases or activation
+        return wide_plain<MB, NB, StoreF32, true>(p, acc, d, false, false, 0, m_w0, n_w0, lr, lq, map);
+    }
     const int odt = d.odt, oesz = d.oesz;
     const bool geglu = d.geglu;
     const bool has_res = !partial && p.R != nullptr;
@@ -317,8 +332,13 @@ constexpr int v2_smem_bytes() { return (2 * BM + 2 * BN) * PITCH + BM * MAXTAP *
 // attention kernel); a separate instantiation (the extra epilogue code costs registers).
 // (Round 3 also built a third A-panel buffer - the gathered panel two slabs ahead - and ablation builds of this loop; measured: the
 // third buffer never beat two, profiles/r03_gemm_v2_explore_and_ablation.md. Removed from the shipped sources in round 4.)
-template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>   // HOT: 0 generic, 1 raw A x split W, 2 split A x split W
-__global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_conv_gemm_t p, const int splits, const int tiles_mn) {
+// Up = Up2Args (one more kernel argument): the sub-pixel Upsample form - a tile's phase 2 py + px (`phase`, or the batch index where that is
+// -1) sets its padding ph = 1 - py, pw = 1 - px and where its rows land (Up2Map, gemm_epilogue.h). Without it the kernel is the one it was.
+template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false, typename... Up>   // HOT: 0 generic, 1 raw A x split W, 2 split A x split W
+__global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_conv_gemm_t p, const int splits, const int tiles_mn, const Up... up) {
+    constexpr bool UP2 = sizeof...(Up) != 0;
+    static_assert(!UP2 || !OSPLIT, "the mapped epilogue writes plain f32 rows");
+    const int up_w = up2_args(up...).w, up_phase = up2_args(up...).phase;
     constexpr int NT = WM * WN * 64;
     constexpr int EPC = Elem<T>::EPC;
     constexpr int BK = BKC * EPC;
@@ -392,7 +412,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
         nslab = min(nslab_all, s_begin + per) - s_begin;
         if (!direct_rows) {
             // the previous tile's table is dead here: its last fetch_pix ran before the K loop's final barrier
-            fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid);
+            if constexpr (UP2) {
+                const int phase = up_phase < 0 ? (int)bz : up_phase;
+                fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid, 1 - (phase >> 1), 1 - (phase & 1));
+            } else {
+                fill_gather_table<BM, NT>(p, tm, ntap, hw, rowpix, tid);
+            }
             __syncthreads();
         }
         tap = tapB = s_begin % ntap;
@@ -487,7 +512,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
 
     const bool partial = splits > 1;                  // split-K: raw fp32 slab, the epilogue runs in the reduce kernel
     auto epilogue = [&](int e_tm, int e_tn, long e_bz, int e_kz) {
-        reg_epilogue<T, MB, NB, OSPLIT>(p, acc, e_tm * BM + wr * WTM, e_tn * BN + wc * WTN, e_bz, e_kz, partial, lr, lq);
+        if constexpr (UP2)
+            reg_epilogue<T, MB, NB, false, false, true>(p, acc, e_tm * BM + wr * WTM, e_tn * BN + wc * WTN, e_bz, e_kz, false, lr, lq,
+                                                        Up2Map{up_w, up_phase < 0 ? (int)e_bz : up_phase});
+        else
+            reg_epilogue<T, MB, NB, OSPLIT>(p, acc, e_tm * BM + wr * WTM, e_tn * BN + wc * WTN, e_bz, e_kz, partial, lr, lq);
     };
 
     // ---- persistent tile loop --------------------------------------------------------------------------------------------------------
@@ -532,15 +561,24 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_gemm_v2_kernel(const geo4d_
 struct GenV2 {
     template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT>
     static auto kernel() { return conv_gemm_v2_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>; }
+    template <typename T, int BM, int BN, int WM, int WN, int HOT>
+    static auto kernel_up2() { return conv_gemm_v2_kernel<T, BM, BN, WM, WN, HOT, false, Up2Args>; }
     template <int BM, int BN> static constexpr int smem() { return v2_smem_bytes<BM, BN>(); }
 };
 
-template <typename G, typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>
+// UP2: the generation's sub-pixel Upsample instantiation, with the plan's source width and phase as one more kernel argument
+template <typename G, typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT, bool UP2>
+auto persistent_kernel() {
+    if constexpr (UP2) return G::template kernel_up2<T, BM, BN, WM, WN, HOT>();
+    else return G::template kernel<T, BM, BN, WM, WN, HOT, OSPLIT>();
+}
+
+template <typename G, typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false, bool UP2 = false>
 int launch_persistent(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
     constexpr int smem = G::template smem<BM, BN>();
     static_assert(smem <= 160 * 1024, "LDS");
     static int resident = 0;
-    auto kern = G::template kernel<T, BM, BN, WM, WN, HOT, OSPLIT>();
+    auto kern = persistent_kernel<G, T, BM, BN, WM, WN, HOT, OSPLIT, UP2>();
     if (!resident) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
             geo4d_set_error("hipFuncSetAttribute(max dynamic LDS) failed");
@@ -559,7 +597,8 @@ int launch_persistent(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t 
     // debug_ablate = 2 (tests only): 3 workgroups whatever the problem, so that small shapes walk the persistent tile loop
     const long cap = p.debug_ablate == 2 ? 3 : resident;
     const unsigned grid = (unsigned)(total < cap ? total : cap);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn);
+    if constexpr (UP2) hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn, Up2Args{plan.up_w, plan.up_phase});
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn);
     GEO4D_CHECK_LAUNCH();
     if (plan.splits > 1) return launch_splitk_reduce<T>(p, plan, stream);
     return GEO4D_OK;
@@ -600,6 +639,24 @@ int launch_v2_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t st
         }
     }
     geo4d_set_error("conv_gemm: no second-generation kernel for this tile_hint and element type");      // (resolve() refuses these)
+    return GEO4D_EINVAL;
+}
+
+// the sub-pixel Upsample kernels of one tile (bf16x3 against a pre-split weight: raw or pre-split activations)
+template <typename G, typename T, int BM, int BN, int WM, int WN>
+int launch_persistent_up2(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    if (plan.hot == 2) return launch_persistent<G, T, BM, BN, WM, WN, 2, false, true>(p, plan, stream);
+    return launch_persistent<G, T, BM, BN, WM, WN, 1, false, true>(p, plan, stream);
+}
+// tile hints 22, 23 and 25 (resolve_up2 refuses the others)
+template <typename T>
+int launch_v2_up2(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    switch (plan.hint) {
+        case 22: return launch_persistent_up2<GenV2, T, 256, 256, 4, 2>(p, plan, stream);
+        case 23: return launch_persistent_up2<GenV2, T, 160, 320, 2, 4>(p, plan, stream);
+        case 25: return launch_persistent_up2<GenV2, T, 128, 128, 2, 2>(p, plan, stream);
+    }
+    geo4d_set_error("conv_gemm_up2: no second-generation kernel for this tile_hint");
     return GEO4D_EINVAL;
 }
 

@@ -45,8 +45,12 @@ constexpr int v3_smem_bytes() { return 2 * (BM + BN) * PITCH; }
 // (Round 3 also carried ablation builds of this loop - no DMA / no MFMA / no reads / no waits / no barriers / s_memtime stamps - a
 // variant with the two wave groups staggered by a second barrier per phase (4-10 % slower) and one with s_setprio around the MFMAs
 // (1-4 % slower in this lockstep schedule): profiles/r03_gemm_v3_phased.md has their numbers; round 4 removed them from the sources.)
-template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false>   // HOT: 0 generic, 1 raw A x split W, 2 split A x split W
-__global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm_t p, const int splits, const int tiles_mn) {
+// Up = Up2Args: the sub-pixel Upsample form, as in conv_gemm_v2_kernel - the tile's phase sets its padding and where its rows land.
+template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT = false, typename... Up>   // HOT: 0 generic, 1 raw A x split W, 2 split A x split W
+__global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm_t p, const int splits, const int tiles_mn, const Up... up) {
+    constexpr bool UP2 = sizeof...(Up) != 0;
+    static_assert(!UP2 || !OSPLIT, "the mapped epilogue writes plain f32 rows");
+    const int up_w = up2_args(up...).w, up_phase = up2_args(up...).phase;
     static_assert(WM * WN == 8, "two groups of four waves");
     static_assert(!std::is_same<T, float>::value, "v3 serves the 16-bit MFMA forms (bf16, bf16x3)");
     constexpr int EPC = Elem<T>::EPC;
@@ -153,13 +157,19 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
     // the A window of tile (tm_, bz_): base = the tap-0 source pixel of the tile's first row (the smallest address any of its rows
     // reads - v3_native in gemm_plan.h admits only geometries in which the tap-0 pixel never decreases with the row; it may lie before
     // the tensor when that pixel is padding - only in-image taps are ever dereferenced)
-    auto tap0_pixel = [&](int m) -> long {
+    auto tap0_pixel = [&](int m, int ph, int pw) -> long {
         const int f = m / hw, rem = m - f * hw;
         const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-        return ((long)(f - p.pt) * p.Hin + (oy * p.stride - p.ph)) * p.Win + (ox * p.stride - p.pw);
+        return ((long)(f - p.pt) * p.Hin + (oy * p.stride - ph)) * p.Win + (ox * p.stride - pw);
     };
     auto window_A = [&](bool valid, int tm_, long bz_) {
-        const long P0 = valid ? tap0_pixel(tm_ * BM) : 0;
+        int ph = p.ph, pw = p.pw;
+        if constexpr (UP2) {
+            const int phase = up_phase < 0 ? (int)bz_ : up_phase;
+            ph = 1 - (phase >> 1);
+            pw = 1 - (phase & 1);
+        }
+        const long P0 = valid ? tap0_pixel(tm_ * BM, ph, pw) : 0;
         rA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + (bz_ * p.a_bs + P0 * p.lda) * ESZ_A), 0, OOB, 0x00020000);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -171,7 +181,7 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
                 if (valid && row >= 0 && m < p.M) {
                     const int f = m / hw, rem = m - f * hw;
                     const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-                    const int iy0 = oy * p.stride - p.ph, ix0 = ox * p.stride - p.pw, ft = (f % p.T) - p.pt;
+                    const int iy0 = oy * p.stride - ph, ix0 = ox * p.stride - pw, ft = (f % p.T) - p.pt;
                     const long px0 = ((long)(f - p.pt) * p.Hin + iy0) * p.Win + ix0;
                     off = (unsigned)(((px0 - P0) * p.lda + chunkA(j)) * ESZ_A);
                     unsigned bit = 1;
@@ -445,7 +455,11 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
             // (dozens of 64-bit row offsets) are hoisted out of the tile loop and live - spilled - across the K loop
             int lr_ = lr, lq_ = lq;
             asm volatile("" : "+v"(lr_), "+v"(lq_));
-            reg_epilogue<T, MB, NB, OSPLIT, true>(p, acc, tmC * BM + wr * WTM, tnC * BN + wc * WTN, bzC, kzC, partial, lr_, lq_);
+            if constexpr (UP2)
+                reg_epilogue<T, MB, NB, false, true, true>(p, acc, tmC * BM + wr * WTM, tnC * BN + wc * WTN, bzC, kzC, false, lr_, lq_,
+                                                           Up2Map{up_w, up_phase < 0 ? (int)bzC : up_phase});
+            else
+                reg_epilogue<T, MB, NB, OSPLIT, true>(p, acc, tmC * BM + wr * WTM, tnC * BN + wc * WTN, bzC, kzC, partial, lr_, lq_);
         }
         // a REAL s_waitcnt vmcnt(0) (the builtin, which the compiler's wait-count pass tracks; an inline-asm one it does not see):
         // without it the pass has to assume pending loads into VGPRs at the K loop's header and drains the DMA queue every slab
@@ -460,6 +474,8 @@ __global__ __launch_bounds__(512) void conv_gemm_v3_kernel(const geo4d_conv_gemm
 struct GenV3 {
     template <typename T, int BM, int BN, int WM, int WN, int HOT, bool OSPLIT>
     static auto kernel() { return conv_gemm_v3_kernel<T, BM, BN, WM, WN, HOT, OSPLIT>; }
+    template <typename T, int BM, int BN, int WM, int WN, int HOT>
+    static auto kernel_up2() { return conv_gemm_v3_kernel<T, BM, BN, WM, WN, HOT, false, Up2Args>; }
     template <int BM, int BN> static constexpr int smem() { return v3_smem_bytes<BM, BN>(); }
 };
 
@@ -478,6 +494,17 @@ int launch_v3_typed(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t st
         }
     }
     geo4d_set_error("conv_gemm: no third-generation kernel for this tile_hint and element type");      // (resolve() refuses these)
+    return GEO4D_EINVAL;
+}
+
+// the sub-pixel Upsample kernels: tile hints 71 and 72 (resolve_up2 refuses the others)
+template <typename T>
+int launch_v3_up2(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t stream) {
+    switch (plan.hint) {
+        case 71: return launch_persistent_up2<GenV3, T, 192, 256, 2, 4>(p, plan, stream);
+        case 72: return launch_persistent_up2<GenV3, T, 160, 320, 2, 4>(p, plan, stream);
+    }
+    geo4d_set_error("conv_gemm_up2: no third-generation kernel for this tile_hint");
     return GEO4D_EINVAL;
 }
 

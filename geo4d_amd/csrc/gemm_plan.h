@@ -50,6 +50,7 @@ struct Plan {
     int hot = 0;                // operand layout fixed at compile time (4-byte types): 0 generic, 1 raw A x split W, 2 split A x split W
     bool osplit = false;        // the epilogue writes the producers' pre-split format (o_split = 1) / plain f16 rows (o_split = 2)
     int colsum_rows = 0;        // rows per gn_colsum entry this launch emits (would emit, where gn_colsum is null); 0 = it cannot
+    int up_w = 0, up_phase = 0; // resolve_up2 only: source width (> 0 = the sub-pixel Upsample kernels) and phase 2 py + px (-1 = the batch index)
     const char* error = nullptr;
 };
 
@@ -250,6 +251,42 @@ inline Plan resolve(const geo4d_conv_gemm_t& p) {
     if (p.gn_colsum && (!pl.colsum_rows || (pl.splits == 1 && !aligned(p.gn_colsum, 16))))
         return refuse("conv_gemm: this launch cannot emit gn_colsum (geo4d_conv_gemm_colsum_rows): it needs a row-major 16-byte aligned output, batch 1, no GEGLU, "
                       "M a multiple of the rows per entry; first generation: no split-K; later generations: f32 rows, no activation");
+    return pl;
+}
+
+// geo4d_conv_gemm_up2: the (validated) descriptor `p` is a 2x2 convolution on the source grid whose rows land on phase 2 py + px of the
+// nearest-2x grid (`phase` 0..3: one launch per phase with ph = 1 - py, pw = 1 - px; -1: the four phases are the batch index, which then
+// steps through the weights only). The launch runs the plan resolve() gives the same descriptor, on the kernels that carry the row
+// mapping: bf16x3 against a pre-split weight, tile hints 22, 23, 25, 71, 72, plain f32 rows with a column bias. gn_colsum entries of the
+// four phases interleave ([M / rows][4][N][2]), so a frame's entries stay contiguous where its source rows are a multiple of `rows`.
+inline Plan resolve_up2(const geo4d_conv_gemm_t& p, int src_w, int phase) {
+    Plan pl;
+    auto refuse = [&pl](const char* why) { pl.error = why; pl.colsum_rows = 0; return pl; };
+    if (p.dtype != GEO4D_BF16X3 || !p.w_split)
+        return refuse("conv_gemm_up2: the sub-pixel form serves bf16x3 (dtype 3) against a pre-split weight; the other modes keep the ups = 2 gather");
+    if (p.ups != 1 || p.KT != 1 || p.KH != 2 || p.KW != 2 || p.stride != 1 || p.pt != 0 || src_w <= 0 || p.Win != src_w || p.Wout != src_w || p.Hout != p.Hin)
+        return refuse("conv_gemm_up2: the descriptor must be the 2x2 stride-1 convolution on the source grid (ups = 1, Hout = Hin, Wout = Win = src_w)");
+    if (phase < -1 || phase > 3) return refuse("conv_gemm_up2: phase must be 2 py + px (0..3), or -1 for the four phases in the batch index");
+    if (phase >= 0 ? (p.batch != 1 || p.ph != 1 - (phase >> 1) || p.pw != 1 - (phase & 1)) : (p.batch != 4 || p.a_bs != 0 || p.o_bs != 0))
+        return refuse("conv_gemm_up2: a phase launch has batch 1, ph = 1 - py, pw = 1 - px; the batch form has batch 4 with a_bs = o_bs = 0");
+    if (p.split_k > 1) return refuse("conv_gemm_up2: no split-K (the reduce kernel writes unmapped rows)");
+    if (p.act != 0 || p.R || p.rowbias || p.bias_per_row || p.out_nchw || p.o_split || p.out_dtype != GEO4D_F32 || (p.N & 3) || (p.ldo & 3) || !aligned(p.O, 16))
+        return refuse("conv_gemm_up2: the mapped epilogue writes plain f32 rows with a column bias only (N % 4 == 0, 16-byte aligned rows)");
+    // a wave tile's (at most 128) rows land within 4 (128 + W) + 2 W rows of the output: their byte offsets must stay inside the buffer window
+    if ((4L * (128 + src_w) + 2L * src_w) * p.ldo * 4 >= (1L << 31)) return refuse("conv_gemm_up2: a wave tile's output rows span more than the 2 GB buffer window");
+    geo4d_conv_gemm_t q = p;      // the phases of the batch form share everything a plan depends on
+    q.batch = 1;
+    q.gn_colsum = nullptr;
+    q.split_k = 1;
+    pl = resolve(q);
+    if (pl.error) return pl;
+    if (pl.hint != 22 && pl.hint != 23 && pl.hint != 25 && pl.hint != 71 && pl.hint != 72)
+        return refuse("conv_gemm_up2: the mapped epilogue lives on tile hints 22, 23, 25, 71 and 72");
+    if ((p.Hin * p.Win) % (pl.colsum_rows ? pl.colsum_rows : 1)) pl.colsum_rows = 0;      // an entry's rows must not straddle frames
+    if (p.gn_colsum && (!pl.colsum_rows || !aligned(p.gn_colsum, 16)))
+        return refuse("conv_gemm_up2: this launch cannot emit gn_colsum: it needs a frame's source rows and M to be multiples of the wave tile's rows");
+    pl.up_w = src_w;
+    pl.up_phase = phase;
     return pl;
 }
 

@@ -426,9 +426,9 @@ def _plan_on(p, tile_hint, split_k):
     return plan if _lib.load().geo4d_conv_gemm_plan(C.byref(p), C.byref(plan)) == 0 else None
 
 
-def _launch_config(p, launch):
+def _launch_config(p, launch, plan_on=_plan_on):
     """(tile_hint, split_k) of a launch that names neither: the tuning table's entry (own or borrowed), else measured now where that is
-    allowed, else (0, 0) = the library's choice."""
+    allowed, else (0, 0) = the library's choice. `plan_on(p, tile, split)`: the plan query of the entry point that launches `p`."""
     def may_measure():
         return AUTOTUNE and not torch.cuda.is_current_stream_capturing()
     key = f"{p.dtype}/{p.out_dtype}|{p.M}x{p.N}x{p.K}|c{p.Cin}|t{p.KT}{p.KH}{p.KW}s{p.stride}u{p.ups}|a{p.act}r{int(bool(p.R))}n{p.out_nchw}|b{p.batch}"
@@ -436,7 +436,7 @@ def _launch_config(p, launch):
         key += f"|x{int(bool(p.a_split))}{p.w_split}" + ("o" if p.o_split else "")       # (dtype 4's "o" = its f16 rows)
     cfg = _tuned_config(_tune_table(), key, p.dtype, p.a_split, p.w_split, p.o_split, may_measure)
     if cfg is None and may_measure():
-        cfg = _autotune(launch, key, lambda tile, split: _plan_on(p, tile, split) is not None)
+        cfg = _autotune(launch, key, lambda tile, split: plan_on(p, tile, split) is not None)
     cfg = cfg if cfg is not None else (0, 0)
     return _f16_rows_config(cfg, p.act) if p.o_split == 2 else cfg
 
@@ -536,6 +536,83 @@ def conv2d(x, w, bias, *, F, Hin, Win, KH, KW, stride=1, pad=0, pad_end=0, ups=1
               ldr=_ld(residual) if residual is not None else 0, act=act, out_nchw=out_nchw, tile_hint=tile_hint,
               split_k=split_k, gn_stats=gn_stats)
     return out, Hout, Wout
+
+
+# Nearest-2x + 3x3 convolutions (the Upsample layers) in their sub-pixel form: four 2x2 convolutions on the source grid, 4 / 9 of the
+# multiplications of conv2d(ups=2) in the same three bf16 passes (include/geo4d_hip.h geo4d_conv_gemm_up2). GEO4D_UP_SUBPIXEL=0 keeps every
+# call site on the gather form (A/B runs in one build). Measured on MI355X (profiles/upsample_subpixel.md section 2, us per conv, gather ->
+# sub-pixel): U-Net 10x16 776 -> 288, 20x32 688 -> 298; VAE decoder (48 frames) 5041 -> 2505, 21173 -> 10267, 22410 -> 11375.
+UP_SUBPIXEL = _env_level("GEO4D_UP_SUBPIXEL", 1)
+# "batch": one launch, the phase in the batch index; "phases": four launches - never faster, and 2.4 - 7.6x slower at the U-Net's sources,
+# where a phase alone under-fills the chip
+UP2_FORM = _os.environ.get("GEO4D_UP2_FORM", "batch")
+# source rows (F H W) below which the gather form stays. The U-Net's 5x8 source (640 rows) is 1.39x faster alone (239 -> 172 us, weights
+# resident in the last-level cache) but SLOWER inside a replayed step (185 -> 202 us in the kernel trace): its four weights are 16/9 of
+# the bytes and the launch is weight-bound. The next level (2560 rows) wins in both.
+UP2_MIN_ROWS = 2048
+_UP2_TILES = (22, 23, 25, 71, 72)
+_UP2_SUMS_TILE = {71: 22}      # the 96-row blocks of tile 71 straddle frames of 2560 k source rows; tile 22 (64) was within 1.5 % of it wherever 71 won
+
+
+def up_subpixel(x, w4, rows):
+    """Does an Upsample conv of `rows` source rows run in the sub-pixel form? `w4`: its pack.pack_conv2d_up2 weight, None where the mode has none."""
+    return bool(UP_SUBPIXEL) and w4 is not None and rows >= UP2_MIN_ROWS and (isinstance(x, SplitAct) or x.dtype == torch.float32)
+
+
+def _up2_plan_on(p, src_w, phase):
+    def plan_on(p_, tile_hint, split_k):
+        if split_k != 1 or tile_hint not in _UP2_TILES:
+            return None
+        p_.tile_hint, p_.split_k = tile_hint, 1
+        plan = ConvGemmPlan()
+        return plan if _lib.load().geo4d_conv_gemm_up2_plan(C.byref(p_), src_w, phase, C.byref(plan)) == 0 else None
+    return plan_on
+
+
+def conv2d_up2(x, w4, bias, *, F, Hin, Win, out=None, gn_stats=False, tile_hint=0, form=None):
+    """conv2d(x, w, bias, KH=3, KW=3, pad=1, ups=2) from the folded weight `w4` = pack.pack_conv2d_up2(w): [4, N, 4 Cin] in the bf16x3 operand
+    format, phase 2 py + px major. x tokens [F*Hin*Win, Cin] (f32 rows or a SplitAct, shared by the four phases); returns (tokens
+    [F*2Hin*2Win, N] f32, 2 Hin, 2 Win). `form`: UP2_FORM. `gn_stats`: as conv_gemm (one sum buffer for the four phases)."""
+    lib = _lib.load()
+    Cin, N, M = act_k(x), w4.shape[1], F * Hin * Win
+    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.stride(2) == 1 and kdim(w4[0], x) == 4 * Cin, (w4.shape, Cin)
+    assert x.shape[0] == M, (x.shape, F, Hin, Win)
+    if out is None:
+        out = torch.empty((4 * M, N), device=x.device, dtype=torch.float32)
+    assert out.dim() == 2 and out.shape[0] == 4 * M and out.dtype == torch.float32 and not isinstance(out, SplitAct)
+    batched = (form or UP2_FORM) == "batch"
+    p = conv_gemm_descriptor(x, w4[0], out, M=M, N=N, K=4 * Cin, Cin=Cin, lda=_ld(x), ldw=w4.stride(1), ldo=_ld(out), Hin=Hin, Win=Win,
+                             Hout=Hin, Wout=Win, KH=2, KW=2, ph=1, pw=1, bias=bias, batch=4 if batched else 1,
+                             w_bs=w4.stride(0) if batched else 0, tile_hint=tile_hint, split_k=1)
+    if getattr(out, "_gn_colsum", None) is not None:
+        out._gn_colsum, out._gn_colsum_rows, out._gn_colsum_tag = None, 32, None
+    phases = (-1,) if batched else (0, 1, 2, 3)
+
+    def launch(tile, split):
+        p.tile_hint, p.split_k = tile, 1
+        for ph in phases:
+            if ph >= 0:
+                p.W, p.ph, p.pw = w4[ph].data_ptr(), 1 - (ph >> 1), 1 - (ph & 1)
+            _lib.check(lib.geo4d_conv_gemm_up2(C.byref(p), Win, ph, _stream()), "geo4d_conv_gemm_up2")
+
+    plan_on = _up2_plan_on(p, Win, phases[0])
+    if tile_hint == 0:
+        tile_hint = _launch_config(p, launch, plan_on)[0] or (72 if M >= 8192 else 25)
+    if gn_stats and GN_FUSED_STATS:
+        rows = getattr(plan_on(p, tile_hint, 1), "colsum_rows", 0)
+        if rows == 0 and tile_hint in _UP2_SUMS_TILE:      # the consumer's statistics pass over the up-sampled map costs more than the tile gains
+            rows = getattr(plan_on(p, _UP2_SUMS_TILE[tile_hint], 1), "colsum_rows", 0)
+            tile_hint = _UP2_SUMS_TILE[tile_hint] if rows > 0 else tile_hint
+        if rows > 0:
+            cs = torch.empty((4 * M // rows, N, 2), device=out.device, dtype=torch.float32)
+            p.gn_colsum = cs.data_ptr()
+            out._gn_colsum, out._gn_colsum_rows = cs, rows
+            out._gn_colsum_tag = (out.data_ptr(), out._version)
+    if GEMM_TIMELINE is None:
+        launch(tile_hint, 1)
+    else:
+        _on_timeline(GEMM_TIMELINE, lambda: launch(tile_hint, 1), 2.0 * 4 * M * N * p.K, 3)
+    return out, 2 * Hin, 2 * Win
 
 
 def conv_temporal(x, w, bias, *, B, T, HW, residual=None, out=None, gn_stats=False, tile_hint=0, split_k=0):

@@ -103,6 +103,27 @@ def pack_conv2d(w, dtype, cin_pad=None):
     return cast(w.reshape(co, kh * kw * cp), dtype)
 
 
+def fold_up2(w):
+    """nn.Conv2d 3x3 weight [Cout, Cin, 3, 3] of an Upsample layer (nearest 2x, then pad 1) -> [4, Cout, Cin, 2, 2]: per output parity
+    2 py + px the 2x2 kernel on the SOURCE grid that computes the same pixels. Up-sampled row 2y + py + dy reads source row
+    (2y + py + dy) >> 1, so py = 0 sees rows {y - 1: W[-1], y: W[0] + W[1]} (top padding 1) and py = 1 rows {y: W[-1] + W[0], y + 1: W[1]}
+    (top padding 0); columns alike. Summed in float64, rounded once to float32."""
+    assert w.shape[2:] == (3, 3), w.shape
+    r = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=torch.float64, device=w.device)
+    w64 = w.double()
+    return torch.stack([torch.einsum("ak,oikl,bl->oiab", r[py], w64, r[px]) for py in (0, 1) for px in (0, 1)]).float()
+
+
+def up2_row(m, W, py, px):
+    """Token row of the [F, 2H, 2W] grid that row m = (f, y, x) of phase (py, px) lands on (frames fold into m // W)."""
+    return 4 * W * (m // W) + 2 * (m % W) + py * 2 * W + px
+
+
+def pack_conv2d_up2(w, dtype):
+    """The folded weights in the operand format of the compute mode: [4, Cout, 4*Cin_pad] (phase major; K = tap-major 2x2, channel fastest)."""
+    return torch.stack([pack_conv2d(f, dtype) for f in fold_up2(w)])
+
+
 def pack_conv3d_t(w, dtype):
     """nn.Conv3d weight [Cout, Cin, 3, 1, 1] -> [Cout, 3*Cin]."""
     co, ci, kt, kh, kw = w.shape

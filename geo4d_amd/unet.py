@@ -362,6 +362,7 @@ class UNetModel(ParamTree):
                 e["w"], e["b"] = pack.pack_conv2d(sd[p + ".op.weight"], dt), f32(p + ".op.bias")
             elif L.kind == "up":
                 e["w"], e["b"] = pack.pack_conv2d(sd[p + ".conv.weight"], dt), f32(p + ".conv.bias")
+                e["w4"] = pack.pack_conv2d_up2(sd[p + ".conv.weight"], dt) if dt.x3 else None      # sub-pixel form (ops.conv2d_up2)
             P[p] = e
         P["emb_w"], P["emb_b"] = torch.cat(emb_w, 0).contiguous(), torch.cat(emb_b, 0).contiguous()
         P["k_text"] = pack.pack_linear(torch.cat(k_text, 0), dt)
@@ -554,7 +555,10 @@ class UNetModel(ParamTree):
             elif L.kind == "up":
                 # (bf16x3 modes: the stream is split ONCE by its own pass instead of per K slab and wave inside the conv - same bits, PRESPLIT_UP)
                 a = ops.presplit(h) if (self.presplit and PRESPLIT_UP) else h
-                h, H, W = ops.conv2d(a, e["w"], e["b"], F=B * T, Hin=H, Win=W, KH=3, KW=3, pad=1, ups=2, out=o)
+                if ops.up_subpixel(a, e["w4"], B * T * H * W):
+                    h, H, W = ops.conv2d_up2(a, e["w4"], e["b"], F=B * T, Hin=H, Win=W, out=o)
+                else:
+                    h, H, W = ops.conv2d(a, e["w"], e["b"], F=B * T, Hin=H, Win=W, KH=3, KW=3, pad=1, ups=2, out=o)
         return h, H, W
 
     # ---- public forward -------------------------------------------------------------------------------------

@@ -188,6 +188,7 @@ class AutoencoderKL(ParamTree):
                 # class together with the U-Net's streams and rejected both; measured alone: profiles/r06_vae_decode.md)
                 up2 = bool(dt.two_pass("vaeup") and self.presplit)
                 P[p] = ((pack.pack_conv2d_x2 if up2 else pack.pack_conv2d)(sd[p + ".weight"], dt), f32(p + ".bias"))
+                P[p + ".w4"] = pack.pack_conv2d_up2(sd[p + ".weight"], dt) if (dt.x3 and not up2) else None      # sub-pixel form (ops.conv2d_up2)
         P["head"] = (norm("decoder.norm_out"), pack.pack_conv2d(sd["decoder.conv_out.weight"], dt), f32("decoder.conv_out.bias"))
         # channel-mean head: mean_c(conv(x, W)_c + b_c) == conv(x, mean_c W_c) + mean_c b_c  (depth modality, test_geo4d.py:254-257)
         P["head_mean"] = (P["head"][0], pack.pack_conv2d(sd["decoder.conv_out.weight"].mean(0, keepdim=True), dt),
@@ -300,7 +301,10 @@ class AutoencoderKL(ParamTree):
             else:
                 from .unet import PRESPLIT_UP
                 a = ops.cast_f16(x) if ops.is_x2_weight(P[p][0]) else ops.presplit(x) if (self.presplit and PRESPLIT_UP) else x
-                x, H, W = ops.conv2d(a, *P[p], F=n, Hin=H, Win=W, KH=3, KW=3, pad=1, ups=2, gn_stats=True)
+                if ops.up_subpixel(a, P[p + ".w4"], n * H * W):
+                    x, H, W = ops.conv2d_up2(a, P[p + ".w4"], P[p][1], F=n, Hin=H, Win=W, gn_stats=True)
+                else:
+                    x, H, W = ops.conv2d(a, *P[p], F=n, Hin=H, Win=W, KH=3, KW=3, pad=1, ups=2, gn_stats=True)
         return x, H, W
 
     def _head(self, head, feat, F_, H, W, out, T, nchw_channels):

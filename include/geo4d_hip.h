@@ -124,6 +124,21 @@ int geo4d_conv_gemm_tiles(geo4d_conv_gemm_tile_t* out, int cap);
    the first-generation tiles, the wave tile's rows (32..128) for tile hints >= 21 without split-K, 32 or 8 for their split-K launches (the
    reduce launch sums them); 0 = this launch cannot emit the sums, or the planner refuses it. gn_colsum then has [M / rows][N][2] floats. */
 int geo4d_conv_gemm_colsum_rows(const geo4d_conv_gemm_t* p);
+/* Nearest-2x upsampling + 3x3 convolution (pad 1) in its sub-pixel form: per output parity (py, px) the operation is a 2x2 convolution on
+   the SOURCE grid [F, H, W] whose weights are sums of the 3x3 ones (geo4d_amd/pack.py fold_up2: rows {y - 1: W[-1], y: W[0] + W[1]} for
+   py = 0, {y: W[-1] + W[0], y + 1: W[1]} for py = 1, columns alike) - 4 / 9 of the multiplications of the ups = 2 gather, same passes.
+   `*p` describes that 2x2 convolution: ups 1, KH = KW = 2, stride 1, Hout = Hin = H, Wout = Win = src_w = W, M = F H W, K = 4 Cin, and O
+   the [F, 2H, 2W] token grid: row m = (f, y, x) is stored at row 4 W (m div W) + 2 (m mod W) + py 2W + px.
+   phase 0..3 = 2 py + px: one launch per phase, batch 1, ph = 1 - py, pw = 1 - px, W that phase's weight;
+   phase -1: ONE launch, the phase is the batch index (batch 4, a_bs = o_bs = 0, w_bs = the stride between the phase weights; ph / pw are
+   set per phase by the kernel).
+   dtype 3 (bf16x3) against a pre-split weight (raw or pre-split activations), tile hints 22, 23, 25, 71, 72, plain f32 rows with a column
+   bias: no activation, residual, row biases, split-K, o_split or NCTHW output - everything else is refused (csrc/gemm_plan.h resolve_up2).
+   gn_colsum: [M / rows][4][N][2] - the entries of the four phases interleave, so that the buffer reads as the [4 M / rows][N][2] sums of O
+   with each frame's entries contiguous; needs H W % rows == 0 (rows = the plan's colsum_rows). */
+int geo4d_conv_gemm_up2(const geo4d_conv_gemm_t* p, int src_w, int phase, void* stream);
+/* pure host function: what geo4d_conv_gemm_up2 would launch, or its refusal (the launch's own return code and message) */
+int geo4d_conv_gemm_up2_plan(const geo4d_conv_gemm_t* p, int src_w, int phase, geo4d_conv_gemm_plan_t* plan);
 
 /* GroupNorm(groups) [+SiLU] over tokens [F][HW][C]; statistics per (F / frames_per_stat, group) in fp32.
  * replaces nn.GroupNorm / GroupNormSpecific + nn.SiLU (basics.py:76-87; openaimodel3d.py:151-153,174-176,256-266;

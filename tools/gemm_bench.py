@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geo4d_amd import ops  # noqa: E402
 
 # (name, kind, M-geometry, N, Cin, count per U-Net forward)
-# kind: lin (K=Cin) | c3 (3x3 conv, K=9*Cin, geometry F,H,W) | t3 (temporal 3-tap, K=3*Cin) | geglu
+# kind: lin (K=Cin) | c3 (3x3 conv, K=9*Cin, geometry F,H,W) | t3 (temporal 3-tap, K=3*Cin) | geglu | u3 / u2 (Upsample layers, below)
 SHAPES = [
     ("L0 conv3x3 320->320", "c3", (16, 40, 64), 320, 320, 7),
     ("L0 conv3x3 640->320", "c3", (16, 40, 64), 320, 640, 2),
@@ -45,6 +45,20 @@ SHAPES = [
     ("VAE conv3x3 512 @80x128 x48f", "c3", (48, 80, 128), 512, 512, 0),
     ("VAE conv3x3 256 @160x256 x48f", "c3", (48, 160, 256), 256, 256, 0),
     ("VAE conv3x3 128 @320x512 x16f", "c3", (16, 320, 512), 128, 128, 0),
+    # the Upsample layers (nearest 2x + conv 3x3; geometry = the SOURCE grid) in both forms: u3 = the ups = 2 gather (K = 9 Cin on the
+    # up-sampled rows), u2 = the sub-pixel form (ops.conv2d_up2: four 2x2 phases, K = 4 Cin; bf16x3 only; counted once, under u3)
+    ("L3 up 1280 5x8 -> 10x16", "u3", (16, 5, 8), 1280, 1280, 1),
+    ("L3 up 1280 5x8 -> 10x16 subpixel", "u2", (16, 5, 8), 1280, 1280, 0),
+    ("L2 up 1280 10x16 -> 20x32", "u3", (16, 10, 16), 1280, 1280, 1),
+    ("L2 up 1280 10x16 -> 20x32 subpixel", "u2", (16, 10, 16), 1280, 1280, 0),
+    ("L1 up 640 20x32 -> 40x64", "u3", (16, 20, 32), 640, 640, 1),
+    ("L1 up 640 20x32 -> 40x64 subpixel", "u2", (16, 20, 32), 640, 640, 0),
+    ("VAE up 512 40x64 -> 80x128 x48f", "u3", (48, 40, 64), 512, 512, 0),
+    ("VAE up 512 40x64 -> 80x128 x48f subpixel", "u2", (48, 40, 64), 512, 512, 0),
+    ("VAE up 512 80x128 -> 160x256 x48f", "u3", (48, 80, 128), 512, 512, 0),
+    ("VAE up 512 80x128 -> 160x256 x48f subpixel", "u2", (48, 80, 128), 512, 512, 0),
+    ("VAE up 256 160x256 -> 320x512 x48f", "u3", (48, 160, 256), 256, 256, 0),
+    ("VAE up 256 160x256 -> 320x512 x48f subpixel", "u2", (48, 160, 256), 256, 256, 0),
 ]
 
 
@@ -83,6 +97,7 @@ def main():
     ap.add_argument("--tiles", default="", help="comma list of tile hints to time per shape (split 1), e.g. the ablation builds 40..64")
     ap.add_argument("--zeros", action="store_true", help="zero-filled operands: same instruction stream, no data toggling (how much of the time is the chip's power-limited clock?)")
     ap.add_argument("--presplit", action="store_true", help="bf16x3: hand the activation over in the producers' pre-split format (what the networks run)")
+    ap.add_argument("--up2-form", default=None, help="the sub-pixel Upsample rows: batch (one launch, the phase in the batch index) | phases (four launches); default ops.UP2_FORM")
     ap.add_argument("--ablate", type=int, default=0, help="bf16x3 only: 1 = skip the in-register operand split (wrong numbers; measures its cost)")
     args = ap.parse_args()
     ops.DEBUG_ABLATE = args.ablate
@@ -112,6 +127,24 @@ def main():
             r = torch.randn((M, N), device=dev).to(dt)
             xa = acast(x)
             fn = lambda tile=args.tile, split=args.split: ops.conv2d(xa, w, b, F=F_, Hin=H, Win=W, KH=3, KW=3, pad=1, residual=r, tile_hint=tile, split_k=split)
+        elif kind in ("u3", "u2"):
+            F_, H, W = geo
+            if kind == "u2" and not x3:
+                print(f"{name:34s} n/a (the sub-pixel form is a bf16x3 launch)")
+                continue
+            M, K = 4 * F_ * H * W, (9 if kind == "u3" else 4) * Cin
+            x = torch.randn((F_ * H * W, Cin), device=dev).to(dt)
+            w33 = torch.randn((N, Cin, 3, 3), device=dev) / (9 * Cin) ** 0.5
+            b = torch.randn((N,), device=dev)
+            xa = acast(x)
+            out = torch.empty((M, N), device=dev, dtype=dt)      # one output buffer: the decoder's maps are gigabytes
+            if kind == "u3":
+                w = wcast(w33.permute(0, 2, 3, 1).reshape(N, 9 * Cin))
+                fn = lambda tile=args.tile, split=args.split: ops.conv2d(xa, w, b, F=F_, Hin=H, Win=W, KH=3, KW=3, pad=1, ups=2, out=out, tile_hint=tile, split_k=split)
+            else:
+                w4 = pack.pack_conv2d_up2(w33, "bf16x3")
+                fn = lambda tile=args.tile, split=args.split: ops.conv2d_up2(xa, w4, b, F=F_, Hin=H, Win=W, out=out, tile_hint=tile, form=args.up2_form)
+            del w33
         elif kind == "t3":
             T, HW = geo
             M, K = T * HW, 3 * Cin
@@ -129,6 +162,10 @@ def main():
             xa = acast(x)
             so = bool(x3 and args.presplit and kind == "geglu")      # the network's GEGLU writes the pre-split format for the ff-out GEMM
             fn = lambda tile=args.tile, split=args.split: ops.linear(xa, w, b, act=act, tile_hint=tile, split_k=split, split_out=so)
+        if kind == "u2":       # (ops.conv2d_up2 asks its own plan query; a configuration it refuses raises at the launch)
+            takes = lambda tile, split: split == 1 and tile in ops._UP2_TILES
+        else:
+            takes = lambda tile, split, fn=fn: plan_takes(fn, tile=tile, split=split)
         def timeit(**kw):
             for _ in range(2):
                 fn(**kw)
@@ -170,7 +207,7 @@ def main():
             res = []
             for tile in (1, 2, 3, 4, 11, 13, 16, 17):
                 for split in (1, 2, 4, 8):
-                    if plan_takes(fn, tile=tile, split=split):
+                    if takes(tile, split):
                         res.append((timeit(tile=tile, split=split), tile, split))
             res.sort()
             print("    auto %.1f us | best: %s" % (us, "  ".join("t%d/s%d %.1f" % (t, s2, u) for u, t, s2 in res[:6])))
@@ -178,7 +215,7 @@ def main():
         if args.explore_all:
             res = []
             for tile, split in ops._CANDIDATES:
-                if plan_takes(fn, tile=tile, split=split):
+                if takes(tile, split):
                     res.append((timeit(tile=tile, split=split), tile, split))
             res.sort()
             fin = {(t, s2): u for u, t, s2 in res[:6]}
@@ -197,7 +234,7 @@ def main():
             row = []
             for t in args.tiles.split(","):
                 t, _, sp = t.partition("/")          # "71" or "71/2" (tile / split)
-                if plan_takes(fn, tile=int(t), split=int(sp or 1)):
+                if takes(int(t), int(sp or 1)):
                     row.append("t%s%s %.1f" % (t, "/" + sp if sp else "", timeit(tile=int(t), split=int(sp or 1))))
                 else:
                     row.append("t%s n/a" % t)
@@ -207,7 +244,7 @@ def main():
                 res = []
                 for tile in tiles:
                     for split in (1, 2, 4, 8):
-                        if plan_takes(fn, tile=tile, split=split):
+                        if takes(tile, split):
                             res.append((timeit(tile=tile, split=split), tile, split))
                 return sorted(res)
             v1, v2 = sweep((1, 2, 3, 4, 11, 13, 16, 17)), sweep(list(range(21, 30)) + [31, 33, 34, 35, 39])
