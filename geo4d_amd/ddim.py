@@ -91,6 +91,18 @@ class DDIMSampler(object):
                      for k, v in sorted(c.items()))
 
     @staticmethod
+    def _check_rows(name, c, batch_size):
+        """Every tensor of a guidance conditioning has one row per sample of the batch."""
+        if c is None:
+            return
+        items = c.items() if isinstance(c, dict) else [(None, c)]
+        for k, v in items:
+            for t in (v if isinstance(v, (list, tuple)) else [v]):
+                if torch.is_tensor(t) and t.shape[0] != batch_size:
+                    where = name if k is None else f"{name}[{k!r}]"
+                    raise ValueError(f"DDIMSampler.sample: {where} has {t.shape[0]} rows, batch_size is {batch_size}")
+
+    @staticmethod
     def _clone_cond(c):
         if not isinstance(c, dict):
             return None if c is None else c.detach().clone()
@@ -154,6 +166,11 @@ class DDIMSampler(object):
             raise ValueError("mask and x0 go together (ddim.py:174-175)")
         if self.model.parameterization != "v":
             raise NotImplementedError("only the v-parameterisation of configs/inference_geo4d.yaml:43 is built")
+        if unconditional_conditioning is not None and unconditional_guidance_scale != 1.:
+            # the evaluations of a guided step are batched row by row with the latent: a conditioning with another row count would raise deep
+            # inside the U-Net or, on a graph refresh, broadcast silently in _fill_cat. Refused here, before any buffer exists.
+            self._check_rows("unconditional_conditioning", unconditional_conditioning, batch_size)
+            self._check_rows("unconditional_conditioning_img_nonetext", kwargs.get("unconditional_conditioning_img_nonetext"), batch_size)
         gen = kwargs.pop("noise_generator", None)
         strict_rng = bool(kwargs.pop("strict_rng", False))
         noise_seeds, noise_draw = kwargs.pop("noise_seeds", None), int(kwargs.pop("noise_draw", 0))

@@ -106,6 +106,39 @@ def get_latent_z(model, videos):
 
 
 @torch.no_grad()
+def unconditional_parts(model, ctx, videos):
+    """test_geo4d.py:171-183, the pieces that do not depend on the conditional context beyond its shape: (text embedding of "" |
+    zeros, Resampler over the image tower's tokens of a ZERO image). ``ctx`` [B, n_text + 16 T, D] is the conditional context,
+    ``videos`` [B,3,T,H,W] the frames it was built for. With ``model.cross_attention`` False neither piece depends on the frames'
+    values, so one call serves every window of a clip."""
+    if model.cross_attention:
+        b, c, t, h, w = videos.shape
+        emb = model.embedder(torch.zeros((b * t, c, h, w), device=videos.device, dtype=videos.dtype))
+        uc_img_emb = model.image_proj_model(emb.reshape(b, t, emb.shape[1], emb.shape[2]))
+    else:
+        uc_img_emb = model.image_proj_model(model.embedder(torch.zeros_like(videos[:, :, 0])))
+    n_text = ctx.shape[1] - uc_img_emb.shape[1]
+    if model.uncond_type == "empty_seq":
+        uc_emb = model.get_learned_conditioning([""] * ctx.shape[0]).to(uc_img_emb.device)
+    elif model.uncond_type == "zero_embed":
+        uc_emb = torch.zeros_like(ctx[:, :n_text])
+    else:
+        raise NotImplementedError(f"uncond_type = {model.uncond_type!r}")
+    return uc_emb, uc_img_emb
+
+
+@torch.no_grad()
+def unconditional_contexts(model, ctx, videos, parts=None):
+    """The cross-attention contexts of the unconditional evaluations of classifier-free guidance (test_geo4d.py:171-195), from the
+    model's front-end: ``(text "" + zero image, text "" + the CONDITIONAL image tokens ctx[:, n_text:])`` - the second is the third
+    evaluation of 3-way guidance (``multiple_cond_cfg``). The one place they are built: ``image_guided_synthesis`` (context built
+    there) and ``run_clip`` (context supplied per window) both call it. ``parts`` = a result of ``unconditional_parts`` to reuse."""
+    uc_emb, uc_img_emb = unconditional_parts(model, ctx, videos) if parts is None else parts
+    n_text = ctx.shape[1] - uc_img_emb.shape[1]
+    return torch.cat([uc_emb, uc_img_emb], dim=1), torch.cat([uc_emb, ctx[:, n_text:]], dim=1)
+
+
+@torch.no_grad()
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing='uniform',
@@ -150,25 +183,11 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         if isinstance(c, dict) and "c_concat" not in c and "c_concat" in cond:
             c = dict(c, c_concat=cond["c_concat"])
         return c
-    parts = {}
+    parts = []
     def uncond_parts():
-        """test_geo4d.py:171-183: (text embedding of "" | zeros, Resampler over the image tower's tokens of a ZERO image, the conditional
-        image tokens). Computed once per call, and only when a dict has to be built."""
+        """The two unconditional contexts of ``unconditional_contexts``. Computed once per call, and only when a dict has to be built."""
         if not parts:
-            if model.cross_attention:
-                b, c, t, h, w = videos.shape
-                emb = model.embedder(torch.zeros((b * t, c, h, w), device=videos.device, dtype=videos.dtype))
-                uc_img_emb = model.image_proj_model(emb.reshape(b, t, emb.shape[1], emb.shape[2]))
-            else:
-                uc_img_emb = model.image_proj_model(model.embedder(torch.zeros_like(videos[:, :, 0])))
-            n_text = own_ctx.shape[1] - uc_img_emb.shape[1]
-            if model.uncond_type == "empty_seq":
-                uc_emb = model.get_learned_conditioning([""] * batch_size).to(uc_img_emb.device)
-            elif model.uncond_type == "zero_embed":
-                uc_emb = torch.zeros_like(own_ctx[:, :n_text])
-            else:
-                raise NotImplementedError(f"uncond_type = {model.uncond_type!r}")
-            parts.update(uc_emb=uc_emb, uc_img_emb=uc_img_emb, img_emb=own_ctx[:, n_text:])
+            parts.extend(unconditional_contexts(model, own_ctx, videos))
         return parts
     uc = None
     if unconditional_guidance_scale != 1.0:
@@ -176,16 +195,14 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         if uc is None:
             if own_ctx is None:
                 raise NotImplementedError("CFG with a caller-supplied `cond` needs the unconditional conditioning passed as well")
-            p = uncond_parts()
-            uc = {"c_crossattn": [torch.cat([p["uc_emb"], p["uc_img_emb"]], dim=1)]}
+            uc = {"c_crossattn": [uncond_parts()[0]]}
         uc = with_latent(uc)
     if multiple_cond_cfg and cfg_img != 1.0 and uc is not None:
         if kwargs.get("unconditional_conditioning_img_nonetext") is None:
             if own_ctx is None:
                 raise NotImplementedError("multiple_cond_cfg with a caller-supplied `cond` needs unconditional_conditioning_img_nonetext "
                                           "passed as well")
-            p = uncond_parts()      # image yes, text "" (test_geo4d.py:191-195)
-            kwargs["unconditional_conditioning_img_nonetext"] = {"c_crossattn": [torch.cat([p["uc_emb"], p["img_emb"]], dim=1)]}
+            kwargs["unconditional_conditioning_img_nonetext"] = {"c_crossattn": [uncond_parts()[1]]}      # image yes, text ""
         kwargs["unconditional_conditioning_img_nonetext"] = with_latent(kwargs["unconditional_conditioning_img_nonetext"])
     else:
         kwargs.update({"unconditional_conditioning_img_nonetext": None})
@@ -212,7 +229,7 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
              unconditional_guidance_scale=1.0, fs=24, timestep_spacing="uniform_trailing", guidance_rescale=0.7,
              prompts=("Output a video that assigns each 3D location in the world a consistent color.",),
              synthesize=None, gather=True, with_cameras=False, decode="local", decoder=None, window_batch=1, step_noise="torch",
-             **kwargs):
+             uncond_context=None, uncond_context_img_nonetext=None, **kwargs):
     """The window loop of ``run_inference`` (test_geo4d.py:396-443), data-parallel over windows.
 
     ``videos_all`` [1,3,T,H,W] in [-1,1]; ``context`` = cross-attention context [1, 77+16*video_length, D] (the OpenCLIP /
@@ -242,7 +259,15 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
     window at a time); "device" - it is made inside the fused update kernel by the counter-based generator of ``geo4d_amd.noise``, keyed
     by the same per-window seed (``noise_seeds``): the stochastic step is captured into the hipGraph like the deterministic one,
     ``window_batch`` applies at eta > 0, and a window's noise cannot depend on what it was batched with. x_T stays the per-window CPU
-    draw in both."""
+    draw in both.
+
+    Classifier-free guidance (``unconditional_guidance_scale != 1``): ``uncond_context`` and, for 3-way guidance (``multiple_cond_cfg=True``
+    with ``cfg_img != 1``), ``uncond_context_img_nonetext`` are the cross-attention contexts of the unconditional evaluations, each a tensor
+    [1, L, D] or a callable ``(window_frames) -> [1, L, D]`` like ``context``. The 1-row dicts ``unconditional_conditioning`` /
+    ``unconditional_conditioning_img_nonetext`` are accepted through ``**kwargs`` as before. With neither, the contexts are built from the
+    model's front-end by ``unconditional_contexts`` (once per clip for what does not depend on the window); a model without one raises
+    ``ValueError``. Every conditioning dict handed to ``synthesize`` has one row per window of the batch (1-row inputs are repeated, callables
+    evaluated per window), so ``window_batch`` applies under guidance exactly as without. With guidance off none of this is looked at."""
     from . import dist as gdist
     synthesize = synthesize or image_guided_synthesis
     if step_noise not in ("torch", "device"):
@@ -259,6 +284,52 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
     noise_shape = [B, channels, video_length, H // 8, W // 8]
     local, traj = [], []
 
+    # classifier-free guidance: where each unconditional dict comes from - a caller's tensor / callable / 1-row dict, or BUILD (the front-end)
+    BUILD = object()
+    guide, built = {}, {}
+    if unconditional_guidance_scale != 1.0:
+        three_way = bool(kwargs.get("multiple_cond_cfg")) and kwargs.get("cfg_img") != 1.0
+        for name, arg, needed in (("unconditional_conditioning", uncond_context, True),
+                                  ("unconditional_conditioning_img_nonetext", uncond_context_img_nonetext, three_way)):
+            src = kwargs.pop(name, None)
+            if src is not None and arg is not None:
+                raise ValueError(f"run_clip: pass either {name} or its context argument, not both")
+            src = arg if arg is not None else src
+            if src is None and needed:
+                if not (hasattr(model, "embedder") and hasattr(model, "image_proj_model")):
+                    raise ValueError("run_clip: guidance is on and the model has no conditioning front-end to build the unconditional contexts "
+                                     "from: pass uncond_context (and, for 3-way guidance, uncond_context_img_nonetext)")
+                src = BUILD
+            if src is not None:
+                guide[name] = src
+
+    def guidance(ctxs, vids):
+        """The unconditional dicts of one ``synthesize`` call, one row per window of the group (in window order); {} with guidance off."""
+        k, out = len(vids), {}
+        if any(src is BUILD for src in guide.values()):
+            if not model.cross_attention and "parts" not in built:      # "" / zero image: the same for every window of the clip
+                built["parts"] = unconditional_parts(model, ctxs[0], vids[0])
+            pairs = [unconditional_contexts(model, c, v, parts=built.get("parts")) for c, v in zip(ctxs, vids)]
+
+        def rows(name, t):
+            if t.shape[0] == k:
+                return t
+            if t.shape[0] != 1:
+                raise ValueError(f"run_clip: {name} has {t.shape[0]} rows (expected 1, or one per window of the batch: {k})")
+            return t.repeat((k,) + (1,) * (t.dim() - 1))
+        for name, src in guide.items():
+            if isinstance(src, dict):
+                out[name] = src if k == 1 else {key: [rows(name, t) for t in v] if isinstance(v, (list, tuple)) else rows(name, v)
+                                                for key, v in src.items()}
+            elif src is BUILD:
+                which = 0 if name == "unconditional_conditioning" else 1
+                out[name] = {"c_crossattn": [torch.cat([p[which] for p in pairs], 0)]}
+            elif callable(src):
+                out[name] = {"c_crossattn": [torch.cat([src(v) for v in vids], 0)]}
+            else:
+                out[name] = {"c_crossattn": [rows(name, src)]}
+        return out
+
     def cameras(maps):
         from .rays import raymap_to_camera_matrix
         return raymap_to_camera_matrix(maps[:, 4:7], maps[:, 7:10])[None]
@@ -273,6 +344,7 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
         elif ddim_eta > 0.0 and videos_all.is_cuda:   # per-window device stream for the stochastic step noise (eta > 0)
             kwargs["noise_generator"] = torch.Generator(device=videos_all.device).manual_seed(wseed)
         ctx = context(videos) if callable(context) else context
+        extra.update(guidance([ctx], [videos]))
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(wseed)                                   # posterior sampling noise of the VAE encode
             maps = synthesize(model, list(prompts), videos, noise_shape, n_samples=1, ddim_steps=ddim_steps, ddim_eta=ddim_eta,
@@ -306,6 +378,7 @@ def run_clip(model, videos_all, context, *, pointmap_vae=None, stride=4, video_l
         extra = {} if decode_here else {"decode": False}
         if step_noise == "device":
             extra["noise_seeds"] = wseeds
+        extra.update(guidance(ctxs, vids))
         maps = synthesize(model, list(prompts) * len(wis), torch.cat(vids, 0), [len(wis)] + noise_shape[1:], n_samples=1, ddim_steps=ddim_steps,
                           ddim_eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale, fs=fs, timestep_spacing=timestep_spacing,
                           guidance_rescale=guidance_rescale, pointmap_vae=pointmap_vae, cond=cond, x_T=torch.cat(xs, 0).to(videos_all.device),

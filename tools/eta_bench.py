@@ -4,7 +4,7 @@ default size (one 16 x 320 x 512 window, bf16x3m, random weights): ms per DDIM s
   (a) eta 1, torch.randn step noise: eager steps (the behaviour without noise_seeds),
   (b) eta 1, noise_seeds: counter-based noise made in the update kernel, the step captured into a hipGraph,
   (c) eta 0, captured (orientation: (b) should land at (c) + the noise arithmetic),
-without guidance and with 2-way CFG 7.5, plus (b) and (c) at two windows per batch as denoised latent frames/s.
+without guidance and with 2-way CFG 7.5, plus (b) and (c) at two windows per batch, unguided and guided, as denoised latent frames/s.
 One process, one GPU; two passes over the variants, each variant warmed up by one full call and then timed `repeats` times with HIP events
 around a call of S steps; the table quotes the median of a variant's calls and their spread. Same-process pairs only (box-to-box spread: README).
 usage (GPU box): python tools/eta_bench.py [steps] [repeats] [--out table.md]"""
@@ -56,6 +56,10 @@ def main():
                  (f"(c) eta 0, captured [{tag}]", variant(0.0, False, cfg), 1)]
     rows += [("(b) eta 1, noise_seeds, captured, 2 windows per batch [CFG 1]", variant(1.0, True, False, 2), 2),
              ("(c) eta 0, captured, 2 windows per batch [CFG 1]", variant(0.0, False, False, 2), 2)]
+    # guided clips batch windows too (run_clip hands every conditioning dict one row per window): the step is then ONE forward of 2 x 2 rows.
+    # Compare with the one-window guided rows (b) / (c) above - the same process, the same guidance
+    rows += [("(b) eta 1, noise_seeds, captured, 2 windows per batch [2-way CFG 7.5]", variant(1.0, True, True, 2), 2),
+             ("(c) eta 0, captured, 2 windows per batch [2-way CFG 7.5]", variant(0.0, False, True, 2), 2)]
     # A variant's calls run back to back after a warm-up call of its own (which packs weights, fills the context K/V cache and captures
     # the step): the eager guided variant allocates new K/V buffers per call, and an eviction from the U-Net's K/V cache makes every
     # sampler capture again, which must not land in another variant's timed call. Two passes over the list expose drift.
