@@ -180,6 +180,10 @@ SIGNATURES = {
                                         C.c_size_t, C.c_void_p, C.c_void_p]),
     "geo4d_align_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "geo4d_align_residual": (C.c_int, [C.POINTER(Align), C.c_void_p]),
+    "geo4d_align_pp_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "geo4d_align_residual_pp": (C.c_int, [C.POINTER(Align), C.c_void_p, C.c_void_p]),
+    "geo4d_align_set_pp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "geo4d_align_pp_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "geo4d_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float,
                                   C.c_int, C.c_void_p]),
     "geo4d_adam_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_float, C.c_float, C.c_float,

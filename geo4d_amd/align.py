@@ -36,6 +36,11 @@ From iteration ``depth_traj_start_iter`` (150) on the reference adds two terms (
     16 4x4 matrices per window, host side); the term itself is tiny-tensor autograd like the smoothing term.
 s_depth / t_depth / traj_align_poses join Adam when their terms start (torch skips parameters without gradients, so their moments
 and bias corrections count from the start iteration — reproduced with a second hyper-parameter table).
+
+Principal points (optimizer_group.py:37, 67-68, 137-167, 203-219): the image centre by default, with no trace in the parameters or the
+launches; ``optimize_pp=True`` adds ``im_pp`` [n, 2] (principal point = centre + 10 im_pp) to the optimised parameters - the residual
+kernel's principal-point form sums dL/dpp per image in the same pass -, ``preset_principal_point`` / ``preset_intrinsics`` set and freeze
+them. ``get_principal_points()`` is what the geometry, the intrinsics, the export and the initialisations read.
 """
 import ctypes as C
 import math
@@ -172,11 +177,13 @@ class GroupAligner:
     MAX_SLOTS = 6          # csrc/align.hip MAXS: windows per image the fused residual kernel unrolls
 
     def __init__(self, groups, pred, conf, shared_focal=True, temporal_smoothing_weight=0.0, translation_weight=0.1, base_scale=0.5,
-                 conf_clamp=10.0, chunk_pixels=4096, inverse_depth=None, traj=None, depth_traj_start_iter=150, shard=None):
+                 conf_clamp=10.0, chunk_pixels=4096, inverse_depth=None, traj=None, depth_traj_start_iter=150, shard=None, optimize_pp=False):
         """groups: list of G lists of S image indices; pred [G, S, H, W, 3], conf [G, S, H, W] fp32 on the HIP device;
         inverse_depth [G, S, H, W(, 1)] (the decoded inverse-depth modality mapped to [0, 1]) and traj [G, S, 4, 4] (every window's
         camera-to-world matrices in its own frame, N2) switch the two late terms on (pred_pts['inverse_depthmap'] / ['traj'],
-        scripts/evaluation/test_geo4d.py:498-501)."""
+        scripts/evaluation/test_geo4d.py:498-501). optimize_pp: one principal point per image, (W/2, H/2) + 10 im_pp, optimised with the
+        other camera parameters (optimizer_group.py:37, 67-68, 210-211); off (default), and without a preset_principal_point, there is no
+        `im_pp` parameter at all and every camera keeps the image centre."""
         if not pred.is_cuda:
             raise _lib.Geo4DNativeError("geo4d_amd.align.GroupAligner runs only on a HIP device (there is no CPU fallback)")
         self.lib = _lib.load()
@@ -226,7 +233,11 @@ class GroupAligner:
         self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
         self._img_sums, self._slot_sums = z(self.n, 14), z(G * S, 14)
         self._grad_ld = z(self.n, H * W)
-        self._pp = torch.tensor([W / 2, H / 2], device=self.dev)
+        self._pp = torch.tensor([W / 2, H / 2], device=self.dev)       # the image centre; the principal points: get_principal_points()
+        self.optimize_pp = bool(optimize_pp)
+        if self.optimize_pp:
+            self.P["im_pp"] = z(self.n, 2)
+        self._pp_sums = None                     # [n, 2] dL/dpp of the residual kernel's principal-point form (made on first use)
         self.invdepth = None if inverse_depth is None else inverse_depth.reshape(G * S, H * W).float().contiguous()
         self.traj = None if traj is None else traj.reshape(G, S, 4, 4).float().to(self.dev)
         self.start_iter = depth_traj_start_iter
@@ -252,7 +263,90 @@ class GroupAligner:
         keys = ("s_depth", "t_depth") if self.invdepth is not None else ()
         return keys + (("traj_align_poses",) if self.traj is not None and len(self.state["valid_traj_groups"]) else ())
 
+    def _pp_grad_on(self):
+        """True when the principal points are optimised: `im_pp` exists and no preset froze it."""
+        return "im_pp" in self.P and "im_pp" not in self.frozen
+
+    def _get_msk_indices(self, msk):
+        """optimizer_group.py:169-182: None = every image, an int, a list / array of indices, or a boolean mask of length n."""
+        if msk is None:
+            return list(range(self.n))
+        if isinstance(msk, int):
+            return [msk]
+        m = np.asarray(msk.cpu() if torch.is_tensor(msk) else msk)
+        if m.dtype == np.bool_:
+            if len(m) != self.n:
+                raise ValueError(f"msk: a boolean mask must have one entry per image ({self.n}), got {len(m)}")
+            return np.where(m)[0].tolist()
+        if np.issubdtype(m.dtype, np.integer):
+            idx = m.reshape(-1).tolist()
+            if any(i < 0 or i >= self.n for i in idx):
+                raise ValueError(f"msk: image indices must lie in [0, {self.n})")
+            return idx
+        raise ValueError(f"bad msk={msk!r}")
+
+    def preset_principal_point(self, known_pp, msk=None):
+        """Set the principal points of the images `msk` selects to `known_pp` ([k, 2] pixels, or a list of k pairs) and freeze ALL of them
+        (optimizer_group.py:159-167, 203-208: im_pp = (pp - (W/2, H/2)) / 10, then im_pp.requires_grad_(False)). Unlike the reference this
+        works without optimize_pp: there `_no_grad` asserts that the parameter still requires a gradient, which im_pp never does with
+        optimize_pp=False - an accident of how the reference marks "not yet set", not a rule about principal points."""
+        idx = self._get_msk_indices(msk)
+        pp = torch.as_tensor(np.asarray([np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64) for v in known_pp])
+                             if isinstance(known_pp, (list, tuple)) else known_pp).detach().to("cpu", torch.float32)
+        if pp.dim() != 2 or tuple(pp.shape) != (len(idx), 2):
+            raise ValueError(f"preset_principal_point: expected [{len(idx)}, 2] pixel coordinates, got shape {tuple(pp.shape)}")
+        if not bool(torch.isfinite(pp).all()):
+            raise ValueError("preset_principal_point: non-finite principal point")
+        if "im_pp" not in self.P:
+            self.P["im_pp"] = torch.zeros(self.n, 2, device=self.dev)
+        self.P["im_pp"][torch.as_tensor(idx, dtype=torch.long, device=self.dev)] = ((pp - self._pp.cpu()) / 10).to(self.dev)
+        self.frozen.add("im_pp")
+        return self
+
+    def preset_focal(self, known_focals, msk=None):
+        """optimizer_group.py:146-157 with requires_grad=False: focals in pixels for the images `msk` selects; the shared focal takes their
+        mean. Frozen when every image was given (as the reference freezes); init_from_group then keeps them."""
+        idx = self._get_msk_indices(msk)
+        f = torch.as_tensor([float(v) for v in known_focals], dtype=torch.float32)
+        if f.numel() != len(idx) or not bool((torch.isfinite(f) & (f > 0)).all()):
+            raise ValueError(f"preset_focal: expected {len(idx)} positive focals")
+        if self.shared_focal:
+            self.P["im_focals"][:] = FOCAL_BREAK * math.log(float(f.mean()))
+        else:
+            self.P["im_focals"][torch.as_tensor(idx, dtype=torch.long, device=self.dev), 0] = (FOCAL_BREAK * torch.log(f)).to(self.dev)
+        if len(idx) == self.n:
+            self.frozen.add("im_focals")
+        return self
+
+    def preset_intrinsics(self, known_intrinsics, msk=None, use_pp=False):
+        """optimizer_group.py:137-144: focal = mean of each K's diagonal, frozen (preset_focal); the principal point K[:2, 2] as well when
+        optimize_pp is on (the reference's rule) or `use_pp` is passed."""
+        K = torch.as_tensor(known_intrinsics).detach().float().cpu() if not isinstance(known_intrinsics, (list, tuple)) else \
+            torch.stack([torch.as_tensor(k).detach().float().cpu() for k in known_intrinsics])
+        if K.dim() == 2:
+            K = K[None]
+        if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3):
+            raise ValueError(f"preset_intrinsics: expected [k, 3, 3], got shape {tuple(K.shape)}")
+        self.preset_focal([float((k[0, 0] + k[1, 1]) / 2) for k in K], msk)
+        if self.optimize_pp or use_pp:
+            self.preset_principal_point(K[:, :2, 2], msk)
+        return self
+
     # ---- parameter -> geometry (tiny device tensors, differentiable) -----------------------------------------------------------
+    def get_principal_points(self):
+        """[n, 2] pixels: (W/2, H/2) + 10 im_pp (optimizer_group.py:210-211); the image centre for every image when there is no im_pp."""
+        if "im_pp" not in self.P:
+            return self._pp.expand(self.n, 2)
+        return self._pp + 10 * self.P["im_pp"]
+
+    def _init_pp(self, idx=None):
+        """What the initialisations hand on as `pp`: None (= the image centre, today's path untouched) without im_pp, else the principal
+        points [n, 2] or, with an image index, that image's [2]."""
+        if "im_pp" not in self.P:
+            return None
+        pp = self.get_principal_points().detach()
+        return pp if idx is None else pp[idx]
+
     def get_focals(self):
         lf = self.P["im_focals"]
         return (lf.expand(self.n, 1) / FOCAL_BREAK).exp()
@@ -289,7 +383,7 @@ class GroupAligner:
         ys, xs = torch.meshgrid(torch.arange(self.H, device=self.dev), torch.arange(self.W, device=self.dev), indexing="ij")
         grid = torch.stack([xs, ys], -1).reshape(1, -1, 2).float()
         d = self.P["im_depthmaps"].exp().unsqueeze(-1)
-        cam = torch.cat([d * (grid - self._pp) / f, d], -1)
+        cam = torch.cat([d * (grid - self.get_principal_points()[:, None]) / f, d], -1)
         return (cam @ R.transpose(1, 2) + t[:, None]).reshape(self.n, self.H, self.W, 3)
 
     # ---- scene state of the export (base_opt_group.py:160-170, 237-242, 327-331, 353-359, 371-381; optimizer_group.py:213-219) ----
@@ -334,11 +428,11 @@ class GroupAligner:
         return (self.init_conf_maps if self.thr_for_init_conf else self.im_conf) > self.min_conf_thr
 
     def get_intrinsics(self):
-        """[n, 3, 3]: the focals on the diagonal, principal point (W/2, H/2)."""
+        """[n, 3, 3]: the focals on the diagonal, the principal points of get_principal_points() ((W/2, H/2) unless optimised or preset)."""
         K = torch.zeros((self.n, 3, 3), device=self.dev)
         f = self.get_focals().detach().flatten()
         K[:, 0, 0] = K[:, 1, 1] = f
-        K[:, :2, 2] = self._pp
+        K[:, :2, 2] = self.get_principal_points().detach()
         K[:, 2, 2] = 1
         return K
 
@@ -385,8 +479,20 @@ class GroupAligner:
         sm.smooth_weight, sm.translation_weight = (self.tsw if self.primary else 0.0), self.tw
         return sm
 
+    def _pp_buffers(self):
+        """The principal-point form's extra state, made on first use (before any capture: the loop's first iteration is eager): the
+        [n, 2] sums and a workspace with room for their per-chunk partials."""
+        if self._pp_sums is None:
+            self._pp_sums = torch.zeros(self.n, 2, device=self.dev)
+            need = self.lib.geo4d_align_pp_workspace(self.n, self.G * self.S, self.H, self.W, self.chunk)
+            if self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
     def loss_and_grads(self):
         """Returns (loss 0-dim device tensor, dict of gradients shaped like self.P; parameters of terms that are off are absent).
+        With principal points (optimize_pp or a preset) one more launch writes every image's own (ppx, ppy) into cams after the refresh;
+        while they are optimised the residual kernel runs in its principal-point form (two more image sums, one more reduction) and a
+        last small launch scales the sums to dL/dim_pp.
         Five launches: parameters -> cams / window transforms / (s, t) per slot (align_refresh), the fused residual kernel + its two
         fixed-order reductions, gradient sums -> parameter gradients (align_small_grads: the chain rule through quaternions / signed-log
         translations / log focal / normalised log scales, the temporal-smoothing term and the trajectory term, csrc/align_small.hip). `GEO4D_ALIGN_CHAIN=torch` selects round 2's autograd chain instead."""
@@ -415,6 +521,14 @@ class GroupAligner:
                 sm.slot_img, sm.img_slot_ptr, sm.img_slot_idx = self.slot_img.data_ptr(), self._img_slot_ptr.data_ptr(), self._img_slot_idx.data_ptr()
                 sm.grad_traj, sm.traj_weight = self._small_grads["traj_align_poses"].data_ptr(), 0.005
         _lib.check(self.lib.geo4d_align_refresh(C.byref(sm), ops._stream()), "geo4d_align_refresh")
+        pp_on = self._pp_grad_on()
+        if "im_pp" in self.P:                                      # per-image principal points over the centre the refresh wrote
+            _lib.check(self.lib.geo4d_align_set_pp(self._cams.data_ptr(), self.P["im_pp"].data_ptr(), self.n, self.W / 2, self.H / 2, ops._stream()),
+                       "geo4d_align_set_pp")
+        if pp_on:
+            self._pp_buffers()
+            if "im_pp" not in self._small_grads:
+                self._small_grads["im_pp"] = z(self.n, 2)
         a = _lib.Align()
         a.pred, a.conf, a.logdepth, a.cams, a.slot_trf = self.pred.data_ptr(), self.conf.data_ptr(), self.P["im_depthmaps"].data_ptr(), self._cams.data_ptr(), self._trf.data_ptr()
         a.slot_ptr, a.slot_idx = self.slot_ptr.data_ptr(), self.slot_idx.data_ptr()
@@ -424,11 +538,16 @@ class GroupAligner:
         a.conf_clamp, a.inv_area = self.conf_clamp, 1.0 / float(self.G * self.S * self.H * self.W)
         if depth_on:
             a.invdepth, a.slot_st, a.depth_weight = self.invdepth.data_ptr(), self._slot_st.data_ptr(), 2.0 * a.inv_area
-        _lib.check(self.lib.geo4d_align_residual(C.byref(a), ops._stream()), "geo4d_align_residual")
+        if pp_on:                                                  # the principal-point form: + dL/dpp per image, then dL/dim_pp = 10 dL/dpp
+            _lib.check(self.lib.geo4d_align_residual_pp(C.byref(a), self._pp_sums.data_ptr(), ops._stream()), "geo4d_align_residual_pp")
+            _lib.check(self.lib.geo4d_align_pp_grads(self._pp_sums.data_ptr(), self._small_grads["im_pp"].data_ptr(), self.n, ops._stream()),
+                       "geo4d_align_pp_grads")
+        else:
+            _lib.check(self.lib.geo4d_align_residual(C.byref(a), ops._stream()), "geo4d_align_residual")
         _lib.check(self.lib.geo4d_align_small_grads(C.byref(sm), ops._stream()), "geo4d_align_small_grads")
         loss = self._loss[0]
-        grads = {k: self._small_grads[k] for k in ("im_poses", "im_focals", "pw_poses") + (("s_depth", "t_depth") if depth_on else ())
-                 + (("traj_align_poses",) if traj_on else ())}
+        grads = {k: self._small_grads[k] for k in ("im_poses", "im_focals", "pw_poses") + (("im_pp",) if pp_on else ())
+                 + (("s_depth", "t_depth") if depth_on else ()) + (("traj_align_poses",) if traj_on else ())}
         grads["im_depthmaps"] = self._grad_ld
         if self.shard is not None:
             loss, grads = self.shard.reduce(loss, grads)        # one all-reduce: loss, small gradients, depth gradients of shared images
@@ -438,15 +557,17 @@ class GroupAligner:
         """Round 2's form of loss_and_grads: the chain rule from the gradient sums to the parameters by autograd over tiny tensors
         (~450 launches per iteration). Kept as the independent cross-check of csrc/align_small.hip (tests) and for A/B."""
         late = self._late_keys()
-        small = {k: self.P[k].detach().clone().requires_grad_(True) for k in ("im_poses", "im_focals", "pw_poses") + late}
+        pp_on = self._pp_grad_on()
+        small = {k: self.P[k].detach().clone().requires_grad_(True) for k in ("im_poses", "im_focals", "pw_poses") + (("im_pp",) if pp_on else ()) + late}
         saved, self.P = self.P, dict(self.P, **small)
         try:
             R, t = self.get_im_poses()
             f = self.get_focals()
             sR, st = self.get_pw_poses()
+            pp = self.get_principal_points()
         finally:
             self.P = saved
-        cams = torch.cat([R.reshape(self.n, 9), t, f, self._pp.expand(self.n, 2), torch.zeros(self.n, 1, device=self.dev)], 1).detach().contiguous()
+        cams = torch.cat([R.reshape(self.n, 9), t, f, pp, torch.zeros(self.n, 1, device=self.dev)], 1).detach().contiguous()
         trf = torch.cat([sR.reshape(self.G, 9), st], 1).detach()[self.slot_group].contiguous()
         a = _lib.Align()
         a.pred, a.conf, a.logdepth, a.cams, a.slot_trf = self.pred.data_ptr(), self.conf.data_ptr(), self.P["im_depthmaps"].data_ptr(), cams.data_ptr(), trf.data_ptr()
@@ -459,7 +580,12 @@ class GroupAligner:
         if depth_on:
             slot_st = torch.cat([small["s_depth"].detach(), small["t_depth"].detach(), self._depth_ok], 1)[self.slot_group].contiguous()
             a.invdepth, a.slot_st, a.depth_weight = self.invdepth.data_ptr(), slot_st.data_ptr(), 2.0 * a.inv_area
-        _lib.check(self.lib.geo4d_align_residual(C.byref(a), ops._stream()), "geo4d_align_residual")
+        if pp_on:
+            self._pp_buffers()
+            a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+            _lib.check(self.lib.geo4d_align_residual_pp(C.byref(a), self._pp_sums.data_ptr(), ops._stream()), "geo4d_align_residual_pp")
+        else:
+            _lib.check(self.lib.geo4d_align_residual(C.byref(a), ops._stream()), "geo4d_align_residual")
         I = self._img_sums
         # slot sums come back in CSR (image-major) order: put them in slot order, then add the S frames of each window
         # (with a shard only this rank's slots are listed: rows past n_local_slots are not written)
@@ -468,6 +594,8 @@ class GroupAligner:
         # chain rule through the tiny parameter -> matrix maps: d loss = <dL/dR, dR> + <dL/dt, dt> + dL/df df + <dL/dsR, dsR> + <dL/dst, dst>
         surrogate = (I[:, :9].reshape(self.n, 3, 3) * R).sum() + (I[:, 9:12] * t).sum() + (I[:, 12:13] * f).sum() + \
             (Ssum[:, :9].reshape(self.G, 3, 3) * sR).sum() + (Ssum[:, 9:12] * st).sum()
+        if pp_on:
+            surrogate = surrogate + (self._pp_sums * pp).sum()
         if depth_on:
             surrogate = surrogate + (Ssum[:, 12:13] * small["s_depth"]).sum() + (Ssum[:, 13:14] * small["t_depth"]).sum()
         eye = torch.eye(3, device=self.dev)
@@ -617,7 +745,7 @@ class GroupAligner:
             _lib.check(self.lib.geo4d_adam_step_dev(d.data_ptr(), grads["im_depthmaps"].data_ptr(), m.data_ptr(), v.data_ptr(), d.numel(),
                                                     hyper.data_ptr(), b1, b2, eps, ops._stream()), "geo4d_adam_step_dev")
             late = self._late_keys()
-            for k in ("im_poses", "im_focals", "pw_poses") + late:   # a few dozen numbers each: plain tensor ops, same formula
+            for k in ("im_poses", "im_focals", "pw_poses") + (("im_pp",) if self._pp_grad_on() else ()) + late:   # a few dozen numbers each
                 if k in self.frozen:
                     continue
                 g, (m, v), h = grads[k].contiguous(), mom[k], hyper_late if k in late else hyper
@@ -685,6 +813,8 @@ class GroupAligner:
         for hypothesis, the image chain enqueued without host copies; see _init_prefix / _init_pnp). Used by "pnp" and "prefix" only."""
         if pnp_backend not in ("host", "device"):
             raise ValueError(f"pnp_backend={pnp_backend!r}: 'host' or 'device'")
+        if focal is None and "im_focals" in self.frozen:         # preset_focal / preset_intrinsics before the initialisation: keep it
+            focal = float(self.get_focals()[0]) if self.shared_focal else self.get_focals().detach().flatten().clone()
         G, S, H, W = self.G, self.S, self.H, self.W
         pred = self.pred.reshape(G, S, H * W, 3)
         conf = self.conf.reshape(G, S, H * W)
@@ -725,13 +855,14 @@ class GroupAligner:
                 for k, i in enumerate(grp):
                     first.setdefault(i, (g, k))
             rm = raymaps.reshape(G, S, H, W, 3)
-            per_image = estimate_focal_weiszfeld(torch.stack([rm[g, k] for g, k in (first[i] for i in range(self.n))]).to(self.dev))
+            per_image = estimate_focal_weiszfeld(torch.stack([rm[g, k] for g, k in (first[i] for i in range(self.n))]).to(self.dev), pp=self._init_pp())
             per_image = torch.where(torch.isfinite(per_image) & (per_image > 0), per_image, torch.full_like(per_image, max(H, W) / (2.0 * math.tan(math.radians(30.0)))))
             self.init_focals = per_image
             focal = float(per_image.mean()) if self.shared_focal else per_image
         if focal is None:
             p0, ys, xs = pred[0, 0], *torch.meshgrid(torch.arange(H, device=self.dev), torch.arange(W, device=self.dev), indexing="ij")
-            u, v = (xs.reshape(-1).float() - W / 2), (ys.reshape(-1).float() - H / 2)
+            pp0 = self._init_pp(self.groups[0][0])                  # window 0's first image
+            u, v = (xs.reshape(-1).float() - (W / 2 if pp0 is None else pp0[0])), (ys.reshape(-1).float() - (H / 2 if pp0 is None else pp0[1]))
             ok = (p0[:, 2] > 1e-6) & (conf[0, 0] > 0.5)
             fx = (u * p0[:, 2] / p0[:, 0])[ok & (u.abs() > W / 8)]
             fy = (v * p0[:, 2] / p0[:, 1])[ok & (v.abs() > H / 8)]
@@ -778,6 +909,14 @@ class _DevicePnp:
         self.poses = torch.eye(4, device=scene.dev, dtype=torch.float64).repeat(scene.n, 1, 1)
         self.status = torch.full((G * S,), -1, device=scene.dev, dtype=torch.int32)          # -1: the slot was not solved
         self.delta = 0.03 * max(scene.H, scene.W)                                            # fast_pnp's -/+ 3 % of the image size
+        self.pp = None                                                                       # one principal point per call (geo4d_pnp_ransac's ppx, ppy)
+        pp = scene._init_pp()
+        if pp is not None:
+            pp = pp.cpu()
+            if bool((pp != pp[0]).any()):
+                raise ValueError("pnp_backend='device' takes ONE principal point per launch (geo4d_pnp_ransac's ppx, ppy), but the preset "
+                                 "principal points differ between images: use pnp_backend='host'")
+            self.pp = (float(pp[0, 0]), float(pp[0, 1]))
 
     def solve(self, slots, points, conf, base, focal_out, pose_out):
         """One launch for the `slots` (flat window * S + frame indices) with points [B, H W, 3], conf [B, H W], base focals [B] fp64."""
@@ -785,7 +924,7 @@ class _DevicePnp:
         sc, B = self.scene, len(slots)
         cand = torch.stack([base, -self.delta + base, self.delta + base], 1)                 # fast_pnp: [focal] + geomspace(-d + focal, d + focal, 2)
         _, _, status, _ = ops.pnp_ransac(points.reshape(B, sc.H, sc.W, 3), conf.reshape(B, sc.H, sc.W), cand, self.tables.rows(slots),
-                                         iterations=self.iterations, out=(focal_out, pose_out))
+                                         iterations=self.iterations, pp=self.pp, out=(focal_out, pose_out))
         if slots == list(range(slots[0], slots[0] + B)):
             self.status[slots[0]:slots[0] + B] = status
         else:
@@ -798,6 +937,12 @@ class _DevicePnp:
         status = host[:sc.G * sc.S].to(torch.int32).reshape(sc.G, sc.S)
         focals = [None if math.isnan(f) else f for f in host[sc.G * sc.S:].tolist()]
         return status, focals, [M.float() for M in self.poses]
+
+
+def host_pp(scene, i):
+    """Image i's principal point for the host PnP backend (pnp.fast_pnp's `pp`): None = the image centre when the scene has no im_pp."""
+    pp = scene._init_pp(i)
+    return None if pp is None else pp.cpu().numpy()
 
 
 def _record_pnp_status(self, status):
@@ -816,13 +961,17 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed, backend="host")
     G, S, H, W = self.G, self.S, self.H, self.W
     pts3d, conf_list, im_poses, im_focals = [None] * self.n, [None] * self.n, [None] * self.n, [None] * self.n
     rm = None if raymaps is None else raymaps.reshape(G, S, H, W, 3)
+
+    def ray_pp(i):                                                          # [1, 2] principal point of image i (None: the centre)
+        pp = self._init_pp(i)
+        return None if pp is None else pp[None]
     if backend == "device":
         dp = _DevicePnp(self, conf, niter_PnP, seed)
 
         def launch(g, ks, first_window):
             idx = torch.as_tensor([self.groups[g][k] for k in ks], device=self.dev)
             # per image, as the host path calls it: a batched reduction may round differently, and the candidates must be the same bits
-            base = (torch.cat([estimate_focal_weiszfeld(rm[g, k][None].to(self.dev)) for k in ks]).double() if rm is not None
+            base = (torch.cat([estimate_focal_weiszfeld(rm[g, k][None].to(self.dev), pp=ray_pp(self.groups[g][k])) for k in ks]).double() if rm is not None
                     else torch.full((len(ks),), float("nan"), device=self.dev, dtype=torch.float64))
             fo, po = base.clone(), dp.poses[idx]
             dp.solve([g * S + k for k in ks], torch.stack([pts3d[self.groups[g][k]] for k in ks]), conf[g, ks], base, fo, po)
@@ -850,11 +999,11 @@ def _init_pnp(self, pred, conf, focal, raymaps, niter_PnP, seed, backend="host")
     ok = torch.full((G, S), -1, dtype=torch.int32)
 
     def ray_focal(g, k):
-        return None if rm is None else float(estimate_focal_weiszfeld(rm[g, k][None].to(self.dev))[0])
+        return None if rm is None else float(estimate_focal_weiszfeld(rm[g, k][None].to(self.dev), pp=ray_pp(self.groups[g][k]))[0])
 
     def run_pnp(i, g, k):
         msk = (conf[g, k] > 0.5).reshape(H, W).cpu().numpy()
-        return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), im_focals[i], msk, niter_PnP=niter_PnP, seed=seed)
+        return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), im_focals[i], msk, pp=host_pp(self, i), niter_PnP=niter_PnP, seed=seed)
     done = set()
     for k, i in enumerate(self.groups[0]):                                  # the first window is the world frame
         pts3d[i], conf_list[i] = pred[0, k].clone(), conf[0, k].clone()
@@ -956,7 +1105,9 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed, backend="host"):
     device from the device-resident focal array the previous launch wrote (or left alone, when it failed: the earlier window's value
     stays), so between the masked-pixel counts copied up front and the status words copied at the end the PnP chain reads nothing back;
     the window registrations of step 2 keep their own 3 x 3 host solve. A start focal that is unset or unusable (where the host would
-    search 63 candidates) reruns the whole initialisation on the host. The `except` path of step 1 stays on the host."""
+    search 63 candidates) reruns the whole initialisation on the host. The `except` path of step 1 stays on the host.
+    Principal points: the PnP of step 3 (and of the `except` path) takes each image's own; step 1's focal / shift solve has no
+    principal-point argument (nor has the reference's point_map_to_depth) and stays centred - its focal is only PnP's first candidate."""
     from . import geometry, pnp
     G, S, H, W = self.G, self.S, self.H, self.W
     pts3d, conf_list, im_poses, im_focals = [None] * self.n, [None] * self.n, [None] * self.n, [None] * self.n
@@ -968,7 +1119,7 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed, backend="host"):
     self.prefix_focals_raw = host[0].clone()
     if bool((host[1] != 0).any()):
         res = pnp.fast_pnp(pred[0, 0].reshape(H, W, 3).double().cpu().numpy(), None, (conf[0, 0] > 0.5).reshape(H, W).cpu().numpy(),
-                           niter_PnP=niter_PnP, seed=seed)
+                           pp=host_pp(self, self.groups[0][0]), niter_PnP=niter_PnP, seed=seed)
         focal_group = [res[0] if res else max(H, W) / (2.0 * math.tan(math.radians(30.0)))] * G
     else:
         focal_group = filter_outlier_focals(host[0])[0].numpy().tolist()
@@ -976,7 +1127,7 @@ def _init_prefix(self, pred, conf, focal, niter_PnP, seed, backend="host"):
 
     def run_pnp(i, g, k, temp_focal):
         msk = (conf[g, k] > 0.5).reshape(H, W).cpu().numpy()
-        return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), temp_focal, msk, niter_PnP=niter_PnP, seed=seed)
+        return pnp.fast_pnp(pts3d[i].reshape(H, W, 3).double().cpu().numpy(), temp_focal, msk, pp=host_pp(self, i), niter_PnP=niter_PnP, seed=seed)
     done = set()
     dp = _DevicePnp(self, conf, niter_PnP, seed) if backend == "device" else None
     window_focals = torch.tensor(focal_group, dtype=torch.float64, device=self.dev) if dp else None
@@ -1028,7 +1179,7 @@ GroupAligner._init_prefix = _init_prefix
 
 def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03, align=True, intrinsics=None,
                       use_raymap=True, use_inverse_depthmap=True, use_traj=True, pointmap_vae_used=True, depth_traj_start_iter=150,
-                      sharded=None, pose_init="traj", imgs=None, pnp_backend="host"):
+                      sharded=None, pose_init="traj", imgs=None, pnp_backend="host", optimize_pp=False, principal_points=None):
     """The consumer of the gathered clip: ``post_optimization`` of scripts/evaluation/test_geo4d.py:30-51 with the pred_list its
     window loop builds (:446-501). ``slices`` / ``maps [n_windows, 11, T, H, W]`` / ``traj [n_windows, T, 4, 4]`` are what
     ``pipeline.run_clip(..., with_cameras=True)`` returns; ``args`` = the config's ``postprocess`` tree (a dict or any object with
@@ -1041,13 +1192,28 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
     kept as ``scene.imgs`` [n, H, W, 3] in [0, 1] (dust3r.utils.image.rgb) for the export (geo4d_amd/scene_export.py).
     ``pose_init``: "traj" (default, Plücker cameras), "pnp" (align_group, the reference's opt_raydir branch) or "prefix"
     (align_group_prefix, what the reference's script runs with its use_raymap = False): GroupAligner.init_from_group.
-    ``pnp_backend``: "host" (default) or "device", the RANSAC-PnP backend of the "pnp" and "prefix" initialisations."""
+    ``pnp_backend``: "host" (default) or "device", the RANSAC-PnP backend of the "pnp" and "prefix" initialisations.
+    ``optimize_pp``: optimise one principal point per image (the reference's ``optimize_pp``, forwarded to the optimiser by its
+    ``post_optimization(**kwargs)``), starting at the image centre unless preset. ``principal_points``: ``[n_images, 2]`` pixels, or
+    ``"intrinsics"`` = ``intrinsics[:, :2, 2]``: preset and frozen (``scene.preset_principal_point``) BEFORE the initialisation, the
+    reference's order. With both defaults the principal points stay at the image centre, also when ``intrinsics`` is passed."""
     from .pipeline import postprocess_window
+    groups = [list(range(s.start, s.stop)) for s in slices]
+    n_images = 1 + max(max(g) for g in groups)
+    if isinstance(principal_points, str):
+        if principal_points != "intrinsics":
+            raise ValueError(f"principal_points={principal_points!r}: an [n_images, 2] array of pixels or 'intrinsics'")
+        if intrinsics is None:
+            raise ValueError("principal_points='intrinsics' needs intrinsics")
+        principal_points = torch.as_tensor(intrinsics)[:, :2, 2]
+    if principal_points is not None:
+        principal_points = torch.as_tensor(principal_points).detach().float().cpu()
+        if tuple(principal_points.shape) != (n_images, 2):
+            raise ValueError(f"principal_points: expected [{n_images}, 2] pixel coordinates, got shape {tuple(principal_points.shape)}")
     get = (lambda k, d: args.get(k, d)) if isinstance(args, dict) else (lambda k, d: getattr(args, k, d))
     if args is None:
         get = lambda k, d: d
     post = [postprocess_window(m[None], pointmap_vae_used=pointmap_vae_used) for m in maps]
-    groups = [list(range(s.start, s.stop)) for s in slices]
     conf = torch.stack([p["conf"][..., 0] for p in post])
     if not conf_optimize:
         conf = torch.ones_like(conf)
@@ -1060,7 +1226,9 @@ def post_optimization(slices, maps, traj, args=None, conf_optimize=True, lr=0.03
                          shared_focal=not get("not_shared_focal", False) and not get("use_gt_focal", False),
                          temporal_smoothing_weight=get("temporal_smoothing_weight", 0.015), translation_weight=get("translation_weight", 1.0),
                          inverse_depth=torch.stack([p["inverse_depthmap"] for p in post]) if use_inverse_depthmap else None,
-                         traj=traj if use_traj else None, depth_traj_start_iter=depth_traj_start_iter)
+                         traj=traj if use_traj else None, depth_traj_start_iter=depth_traj_start_iter, optimize_pp=optimize_pp)
+    if principal_points is not None:
+        scene.preset_principal_point(principal_points)
     focal = None
     if intrinsics is not None:
         per_image = (intrinsics[:, 0, 0] + intrinsics[:, 1, 1]) / 2.0

@@ -12,6 +12,7 @@
 // in a fixed order (deterministic: no atomics). The chain rule from those 3x3 / 3-vector sums to quaternion, log-translation,
 // log-focal and log-scale parameters is a few hundred flops per image and stays on the host side (geo4d_amd/align.py), as does
 // the camera temporal-smoothing term. Everything here is HBM-bound: 20 B read + 4 B written per slot-pixel.
+#include <cstdio>
 #include <cstdlib>
 #include "common.h"
 #include "geo4d_hip.h"
@@ -21,6 +22,7 @@ namespace {
 constexpr int MAXS = 6;        // windows an image can belong to (stride 4, length 16 -> 4, + the duplicated tail window = 5)
 constexpr int IMG_SUMS = 14;   // dL/dR (9) | dL/dt (3) | dL/df (1) | loss (1)
 constexpr int SLOT_SUMS = 14;  // dL/d(sR) (9) | dL/d(st) (3) | inverse-depth term: dL/ds_g, dL/dt_g
+constexpr int PP_SUMS = 2;     // dL/dppx, dL/dppy (principal-point form only)
 
 // fixed-order block reduction of NV values per thread: xor-butterfly inside the wave, then the 4 waves through LDS
 template <int NV>
@@ -134,9 +136,14 @@ __global__ __launch_bounds__(256) void align_residual_kernel(const geo4d_align_t
 // v_exp + ~12 flops; the log-depth re-read hits L1 / L2) and reduces the slot sums at the end of each pass. ~90 VGPRs instead of 188.
 // Same partial-sum layout, same fixed-order reductions (deterministic); sums are accumulated slot-major instead of pixel-major, so the
 // results differ from the first kernel by fp32 re-association only.
-template <bool DEPTH, int NPX>
-__global__ __launch_bounds__(256) void align_residual_kernel2(const geo4d_align_t p) {
-    __shared__ float red[4 * SLOT_SUMS > 4 * IMG_SUMS ? 4 * SLOT_SUMS : 4 * IMG_SUMS];
+// PP (principal-point form, geo4d_align_residual_pp): cams[13..14] hold a per-image principal point and two more image sums,
+//     dL/dppx = -sum_px c0 d / f,  dL/dppy = -sum_px c1 d / f    (c = R^T g; dX_c/dppx = (-d / f, 0, 0)),
+// ride through the same block reduction (16 values instead of 14) into pp_part [n_imgs][chunks][2]. Without PP the pointer is unused and
+// the instantiations are the ones that ran before the form existed.
+template <bool DEPTH, int NPX, bool PP>
+__global__ __launch_bounds__(256) void align_residual_kernel2(const geo4d_align_t p, float* __restrict__ pp_part) {
+    constexpr int NIMG = IMG_SUMS + (PP ? PP_SUMS : 0);
+    __shared__ float red[4 * SLOT_SUMS > 4 * NIMG ? 4 * SLOT_SUMS : 4 * NIMG];
     const int tid = threadIdx.x, chunk = blockIdx.x, img = blockIdx.y;
     const int HW = p.H * p.W;
     const float* cam = p.cams + img * 16;
@@ -148,9 +155,9 @@ __global__ __launch_bounds__(256) void align_residual_kernel2(const geo4d_align_
     const float f = cam[12], inv_f = 1.0f / f, ppx = cam[13], ppy = cam[14];
     const int s0 = p.slot_ptr[img], ns = p.slot_ptr[img + 1] - s0;
     const int px0 = chunk * p.chunk_pixels + tid;
-    float simg[IMG_SUMS], gl[NPX];
+    float simg[NIMG], gl[NPX];
 #pragma unroll
-    for (int i = 0; i < IMG_SUMS; ++i) simg[i] = 0.f;
+    for (int i = 0; i < NIMG; ++i) simg[i] = 0.f;
 #pragma unroll
     for (int k = 0; k < NPX; ++k) gl[k] = 0.f;
     const float* ld = p.logdepth + (long)img * HW;
@@ -220,6 +227,7 @@ __global__ __launch_bounds__(256) void align_residual_kernel2(const geo4d_align_
             simg[6] += a2 * xc; simg[7] += a2 * yc; simg[8] += a2 * zc;
             simg[9] += a0; simg[10] += a1; simg[11] += a2;
             simg[12] -= (c0 * xc + c1 * yc) * inv_f;
+            if constexpr (PP) { simg[14] -= c0 * d * inv_f; simg[15] -= c1 * d * inv_f; }
         }
         block_sum<SLOT_SUMS>(ss, red, tid);
         if (tid < SLOT_SUMS) p.slot_part[((long)(s0 + j) * gridDim.x + chunk) * SLOT_SUMS + tid] = ss[0];
@@ -229,8 +237,11 @@ __global__ __launch_bounds__(256) void align_residual_kernel2(const geo4d_align_
         const int px = px0 + k * 256;
         if (px < HW) p.grad_logdepth[(long)img * HW + px] = gl[k];
     }
-    block_sum<IMG_SUMS>(simg, red, tid);
+    block_sum<NIMG>(simg, red, tid);
     if (tid < IMG_SUMS) p.img_part[((long)img * gridDim.x + chunk) * IMG_SUMS + tid] = simg[0];
+    if constexpr (PP) {
+        if (tid >= IMG_SUMS && tid < NIMG) pp_part[((long)img * gridDim.x + chunk) * PP_SUMS + (tid - IMG_SUMS)] = simg[0];
+    }
 }
 
 // out[row][c] = sum over chunks (fixed order) of part[row][chunk][c]; one thread per (row, c)
@@ -274,6 +285,19 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ prm, 
     prm[i] -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
 }
 
+// principal-point form: cams[i][13..14] = (W/2, H/2) + 10 im_pp[i] (optimizer_group.py:210-211), after align_refresh wrote the centre
+__global__ __launch_bounds__(256) void align_set_pp_kernel(float* __restrict__ cams, const float* __restrict__ im_pp, int n_imgs, float ppx, float ppy) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_imgs) return;
+    cams[i * 16 + 13] = ppx + 10.f * im_pp[i * 2];
+    cams[i * 16 + 14] = ppy + 10.f * im_pp[i * 2 + 1];
+}
+
+// ... and back: dL/dim_pp = 10 dL/dpp
+__global__ __launch_bounds__(256) void align_pp_grads_kernel(const float* __restrict__ pp_sums, float* __restrict__ grad_im_pp, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) grad_im_pp[i] = 10.f * pp_sums[i];
+}
 
 // ---- start-up of the inverse-depth term: per-window least-absolute-deviation fit (optimizer_group.py:333-372) ------------------------
 // The reference fits, per window, (s, t) minimising sum | s q + t - g | with 5000 Adam iterations of torch ops over the window's
@@ -440,41 +464,90 @@ extern "C" size_t geo4d_align_workspace(int n_imgs, int n_slots, int H, int W, i
     return ((size_t)n_imgs * nchunk * IMG_SUMS + (size_t)n_slots * nchunk * SLOT_SUMS) * sizeof(float);
 }
 
-extern "C" int geo4d_align_residual(const geo4d_align_t* pp, void* stream) {
+extern "C" size_t geo4d_align_pp_workspace(int n_imgs, int n_slots, int H, int W, int chunk_pixels) {
+    const size_t base = geo4d_align_workspace(n_imgs, n_slots, H, W, chunk_pixels);
+    if (!base) return 0;
+    const size_t nchunk = ((size_t)H * W + chunk_pixels - 1) / chunk_pixels;
+    return base + (size_t)n_imgs * nchunk * PP_SUMS * sizeof(float);
+}
+
+// pp_sums == nullptr: geo4d_align_residual; else the principal-point form geo4d_align_residual_pp (slot-outer kernel only)
+static int align_residual_launch(const geo4d_align_t* pp, float* pp_sums, void* stream) {
+    const bool with_pp = pp_sums != nullptr;
+    auto fail = [&](const char* what, int rc) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: %s", with_pp ? "align_residual_pp" : "align_residual", what);
+        geo4d_set_error(msg);
+        return rc;
+    };
     if (!pp) return GEO4D_EINVAL;
     geo4d_align_t p = *pp;
     if (p.n_imgs <= 0 || p.n_slots <= 0 || p.H <= 0 || p.W <= 0 || p.chunk_pixels < 256 || (p.chunk_pixels % 256) || !p.pred || !p.conf ||
-        !p.logdepth || !p.cams || !p.slot_trf || !p.slot_ptr || !p.slot_idx || !p.grad_logdepth || !p.img_sums || !p.slot_sums || !p.workspace) {
-        geo4d_set_error("align_residual: bad arguments (chunk_pixels must be a positive multiple of 256)");
-        return GEO4D_EINVAL;
-    }
-    if (p.invdepth && !p.slot_st) { geo4d_set_error("align_residual: invdepth needs slot_st"); return GEO4D_EINVAL; }
-    if (p.max_slots_per_image > MAXS) { geo4d_set_error("align_residual: an image belongs to more than 6 windows"); return GEO4D_ENOTSUP; }
+        !p.logdepth || !p.cams || !p.slot_trf || !p.slot_ptr || !p.slot_idx || !p.grad_logdepth || !p.img_sums || !p.slot_sums || !p.workspace)
+        return fail("bad arguments (chunk_pixels must be a positive multiple of 256)", GEO4D_EINVAL);
+    if (p.invdepth && !p.slot_st) return fail("invdepth needs slot_st", GEO4D_EINVAL);
+    if (p.max_slots_per_image > MAXS) return fail("an image belongs to more than 6 windows", GEO4D_ENOTSUP);
     const int HW = p.H * p.W;
     const int nchunk = (HW + p.chunk_pixels - 1) / p.chunk_pixels;
-    if (p.workspace_bytes < geo4d_align_workspace(p.n_imgs, p.n_slots, p.H, p.W, p.chunk_pixels)) { geo4d_set_error("align_residual: workspace too small"); return GEO4D_EINVAL; }
-    if (p.n_imgs > 65535) { geo4d_set_error("align_residual: too many images"); return GEO4D_EINVAL; }
+    const size_t need = with_pp ? geo4d_align_pp_workspace(p.n_imgs, p.n_slots, p.H, p.W, p.chunk_pixels)
+                                : geo4d_align_workspace(p.n_imgs, p.n_slots, p.H, p.W, p.chunk_pixels);
+    if (p.workspace_bytes < need) return fail("workspace too small", GEO4D_EINVAL);
+    if (p.n_imgs > 65535) return fail("too many images", GEO4D_EINVAL);
     p.img_part = (float*)p.workspace;
     p.slot_part = p.img_part + (size_t)p.n_imgs * nchunk * IMG_SUMS;
+    float* pp_part = with_pp ? p.slot_part + (size_t)p.n_slots * nchunk * SLOT_SUMS : nullptr;
     hipStream_t s = (hipStream_t)stream;
     // slot-major kernel (round 3) for the chunk sizes it is instantiated for; the pixel-major kernel serves any other multiple of 256
-#define GEO4D_ALIGN2(NPX_)                                                                                                        \
-    do {                                                                                                                           \
-        if (p.invdepth) hipLaunchKernelGGL((align_residual_kernel2<true, NPX_>), dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);       \
-        else hipLaunchKernelGGL((align_residual_kernel2<false, NPX_>), dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);                  \
+#define GEO4D_ALIGN2(NPX_, PP_)                                                                                                              \
+    do {                                                                                                                                      \
+        if (p.invdepth) hipLaunchKernelGGL((align_residual_kernel2<true, NPX_, PP_>), dim3(nchunk, p.n_imgs), dim3(256), 0, s, p, pp_part);    \
+        else hipLaunchKernelGGL((align_residual_kernel2<false, NPX_, PP_>), dim3(nchunk, p.n_imgs), dim3(256), 0, s, p, pp_part);               \
     } while (0)
-    const bool v1 = getenv("GEO4D_ALIGN_KERNEL") && atoi(getenv("GEO4D_ALIGN_KERNEL")) == 1;
-    if (!v1 && p.chunk_pixels == 4096) GEO4D_ALIGN2(16);
-    else if (!v1 && p.chunk_pixels == 2048) GEO4D_ALIGN2(8);
-    else if (!v1 && p.chunk_pixels == 1024) GEO4D_ALIGN2(4);
-    else if (!v1 && p.chunk_pixels == 256) GEO4D_ALIGN2(1);
-    else if (p.invdepth) hipLaunchKernelGGL(align_residual_kernel<true>, dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(align_residual_kernel<false>, dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);
+    if (with_pp) {
+        if (p.chunk_pixels == 4096) GEO4D_ALIGN2(16, true);
+        else if (p.chunk_pixels == 2048) GEO4D_ALIGN2(8, true);
+        else if (p.chunk_pixels == 1024) GEO4D_ALIGN2(4, true);
+        else if (p.chunk_pixels == 256) GEO4D_ALIGN2(1, true);
+        else return fail("chunk_pixels must be 256, 1024, 2048 or 4096 (slot-outer kernel only)", GEO4D_ENOTSUP);
+    } else {
+        const bool v1 = getenv("GEO4D_ALIGN_KERNEL") && atoi(getenv("GEO4D_ALIGN_KERNEL")) == 1;
+        if (!v1 && p.chunk_pixels == 4096) GEO4D_ALIGN2(16, false);
+        else if (!v1 && p.chunk_pixels == 2048) GEO4D_ALIGN2(8, false);
+        else if (!v1 && p.chunk_pixels == 1024) GEO4D_ALIGN2(4, false);
+        else if (!v1 && p.chunk_pixels == 256) GEO4D_ALIGN2(1, false);
+        else if (p.invdepth) hipLaunchKernelGGL(align_residual_kernel<true>, dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(align_residual_kernel<false>, dim3(nchunk, p.n_imgs), dim3(256), 0, s, p);
+    }
 #undef GEO4D_ALIGN2
     GEO4D_CHECK_LAUNCH();
     hipLaunchKernelGGL(align_reduce_kernel, dim3((p.n_imgs * IMG_SUMS + 255) / 256), dim3(256), 0, s, p.img_part, p.img_sums, p.n_imgs, nchunk, IMG_SUMS);
     GEO4D_CHECK_LAUNCH();
     hipLaunchKernelGGL(align_reduce_kernel, dim3((p.n_slots * SLOT_SUMS + 255) / 256), dim3(256), 0, s, p.slot_part, p.slot_sums, p.n_slots, nchunk, SLOT_SUMS);
+    GEO4D_CHECK_LAUNCH();
+    if (with_pp) {
+        hipLaunchKernelGGL(align_reduce_kernel, dim3((p.n_imgs * PP_SUMS + 255) / 256), dim3(256), 0, s, pp_part, pp_sums, p.n_imgs, nchunk, PP_SUMS);
+        GEO4D_CHECK_LAUNCH();
+    }
+    return GEO4D_OK;
+}
+
+extern "C" int geo4d_align_residual(const geo4d_align_t* pp, void* stream) { return align_residual_launch(pp, nullptr, stream); }
+
+extern "C" int geo4d_align_residual_pp(const geo4d_align_t* pp, float* pp_sums, void* stream) {
+    if (!pp_sums) { geo4d_set_error("align_residual_pp: bad arguments (pp_sums)"); return GEO4D_EINVAL; }
+    return align_residual_launch(pp, pp_sums, stream);
+}
+
+extern "C" int geo4d_align_set_pp(float* cams, const float* im_pp, int n_imgs, float ppx, float ppy, void* stream) {
+    if (!cams || !im_pp || n_imgs <= 0) { geo4d_set_error("align_set_pp: bad arguments"); return GEO4D_EINVAL; }
+    hipLaunchKernelGGL(align_set_pp_kernel, dim3((n_imgs + 255) / 256), dim3(256), 0, (hipStream_t)stream, cams, im_pp, n_imgs, ppx, ppy);
+    GEO4D_CHECK_LAUNCH();
+    return GEO4D_OK;
+}
+
+extern "C" int geo4d_align_pp_grads(const float* pp_sums, float* grad_im_pp, int n_imgs, void* stream) {
+    if (!pp_sums || !grad_im_pp || n_imgs <= 0) { geo4d_set_error("align_pp_grads: bad arguments"); return GEO4D_EINVAL; }
+    hipLaunchKernelGGL(align_pp_grads_kernel, dim3((n_imgs * PP_SUMS + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp_sums, grad_im_pp, n_imgs * PP_SUMS);
     GEO4D_CHECK_LAUNCH();
     return GEO4D_OK;
 }

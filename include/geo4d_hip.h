@@ -366,6 +366,20 @@ typedef struct geo4d_align_t {
 } geo4d_align_t;
 size_t geo4d_align_workspace(int n_imgs, int n_slots, int H, int W, int chunk_pixels);
 int geo4d_align_residual(const geo4d_align_t* p, void* stream);
+/* Principal-point form (optimizer_group.py:67-68, 203-211: im_pp per image, principal point = (W/2, H/2) + 10 im_pp, optimize_pp).
+ *   geo4d_align_set_pp       cams[i][13..14] = (ppx, ppy) + 10 im_pp[i]  (im_pp [n_imgs][2]); run it after geo4d_align_refresh, which
+ *                            writes the scalar centre there. geo4d_align_residual reads whatever cams holds, so a preset (frozen)
+ *                            principal point needs only this launch.
+ *   geo4d_align_residual_pp  geo4d_align_residual + pp_sums [n_imgs][2] = (dL/dppx, dL/dppy) = -sum_px (c0, c1) d / f with c = R^T g the
+ *                            camera-frame gradient; the two sums ride through the same fixed-order block and chunk reductions as the 14
+ *                            image sums (deterministic), every other output equals geo4d_align_residual's bit for bit. Dispatches to the
+ *                            slot-outer kernel ONLY: chunk_pixels in {256, 1024, 2048, 4096}, anything else is -ENOTSUP (and
+ *                            GEO4D_ALIGN_KERNEL=1 is not consulted). workspace: geo4d_align_pp_workspace bytes.
+ *   geo4d_align_pp_grads     grad_im_pp [n_imgs][2] = 10 pp_sums. */
+size_t geo4d_align_pp_workspace(int n_imgs, int n_slots, int H, int W, int chunk_pixels);
+int geo4d_align_residual_pp(const geo4d_align_t* p, float* pp_sums, void* stream);
+int geo4d_align_set_pp(float* cams, const float* im_pp, int n_imgs, float ppx, float ppy, void* stream);
+int geo4d_align_pp_grads(const float* pp_sums, float* grad_im_pp, int n_imgs, void* stream);
 /* One torch.optim.Adam step on a flat fp32 tensor (no weight decay / amsgrad); `step` counts from 1.
  * replaces optimizer.step() of global_alignment_iter (dust3r/cloud_opt/base_opt_group.py:596-626) for the depth maps. */
 int geo4d_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1, float beta2,

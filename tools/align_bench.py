@@ -2,7 +2,7 @@
 """Per-iteration cost of the global-alignment loop (geo4d_amd/align.py + csrc/align.hip) at clip size: G windows of 16 frames at
 HxW, stride 4 (BASELINE configs[2]/[3]: 14 windows for 64 frames, 30 for 128). Reports the fused residual kernel's achieved HBM
 bandwidth against its algorithmic bytes (20 B read + 4 B written per window-frame pixel, + the depth map once per image).
-usage: align_bench.py [n_frames] [H] [W]"""
+usage: align_bench.py [n_frames] [H] [W]   (ALIGN_BENCH_PP=1: also with optimize_pp; ALIGN_BENCH_LATE=0: skip the late terms)"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from geo4d_amd.align import GroupAligner
@@ -14,8 +14,9 @@ G, S = len(groups), 16
 g = torch.Generator().manual_seed(0)
 pred = (torch.randn((G, S, H, W, 3), generator=g) * 0.3 + torch.tensor([0.0, 0.0, 2.0])).to(dev)
 conf = (torch.rand((G, S, H, W), generator=g) * 4 + 0.5).to(dev)
-for chunk in (1024, 2048, 4096):
-    a = GroupAligner(groups, pred, conf, temporal_smoothing_weight=0.015, translation_weight=1.0, chunk_pixels=chunk)
+# ALIGN_BENCH_PP=1: every chunk size a second time with optimize_pp (principal-point form of the residual kernel + its two small launches)
+for chunk, pp in [(c, p) for c in (1024, 2048, 4096) for p in ((False, True) if os.environ.get("ALIGN_BENCH_PP") == "1" else (False,))]:
+    a = GroupAligner(groups, pred, conf, temporal_smoothing_weight=0.015, translation_weight=1.0, chunk_pixels=chunk, optimize_pp=pp)
     a.P["im_depthmaps"] += 0.7
     for _ in range(3):
         a.loss_and_grads()
@@ -37,7 +38,7 @@ for chunk in (1024, 2048, 4096):
         res[graph] = (time.perf_counter() - t0) * 1e3 / 100
     bytes_alg = G * S * H * W * 20 + a.n * H * W * 8            # residual kernel: pred 12 + conf 4 + depth gradient 4 B per slot-pixel
     bytes_it = bytes_alg + a.n * H * W * 24                      # + fused Adam on the depth maps: param, grad, m, v read, param, m, v written
-    print(f"align {n} frames = {G} windows of 16 at {H}x{W}, chunk {chunk}: loss+grads eager {ms:.3f} ms; full Adam iteration eager "
+    print(f"align {n} frames = {G} windows of 16 at {H}x{W}, chunk {chunk}{', optimize_pp' if pp else ''}: loss+grads eager {ms:.3f} ms; full Adam iteration eager "
           f"{res[False]:.3f} ms, hipGraph replay {res[True]:.3f} ms = {bytes_it / res[True] / 1e6:.0f} GB/s of {bytes_it / 1e9:.2f} GB algorithmic "
           f"({100 * bytes_it / res[True] / 1e6 / 8000:.1f} % of the 8 TB/s HBM peak)", flush=True)
 
