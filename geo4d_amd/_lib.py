@@ -208,6 +208,12 @@ SIGNATURES = {
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_scene_mesh_faces_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_scene_mesh_faces": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_render_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_long]),
+    "geo4d_render_splat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_render_fill": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_render_resolve": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -259,6 +259,16 @@ __device__ __forceinline__ float erf_as(float x) {
 }
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erf_as(x * 0.70710678118654752440f)); }
 
+// float colour in [0, 1] -> u8 as io.save_glb does: clip(c * 255 + 0.5, 0, 255) then truncation. One rule for the glb's vertex colours
+// (scene_export.hip) and the rendered frames (render.hip); no FMA, so numpy's float32 rounds the same way.
+__device__ __forceinline__ unsigned quant_u8(float c) {
+#pragma clang fp contract(off)
+    float v = c * 255.0f;
+    v = v + 0.5f;
+    v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    return (unsigned)(int)v;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

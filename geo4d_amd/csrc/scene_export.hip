@@ -78,20 +78,13 @@ struct PointsOp {
 
     __device__ bool keep(long e) const { return !mask || mask[e]; }
 
-    __device__ static unsigned quant(float c) {
-        float v = c * 255.0f;
-        v = v + 0.5f;
-        v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-        return (unsigned)(int)v;
-    }
-
     __device__ void emit(long e, unsigned pos) const {
         const float* q = pts + e * 3;
         float* o = pts_out + (long)pos * 3;
         o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
         if (rgba_out) {
             const float* r = rgb + e * 3;
-            rgba_out[pos] = quant(r[0]) | (quant(r[1]) << 8) | (quant(r[2]) << 16) | (255u << 24);
+            rgba_out[pos] = quant_u8(r[0]) | (quant_u8(r[1]) << 8) | (quant_u8(r[2]) << 16) | (255u << 24);
         }
     }
 };

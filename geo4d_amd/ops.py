@@ -1195,6 +1195,61 @@ def scene_mesh_faces(mask, n, H, W, device):
     return faces, count
 
 
+def render_workspace(V, H, W, n_entries, device):
+    """The renderer's workspace (two uint64 key buffers [V, H, W] and the device copy of the source lists) as an int64 tensor."""
+    need = _lib.load().geo4d_render_workspace(V, H, W, n_entries)
+    if need == 0:
+        raise _lib.Geo4DNativeError(f"geo4d_render_workspace: need V, H, W > 0 and V * H * W < 2^31, got {(V, H, W)}")
+    return torch.empty((need + 7) // 8, device=device, dtype=torch.int64)
+
+
+def render_splat(points, views, view_src_ptr, view_src, size, ws, mask=None, radius=None, pts_per_image=None, near=1e-3, max_size=9):
+    """Splat points fp32 [N, 3] into the key buffers of `ws` (render_workspace) for views fp32 [V, 16] (world-to-camera rows 0..2, then
+    fx, fy, cx, cy). view_src_ptr / view_src: host int lists, the CSR of source images per view, an image being `pts_per_image`
+    consecutive points (None: all N are one image). mask [N] bool, radius [N] fp32 world radii (None: one pixel per point)."""
+    lib = _lib.load()
+    H, W = size
+    _dev(points, "points"), _dev(views, "views"), _dev(ws, "ws")
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 and points.is_contiguous(), (points.dtype, points.shape)
+    assert views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16 and views.is_contiguous(), (views.dtype, views.shape)
+    N, V = points.shape[0], views.shape[0]
+    if mask is not None:
+        assert tuple(_dev(mask, "mask").shape) == (N,), mask.shape
+        mask = mask.to(torch.bool).contiguous()
+    if radius is not None:
+        assert tuple(_dev(radius, "radius").shape) == (N,) and radius.dtype == torch.float32 and radius.is_contiguous(), (radius.dtype, radius.shape)
+    assert len(view_src_ptr) == V + 1 and len(view_src) == view_src_ptr[-1], (len(view_src_ptr), len(view_src), V)
+    ptr = (C.c_int * (V + 1))(*view_src_ptr)
+    src = (C.c_int * max(len(view_src), 1))(*view_src)
+    _lib.check(lib.geo4d_render_splat(points.data_ptr(), _ptr(mask), _ptr(radius), N, N if pts_per_image is None else pts_per_image,
+                                      views.data_ptr(), ptr, src, V, H, W, float(near), int(max_size), ws.data_ptr(), ws.numel() * 8,
+                                      _stream()), "geo4d_render_splat")
+    return ws
+
+
+def render_fill(ws, V, size, passes):
+    """`passes` hole-filling passes on the key buffers of `ws`: an empty pixel takes the minimum key of its 3 x 3 neighbours."""
+    _dev(ws, "ws")
+    _lib.check(_lib.load().geo4d_render_fill(V, size[0], size[1], int(passes), ws.data_ptr(), ws.numel() * 8, _stream()), "geo4d_render_fill")
+    return ws
+
+
+def render_resolve(ws, colors, V, size, background=(1.0, 1.0, 1.0)):
+    """(rgb uint8 [V, H, W, 3], depth fp32 [V, H, W], index int32 [V, H, W]) of the key buffers of `ws`: the winning point's colour
+    (colors fp32 [N, 3] in [0, 1], scene_points' rounding), camera depth and id; background / 0 / -1 where no point landed."""
+    lib = _lib.load()
+    H, W = size
+    _dev(ws, "ws"), _dev(colors, "colors")
+    assert colors.dtype == torch.float32 and colors.dim() == 2 and colors.shape[1] == 3 and colors.is_contiguous(), (colors.dtype, colors.shape)
+    rgb = torch.empty((V, H, W, 3), device=ws.device, dtype=torch.uint8)
+    depth = torch.empty((V, H, W), device=ws.device, dtype=torch.float32)
+    index = torch.empty((V, H, W), device=ws.device, dtype=torch.int32)
+    bg = (C.c_float * 3)(*[float(c) for c in background])
+    _lib.check(lib.geo4d_render_resolve(colors.data_ptr(), colors.shape[0], bg, V, H, W, rgb.data_ptr(), depth.data_ptr(), index.data_ptr(),
+                                        ws.data_ptr(), ws.numel() * 8, _stream()), "geo4d_render_resolve")
+    return rgb, depth, index
+
+
 def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=None, iters=40):
     """(shift [B], focal [B] fp32, status [B] int32) of point maps `points` fp32 [B, H, W, 3] (any map stride: `pred[:, 0]` is used in
     place): the z-shift and normalised focal that minimise sum |focal * xy / (z + shift) - uv|^2 over the pixels with `weight` [B, H, W]

@@ -1,0 +1,183 @@
+"""Frames of an aligned scene, rendered where it was computed: z-buffered point splats on the HIP device (csrc/render.hip).
+
+The reference's user opens the results folder in a browser viewer; a GPU server has neither browser nor display, so this module draws
+the scene's points into images instead. Nothing is ported: the projection, the footprint rule and the depth test are stated in
+include/geo4d_hip.h and restated in numpy in tests/render_restatement.py. ``render_points`` draws any point set from any cameras,
+``render_scene`` a ``GroupAligner`` in three modes (its own cameras, 4-D playback, a turntable), ``save_render`` writes PNG frames and
+a GIF. Pixel convention as everywhere in the project: pixel i sits at coordinate i, the principal point defaults to (W/2, H/2).
+Images are identical from run to run, bit for bit: the depth test is an integer minimum, which no arrival order changes.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+MODES = ("cameras", "playback", "turntable")
+
+
+def _views(cams2world, K):
+    """[V, 16] fp32 on the host: rows 0..2 of inv(cams2world) (4x4 algebra in fp64), then fx, fy, cx, cy of K [V, 3, 3]."""
+    c2w = torch.as_tensor(cams2world).detach().double().cpu().numpy().reshape(-1, 4, 4)
+    K = torch.as_tensor(K).detach().double().cpu().numpy().reshape(-1, 3, 3)
+    if len(c2w) != len(K):
+        raise ValueError(f"render: {len(c2w)} camera poses but {len(K)} intrinsics")
+    w2c = np.linalg.inv(c2w)
+    v = np.concatenate([w2c[:, :3, :].reshape(-1, 12), K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3]], 1)
+    return torch.from_numpy(v.astype(np.float32))
+
+
+def _csr(sources, V, n_img):
+    """Host CSR (ptr, idx) of the source images per view; None = every image for every view."""
+    if sources is None:
+        sources = [range(n_img)] * V
+    if len(sources) != V:
+        raise ValueError(f"render: {len(sources)} source lists for {V} views")
+    ptr, idx = [0], []
+    for s in sources:
+        idx.extend(int(i) for i in s)
+        ptr.append(len(idx))
+    return ptr, idx
+
+
+@torch.no_grad()
+def render_points(points, colors, cams2world, K, size, *, mask=None, radius=None, sources=None, near=1e-3, max_size=9, fill=0,
+                  background=(1, 1, 1)):
+    """Draw points into V views; returns dict(rgb uint8 [V, H, W, 3], depth fp32 [V, H, W], index int32 [V, H, W]) on the device.
+
+    points [n_img, ..., 3] or [N, 3] fp32 world points on the HIP device (the leading axis of a >2-D tensor is the image axis that
+    `sources` indexes; [N, 3] is one image), colors the same shape in [0, 1]; cams2world [V, 4, 4] camera-to-world (OpenCV axes), K
+    [V, 3, 3]; size = (H, W) of the frames. mask (points' shape without the 3, bool) drops points; radius (same shape, world units)
+    gives every point a square footprint of ceil(2 radius fx / z) pixels, at most max_size, instead of one pixel; sources = per view the
+    list of images drawn into it (None: all). Points not beyond `near` in front of the camera are dropped. `fill` hole-filling passes
+    let an empty pixel take the nearest of its 3 x 3 neighbours. Per pixel the nearest point wins, at equal depth the lower index;
+    `index` is that point's row in points.reshape(-1, 3), -1 where nothing landed (rgb = background, depth = 0)."""
+    for t, what in ((points, "points"), (colors, "colors")):
+        if not t.is_cuda:
+            raise _lib.Geo4DNativeError(f"render_points: `{what}` lives on {t.device}; rendering runs only on a HIP device (there is no "
+                                        "CPU fallback)")
+    if points.shape[-1] != 3 or colors.shape != points.shape:
+        raise ValueError(f"render_points: points and colors must both be [..., 3], got {tuple(points.shape)} and {tuple(colors.shape)}")
+    H, W = int(size[0]), int(size[1])
+    n_img = points.shape[0] if points.dim() > 2 else 1
+    pts = points.reshape(-1, 3).float().contiguous()
+    col = colors.reshape(-1, 3).float().contiguous()
+    N = pts.shape[0]
+    views = _views(cams2world, K)
+    V = len(views)
+    ptr, idx = _csr(sources, V, n_img)
+    flat = lambda t, dt: None if t is None else t.to(pts.device).reshape(-1).to(dt).contiguous()
+    mask, radius = flat(mask, torch.bool), flat(radius, torch.float32)
+    ws = ops.render_workspace(V, H, W, len(idx), pts.device)
+    ops.render_splat(pts, views.to(pts.device), ptr, idx, (H, W), ws, mask=mask, radius=radius, pts_per_image=N // n_img, near=near,
+                     max_size=max_size)
+    if fill:
+        ops.render_fill(ws, V, (H, W), fill)
+    rgb, depth, index = ops.render_resolve(ws, col, V, (H, W), background)
+    return dict(rgb=rgb, depth=depth, index=index)
+
+
+def orbit_cameras(center, radius, n, elevation=0.0, up=(0.0, -1.0, 0.0)):
+    """[n, 4, 4] fp64 camera-to-world poses on a circle of `radius` round `center`, raised by `elevation` radians above the plane
+    normal to `up`, each looking at `center`. OpenCV convention: x right, y down, z forward, so the image's top points along `up`
+    (the default is the -y of a world laid out like the first camera)."""
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    up = np.asarray(up, dtype=np.float64).reshape(3)
+    up = up / np.linalg.norm(up)
+    a = np.eye(3)[np.argmin(np.abs(up))]                      # any direction that is not parallel to `up`
+    e0 = np.cross(up, a)
+    e0 /= np.linalg.norm(e0)
+    e1 = np.cross(up, e0)
+    poses = np.tile(np.eye(4), (n, 1, 1))
+    for k in range(n):
+        th = 2 * math.pi * k / n
+        pos = c + radius * (math.cos(elevation) * (math.cos(th) * e0 + math.sin(th) * e1) + math.sin(elevation) * up)
+        z = c - pos
+        z /= np.linalg.norm(z)
+        x = np.cross(z, up)                                     # right = forward x up (y down = -up once orthogonalised)
+        x /= np.linalg.norm(x)
+        y = np.cross(z, x)
+        poses[k, :3, 0], poses[k, :3, 1], poses[k, :3, 2], poses[k, :3, 3] = x, y, z, pos
+    return poses
+
+
+@torch.no_grad()
+def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=True, thr_for_init_conf=True, point_size=0, trail=0,
+                 path=None, sources=None, n_views=24, elevation=0.3, orbit_radius=None, near=1e-3, max_size=9, fill=0,
+                 background=(1, 1, 1)):
+    """Frames of a GroupAligner: dict(rgb, depth, index) as render_points returns them, one view per frame.
+
+    Points, colours and masks are those get_3D_model_from_scene exports (get_pts3d, scene.imgs, get_masks with `min_conf_thr` /
+    `thr_for_init_conf`; `is_msk=False` keeps every pixel). mode "cameras": view i is image i's camera and draws every image;
+    "playback": view t is image t's camera - or pose t of `path` [n, 4, 4] - and draws images t - trail .. t, the clip as it unfolds;
+    "turntable": `n_views` cameras of orbit_cameras round the masked points' median, `orbit_radius` away (None: twice the median
+    distance of the points from it), `elevation` radians up, drawing every image. `sources` overrides the mode's lists. `point_size`
+    > 0 draws point p of image i with the world radius 0.5 point_size depth / focal, i.e. point_size pixels wide in its own camera and
+    accordingly larger from nearer by; 0 draws single pixels. `size` (H, W) other than the scene's rescales the intrinsics."""
+    if mode not in MODES:
+        raise ValueError(f"render_scene: mode must be one of {MODES}, got {mode!r}")
+    if scene.imgs is None:
+        raise ValueError("render_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs [n, H, W, 3] in [0, 1]")
+    scene.require_all_depthmaps("render_scene")
+    n, H, W = scene.n, scene.H, scene.W
+    imgs = scene.imgs.to(scene.dev).float().contiguous()
+    pts3d = scene.get_pts3d().detach().contiguous()
+    scene.min_conf_thr = min_conf_thr
+    scene.thr_for_init_conf = thr_for_init_conf
+    msk = scene.get_masks() if is_msk else None
+    focals = scene.get_focals().detach().reshape(n)
+    c2w = scene.get_im_poses_matrix().detach().double().cpu()
+    K = torch.zeros((n, 3, 3), dtype=torch.float64)
+    K[:, 0, 0] = K[:, 1, 1] = focals.double().cpu()
+    K[:, :2, 2] = scene.get_principal_points().detach().double().cpu()
+    K[:, 2, 2] = 1
+    radius = None
+    if point_size:
+        radius = 0.5 * float(point_size) * scene.get_depthmaps().detach() / focals.view(n, 1, 1)
+    everything = list(range(n))
+    if mode == "cameras":
+        poses, Kv, src = c2w, K, [everything] * n
+    elif mode == "playback":
+        poses = c2w if path is None else torch.as_tensor(path).double().reshape(-1, 4, 4)
+        if len(poses) != n:
+            raise ValueError(f"render_scene: playback needs one pose per image ({n}), got {len(poses)}")
+        Kv, src = K, [list(range(max(0, t - int(trail)), t + 1)) for t in range(n)]
+    else:
+        sel = pts3d[msk] if msk is not None else pts3d.reshape(-1, 3)
+        sel = sel[torch.isfinite(sel).all(-1)]
+        if len(sel) == 0:
+            raise ValueError("render_scene: no valid point to orbit round (lower min_conf_thr or pass is_msk=False)")
+        center = sel.median(0).values
+        if orbit_radius is None:
+            orbit_radius = 2 * float((sel - center).norm(dim=-1).median())
+        up = -c2w[0, :3, 1].numpy()                              # the first camera's "up"
+        poses = torch.from_numpy(orbit_cameras(center.double().cpu().numpy(), orbit_radius, n_views, elevation, up))
+        Kv, src = K[:1].expand(n_views, 3, 3).clone(), [everything] * n_views
+    if sources is not None:
+        src = sources
+    oh, ow = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if (oh, ow) != (H, W):
+        Kv = Kv.clone()
+        Kv[:, 0] *= ow / W
+        Kv[:, 1] *= oh / H
+    return render_points(pts3d, imgs, poses, Kv, (oh, ow), mask=msk, radius=radius, sources=src, near=near, max_size=max_size, fill=fill,
+                         background=background)
+
+
+def save_render(path, rgb, fps=10):
+    """frame_%04d.png per view of rgb uint8 [V, H, W, 3] (tensor or array) and render.gif at `fps`, in directory `path`."""
+    from PIL import Image
+    frames = rgb.detach().cpu().numpy() if torch.is_tensor(rgb) else np.asarray(rgb)
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"save_render: rgb must be uint8 [V, H, W, 3], got {frames.dtype} {frames.shape}")
+    os.makedirs(path, exist_ok=True)
+    images = []
+    for i, f in enumerate(frames):
+        p = os.path.join(path, f"frame_{i:04d}.png")
+        Image.fromarray(np.ascontiguousarray(f)).save(p)
+        images.append(Image.open(p))
+    if images:
+        images[0].save(os.path.join(path, "render.gif"), save_all=True, append_images=images[1:], duration=max(1, round(1000 / fps)), loop=0)
+    return path

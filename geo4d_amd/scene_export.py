@@ -95,11 +95,12 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
                               cam_color=camera_colors(n))
 
 
-def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, **glb_kw):
+def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, **glb_kw):
     """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
     cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
     previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
-    Returns the directory."""
+    `render`: None, or a mode of geo4d_amd.render.render_scene ("cameras", "playback", "turntable"): also writes <seq>/render/
+    (frame_%04d.png, render.gif) with the glb's threshold and masking. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -107,6 +108,7 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, **glb_kw):
         scene.imgs = rgb_frames(imgs, scene.n, scene.H, scene.W).to(scene.dev)
     kw = dict(silent=True, as_pointcloud=True, mask_sky=False, clean_depth=False, transparent_cams=False, cam_size=0.01, is_msk=False)
     kw.update(glb_kw)
+    is_msk, thr_init = kw["is_msk"], kw.get("thr_for_init_conf", True)
     get_3D_model_from_scene(d, kw.pop("silent"), scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
@@ -116,4 +118,8 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, **glb_kw):
         io.save_conf_maps(d, scene.get_conf(), "conf")
         io.save_conf_maps(d, scene.get_init_conf(), "init_conf")
         io.save_rgb_imgs(d, scene.imgs.detach().cpu().numpy())
+    if render is not None:
+        from . import render as _render
+        frames = _render.render_scene(scene, render, min_conf_thr=min_conf_thr, is_msk=is_msk, thr_for_init_conf=thr_init)
+        _render.save_render(os.path.join(d, "render"), frames["rgb"])
     return d

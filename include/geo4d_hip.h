@@ -484,6 +484,33 @@ size_t geo4d_scene_mesh_faces_workspace(int n, int H, int W);
 int geo4d_scene_mesh_faces(const unsigned char* mask, int n, int H, int W, int* faces, long* count, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Frames of the aligned scene: z-buffered point splats (geo4d_amd/csrc/render.hip, geo4d_amd/render.py). Nothing of the reference is
+ * replaced (it shows a scene in a browser); the rules are this project's own, restated in numpy in tests/render_restatement.py.
+ *   V views of H x W pixels, V * H * W < 2^31. N points, 0 < N < 2^32 - 1, in whole images of pts_per_image points: image s holds the
+ *   points s * pts_per_image .. ; a point's id is its row. Device arrays: points [N][3] fp32, mask [N] bytes (NULL: all), radius [N]
+ *   fp32 world radii (NULL: one pixel per point), colors [N][3] fp32 in [0, 1], views [V][16] fp32 = rows 0..2 of the world-to-camera
+ *   matrix (12, row-major) then fx, fy, cx, cy. HOST arrays: view_src_ptr [V + 1] and view_src, the CSR list of source images per view
+ *   (rising from 0, every index < N / pts_per_image, checked before any launch), and background [3].
+ *   workspace: geo4d_render_workspace bytes for n_entries = view_src_ptr[V], 8-byte aligned = two key buffers [V][H][W] uint64 (every
+ *     call leaves its result in the first) and the device copy of the source lists.
+ *   geo4d_render_splat: the key buffer := all ones, then for every view and every point of its source images (one launch, order
+ *     irrelevant): xc = ((r00 X + r01 Y) + r02 Z) + t0, likewise yc, zc, no FMA; the point is dropped when masked out, when a world or
+ *     camera coordinate is not finite, or when zc <= near; u = fx (xc / zc) + cx, v = fy (yc / zc) + cy (pixel i sits at coordinate i);
+ *     side s = 1, or with radius min(max_size, max(1, ceil(2 radius fx / zc))), 1 <= max_size <= 64; columns x0 .. x0 + s - 1 with
+ *     x0 = floor(u - 0.5 (s - 1) + 0.5), rows likewise, clipped to the image; every covered pixel takes the unsigned 64-bit minimum
+ *     (a vector atomic) of key = float_bits(zc) << 32 | id: the nearest point, at equal depth the lower id, whatever the arrival order.
+ *   geo4d_render_fill: `passes` times, every empty pixel (all ones) takes the minimum key of its 3 x 3 neighbours inside its view.
+ *   geo4d_render_resolve: per pixel rgb [V][H][W][3] u8 = clip(c * 255 + 0.5, 0, 255) truncated of the winner's colour (the rule of
+ *     geo4d_scene_points) or of background, depth [V][H][W] fp32 = zc or 0, index [V][H][W] int32 = id or -1 (hence N < 2^31 here);
+ *     any of the three may be NULL, not all. */
+size_t geo4d_render_workspace(int V, int H, int W, long n_entries);
+int geo4d_render_splat(const float* points, const unsigned char* mask, const float* radius, long N, long pts_per_image, const float* views,
+                       const int* view_src_ptr, const int* view_src, int V, int H, int W, float near, int max_size, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int geo4d_render_fill(int V, int H, int W, int passes, void* workspace, size_t workspace_bytes, void* stream);
+int geo4d_render_resolve(const float* colors, long N, const float* background, int V, int H, int W, unsigned char* rgb, float* depth,
+                         int* index, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
