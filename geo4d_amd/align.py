@@ -253,6 +253,7 @@ class GroupAligner:
         # min_conf_thr = 3, thr_for_init_conf = False (base_opt_group.py:104-170); the confidence maps are built on first use
         self.conf_mode, self.min_conf_thr, self.thr_for_init_conf = "id", 3, False
         self.imgs = None                         # [n, H, W, 3] RGB in [0, 1] (post_optimization(imgs=...))
+        self.dynamic_masks = None                # [n, H, W] bool: the moving pixels (geo4d_amd.motion.segment_motion)
         self._conf_maps = None                   # (im_conf, init_conf_maps)
         self._all_depthmaps = True               # False while a sharded alignment holds only this rank's images' final depth maps
 

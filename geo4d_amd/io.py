@@ -269,6 +269,19 @@ def save_rgb_imgs(path, imgs):
         Image.fromarray((np.asarray(img) * 255).astype(np.uint8)).save(f'{path}/frame_{i:04d}.png')
 
 
+def save_dynamic_masks(path, masks):
+    """dynamic_mask_{i}.png per image of masks [n, H, W] (bool tensor or array): 8-bit, 0 / 255, the file names and values of
+    dust3r/utils/misc.py:176-180 (which writes them through cv2)."""
+    from PIL import Image
+    m = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+    if m.ndim != 3:
+        raise ValueError(f"save_dynamic_masks: masks must be [n, H, W], got {m.shape}")
+    os.makedirs(path, exist_ok=True)
+    for i, d in enumerate(m):
+        Image.fromarray(np.ascontiguousarray(d.astype(bool)).astype(np.uint8) * 255).save(f'{path}/dynamic_mask_{i}.png')
+    return path
+
+
 # ---- glb export (dust3r/demo.py:56-86 -> dust3r/utils/viz_demo.py:13-58) -------------------------------------------------------------
 OPENGL = np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]], dtype=np.float64)     # dust3r/viz.py:338-341
 

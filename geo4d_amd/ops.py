@@ -1250,6 +1250,44 @@ def render_resolve(ws, colors, V, size, background=(1.0, 1.0, 1.0)):
     return rgb, depth, index
 
 
+def motion_range(depth, valid=None):
+    """The motion rule's workspace for depth fp32 [n, H, W] and valid bool [n, H, W] (None: every pixel): per pixel the (dmin, dmax) of
+    the valid depths in its 3 x 3 neighbourhood, dmin = NaN on invalid pixels; fp32 [n, H, W, 2]."""
+    lib = _lib.load()
+    _dev(depth, "depth")
+    assert depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous(), (depth.dtype, depth.shape)
+    n, H, W = depth.shape
+    if valid is not None:
+        _dev(valid, "valid")
+    valid = _scene_mask(valid, (n, H, W), depth.device)
+    need = lib.geo4d_motion_workspace(n, H, W)
+    if need == 0:
+        raise _lib.Geo4DNativeError(f"geo4d_motion_workspace: need n, H, W > 0 and n * H * W < 2^31, got {(n, H, W)}")
+    ws = torch.empty((n, H, W, 2), device=depth.device, dtype=torch.float32)
+    _lib.check(lib.geo4d_motion_range(depth.data_ptr(), _ptr(valid), n, H, W, ws.data_ptr(), need, _stream()), "geo4d_motion_range")
+    return ws
+
+
+def motion_votes(pts3d, depth, valid, views, radius=8, tol=0.05, near=1e-3, ws=None):
+    """votes uint8 [n, H, W, 3] = (consistent, free, occluded) counts of every pixel over the images 0 < |j - i| <= radius (the rule of
+    include/geo4d_hip.h): pts3d fp32 [n, H, W, 3] world points, depth fp32 [n, H, W], valid bool [n, H, W] or None, views fp32 [n, 16]
+    (world-to-camera rows 0..2, then fx, fy, cx, cy). `ws`: a motion_range result to reuse instead of computing the depth ranges."""
+    lib = _lib.load()
+    _dev(pts3d, "pts3d"), _dev(views, "views")
+    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous(), (pts3d.dtype, pts3d.shape)
+    n, H, W, _ = pts3d.shape
+    assert views.dtype == torch.float32 and tuple(views.shape) == (n, 16) and views.is_contiguous(), (views.dtype, views.shape)
+    if ws is None:
+        assert tuple(depth.shape) == (n, H, W), (depth.shape, pts3d.shape)
+        ws = motion_range(depth, valid)
+    _dev(ws, "ws")
+    assert ws.dtype == torch.float32 and tuple(ws.shape) == (n, H, W, 2) and ws.is_contiguous(), (ws.dtype, ws.shape)
+    votes = torch.empty((n, H, W, 3), device=pts3d.device, dtype=torch.uint8)
+    _lib.check(lib.geo4d_motion_votes(pts3d.data_ptr(), views.data_ptr(), n, H, W, int(radius), float(tol), float(near), votes.data_ptr(),
+                                      ws.data_ptr(), ws.numel() * 4, _stream()), "geo4d_motion_votes")
+    return votes
+
+
 def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=None, iters=40):
     """(shift [B], focal [B] fp32, status [B] int32) of point maps `points` fp32 [B, H, W, 3] (any map stride: `pred[:, 0]` is used in
     place): the z-shift and normalised focal that minimise sum |focal * xy / (z + shift) - uv|^2 over the pixels with `weight` [B, H, W]

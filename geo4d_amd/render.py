@@ -29,6 +29,16 @@ def _views(cams2world, K):
     return torch.from_numpy(v.astype(np.float32))
 
 
+def _scene_cameras(scene):
+    """(cams2world [n, 4, 4], K [n, 3, 3]) fp64 on the host from a GroupAligner's poses, focals and principal points."""
+    n = scene.n
+    K = torch.zeros((n, 3, 3), dtype=torch.float64)
+    K[:, 0, 0] = K[:, 1, 1] = scene.get_focals().detach().reshape(n).double().cpu()
+    K[:, :2, 2] = scene.get_principal_points().detach().double().cpu()
+    K[:, 2, 2] = 1
+    return scene.get_im_poses_matrix().detach().double().cpu(), K
+
+
 def _csr(sources, V, n_img):
     """Host CSR (ptr, idx) of the source images per view; None = every image for every view."""
     if sources is None:
@@ -106,7 +116,7 @@ def orbit_cameras(center, radius, n, elevation=0.0, up=(0.0, -1.0, 0.0)):
 @torch.no_grad()
 def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=True, thr_for_init_conf=True, point_size=0, trail=0,
                  path=None, sources=None, n_views=24, elevation=0.3, orbit_radius=None, near=1e-3, max_size=9, fill=0,
-                 background=(1, 1, 1)):
+                 background=(1, 1, 1), persist_static=False):
     """Frames of a GroupAligner: dict(rgb, depth, index) as render_points returns them, one view per frame.
 
     Points, colours and masks are those get_3D_model_from_scene exports (get_pts3d, scene.imgs, get_masks with `min_conf_thr` /
@@ -115,7 +125,11 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
     "turntable": `n_views` cameras of orbit_cameras round the masked points' median, `orbit_radius` away (None: twice the median
     distance of the points from it), `elevation` radians up, drawing every image. `sources` overrides the mode's lists. `point_size`
     > 0 draws point p of image i with the world radius 0.5 point_size depth / focal, i.e. point_size pixels wide in its own camera and
-    accordingly larger from nearer by; 0 draws single pixels. `size` (H, W) other than the scene's rescales the intrinsics."""
+    accordingly larger from nearer by; 0 draws single pixels. `size` (H, W) other than the scene's rescales the intrinsics.
+    `persist_static=True`: every view draws the static points of ALL images and the dynamic points (scene.dynamic_masks, made by
+    geo4d_amd.motion.segment_motion with this call's thresholds when the scene has none) only of the images in its source list, so
+    playback shows the current frame's movers over a background that is complete from the first frame and cameras / turntable
+    show the movers of no frame unless `sources` names some; `index` still counts rows of the scene's pts3d.reshape(-1, 3)."""
     if mode not in MODES:
         raise ValueError(f"render_scene: mode must be one of {MODES}, got {mode!r}")
     if scene.imgs is None:
@@ -128,11 +142,7 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
     scene.thr_for_init_conf = thr_for_init_conf
     msk = scene.get_masks() if is_msk else None
     focals = scene.get_focals().detach().reshape(n)
-    c2w = scene.get_im_poses_matrix().detach().double().cpu()
-    K = torch.zeros((n, 3, 3), dtype=torch.float64)
-    K[:, 0, 0] = K[:, 1, 1] = focals.double().cpu()
-    K[:, :2, 2] = scene.get_principal_points().detach().double().cpu()
-    K[:, 2, 2] = 1
+    c2w, K = _scene_cameras(scene)
     radius = None
     if point_size:
         radius = 0.5 * float(point_size) * scene.get_depthmaps().detach() / focals.view(n, 1, 1)
@@ -162,8 +172,23 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
         Kv = Kv.clone()
         Kv[:, 0] *= ow / W
         Kv[:, 1] *= oh / H
-    return render_points(pts3d, imgs, poses, Kv, (oh, ow), mask=msk, radius=radius, sources=src, near=near, max_size=max_size, fill=fill,
-                         background=background)
+    if not persist_static:
+        return render_points(pts3d, imgs, poses, Kv, (oh, ow), mask=msk, radius=radius, sources=src, near=near, max_size=max_size,
+                             fill=fill, background=background)
+    # the images twice, n static-masked copies then n dynamic-masked ones: every view draws all of the former and its own sources of the latter
+    dyn = getattr(scene, "dynamic_masks", None)
+    if dyn is None:
+        from .motion import segment_motion
+        dyn = segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+    keep = msk if msk is not None else torch.ones_like(dyn)
+    twice = lambda t: None if t is None else torch.cat([t, t])
+    movers = src if sources is not None or mode == "playback" else [[]] * len(src)  # "every image" would smear the movers again
+    out = render_points(twice(pts3d), twice(imgs), poses, Kv, (oh, ow), mask=torch.cat([keep & ~dyn, keep & dyn]), radius=twice(radius),
+                        sources=[everything + [n + int(i) for i in s] for s in movers], near=near, max_size=max_size, fill=fill,
+                        background=background)
+    idx = out["index"]
+    out["index"] = torch.where(idx >= n * H * W, idx - n * H * W, idx)            # rows of the original pts3d.reshape(-1, 3)
+    return out
 
 
 def save_render(path, rgb, fps=10):

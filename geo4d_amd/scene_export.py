@@ -51,15 +51,34 @@ def camera_colors(n):
     return [tuple(255 * c for c in cmap(i / n)[:3]) for i in range(n)]
 
 
+MOTION = (None, "static", "dynamic")
+
+
+def motion_part(scene, msk, motion, **seg_kw):
+    """The export mask [n, H, W] restricted to the "static" or "dynamic" pixels of scene.dynamic_masks (segment_motion(**seg_kw) makes
+    them when the scene has none); msk None = every pixel."""
+    dyn = getattr(scene, "dynamic_masks", None)
+    if dyn is None:
+        from .motion import segment_motion
+        dyn = segment_motion(scene, **seg_kw)
+    part = dyn if motion == "dynamic" else ~dyn
+    return part if msk is None else msk & part
+
+
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
-                            transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True):
+                            transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
+                            motion=None):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
     to geo4d_amd.io.save_glb on the same points, colours and masks; the mesh is one indexed TRIANGLES primitive with per-vertex colours
     (io.mesh_geometry says why it is not trimesh's per-face layout). `mask_sky=True` raises NotImplementedError: segment_sky needs
     OpenCV, which this engine does not use. `transparent_cams` is accepted and changes nothing: the camera glyphs here are untextured
-    wireframes, there is no image on them to make transparent."""
+    wireframes, there is no image on them to make transparent. `motion`: None exports everything, "static" only the points and mesh
+    faces that are not dynamic, "dynamic" only the dynamic ones; the masks are scene.dynamic_masks, made by
+    geo4d_amd.motion.segment_motion with this call's thresholds and its default rule when the scene has none yet."""
+    if motion not in MOTION:
+        raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
     if scene is None:
         return None
     if mask_sky:
@@ -78,11 +97,13 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         scene.min_conf_thr = min_conf_thr
         scene.thr_for_init_conf = thr_for_init_conf
         msk = scene.get_masks() if is_msk else None
+        if motion is not None:
+            msk = motion_part(scene, msk, motion, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
         n, H, W, _ = pts3d.shape
         if as_pointcloud:
             pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
             c = int(count.item())
-            geometry = [dict(mode=0, positions=pts[:c].cpu().numpy(), colors=rgba[:c].cpu().numpy())]
+            geometry = [dict(mode=0, positions=pts[:c].cpu().numpy(), colors=rgba[:c].cpu().numpy())] if c else []   # e.g. no mover
         else:
             pts, rgba, _ = ops.scene_points(pts3d, imgs, None)          # every vertex, as cat_meshes keeps them
             faces, count = ops.scene_mesh_faces(msk, n, H, W, pts3d.device)
@@ -95,12 +116,14 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
                               cam_color=camera_colors(n))
 
 
-def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, **glb_kw):
+def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynamic_masks=False, **glb_kw):
     """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
     cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
     previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
     `render`: None, or a mode of geo4d_amd.render.render_scene ("cameras", "playback", "turntable"): also writes <seq>/render/
-    (frame_%04d.png, render.gif) with the glb's threshold and masking. Returns the directory."""
+    (frame_%04d.png, render.gif) with the glb's threshold and masking. `dynamic_masks=True` also writes dynamic_mask_{i}.png
+    (scene.dynamic_masks, made by geo4d_amd.motion.segment_motion with the glb's threshold and masking when the scene has none) and
+    <seq>_static.glb, the glb without the moving points. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -109,7 +132,14 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, **glb
     kw = dict(silent=True, as_pointcloud=True, mask_sky=False, clean_depth=False, transparent_cams=False, cam_size=0.01, is_msk=False)
     kw.update(glb_kw)
     is_msk, thr_init = kw["is_msk"], kw.get("thr_for_init_conf", True)
-    get_3D_model_from_scene(d, kw.pop("silent"), scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
+    silent = kw.pop("silent")
+    get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
+    if dynamic_masks:
+        if getattr(scene, "dynamic_masks", None) is None:
+            from .motion import segment_motion
+            segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_init, is_msk=is_msk)
+        io.save_dynamic_masks(d, scene.dynamic_masks)
+        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static", **dict(kw, motion="static"))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())

@@ -511,6 +511,29 @@ int geo4d_render_fill(int V, int H, int W, int passes, void* workspace, size_t w
 int geo4d_render_resolve(const float* colors, long N, const float* background, int V, int H, int W, unsigned char* rgb, float* depth,
                          int* index, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which pixels of the aligned scene moved: geometric votes between the images (geo4d_amd/csrc/motion.hip, geo4d_amd/motion.py). Nothing
+ * of the reference is replaced (it fills dynamic_mask_{i}.png from optical flow and SAM2); the rule is this project's own, restated in
+ * numpy in tests/motion_restatement.py.
+ *   n images of H x W pixels, n * H * W < 2^31. Device arrays: depth [n][H][W] fp32, valid [n][H][W] bytes (NULL: all), pts3d
+ *   [n][H][W][3] fp32 world points, views [n][16] fp32 = rows 0..2 of each image's world-to-camera matrix (12, row-major) then fx, fy,
+ *   cx, cy, votes [n][H][W][3] u8. workspace: geo4d_motion_workspace bytes, 8-byte aligned = one (dmin, dmax) fp32 pair per pixel.
+ *   geo4d_motion_range: for every image j and pixel q, dmin / dmax = the minimum / maximum of depth[j] over the valid pixels of q's
+ *     3 x 3 neighbourhood inside the image (a NaN depth never wins; nothing to compare leaves (+inf, -inf)); an invalid q gets
+ *     dmin = NaN, which is how geo4d_motion_votes sees the mask.
+ *   geo4d_motion_votes: for every image i, every valid pixel p with a finite world point (X, Y, Z) and every j with
+ *     0 < |j - i| <= radius, 0 <= j < n (1 <= radius <= 127): xc = ((r00 X + r01 Y) + r02 Z) + t0, likewise yc, zc, no FMA; skipped
+ *     unless all three are finite and zc > near (near >= 0); u = fx (xc / zc) + cx, v = fy (yc / zc) + cy; column = floor(u + 0.5),
+ *     row = floor(v + 0.5) (pixel k sits at coordinate k), inside / outside decided in float before any cast; skipped when outside or
+ *     when j's pixel there is invalid. With lo = 1 - tol, hi = 1 + tol in fp32 (0 < tol < 1): free if zc < dmin lo (camera j sees past
+ *     the place where the point was), else occluded if zc > dmax hi (something is in front: no evidence), else consistent.
+ *     votes[i][p] = (consistent, free, occluded) counts, each <= 2 radius; (0, 0, 0) for invalid pixels. One writer per byte, no atomics.
+ *   Bad sizes, radius, tol, near and null pointers return -EINVAL before any launch. */
+size_t geo4d_motion_workspace(int n, int H, int W);
+int geo4d_motion_range(const float* depth, const unsigned char* valid, int n, int H, int W, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int geo4d_motion_votes(const float* pts3d, const float* views, int n, int H, int W, int radius, float tol, float near,
+                       unsigned char* votes, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
