@@ -218,6 +218,12 @@ SIGNATURES = {
     "geo4d_motion_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_motion_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_fuse_workspace": (C.c_size_t, [C.c_long, C.c_int]),
+    "geo4d_fuse_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_long, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_fuse_compact": (C.c_int, [C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_fuse_finalize": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_long,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1,0 +1,129 @@
+"""The aligned scene's points fused into one cloud: one point per occupied voxel, on the HIP device (csrc/fuse.hip).
+
+The export, the renderer and the static / moving split all treat the aligned scene as n separate images, so a wall seen in 64 frames is
+exported 64 times. ``fuse_points`` bins points into voxels of side ``voxel`` and reduces every voxel to one point: the weighted mean of
+its points' positions and colours (``reduce="mean"``) or its point of highest weight (``reduce="best"``). ``fuse_scene`` does that for a
+``GroupAligner`` with the masks of the export (``get_3D_model_from_scene``), weighted by the scene's confidence, and leaves the result in
+``scene.fused``; ``get_3D_model_from_scene(fuse_voxel=...)`` and ``save_scene(fuse_static=...)`` write it as a glb. The reference has no
+such step and nothing is ported. The rule is stated in include/geo4d_hip.h and restated in numpy in tests/fusion_restatement.py; the
+per-voxel sums are integers, so the result does not depend on the order of the points and is bitwise reproducible, and the rows come
+out sorted by voxel (cx, cy, cz).
+
+This removes duplicates, not noise: points are binned by their noisy positions, so every voxel keeps its bias (at 2 % depth noise the
+fused points of the synthetic scene are no closer to the wall than the raw ones). Limits: cell indices must stay below 2^20 in
+magnitude on every axis (points beyond are refused, not clipped); offsets inside a voxel are kept to 1 / 65536 of its side and weights
+to 1 / 128 within [1 / 128, 256); a surface that crosses a voxel obliquely still leaves one point per voxel it touches.
+"""
+import math
+
+import torch
+
+from . import _lib, ops
+
+REDUCE = tuple(ops.FUSE_REDUCE)
+CELL_LIMIT = 1 << 20
+
+
+def _rgba(colors, N, device):
+    """u8 [N, 4] of `colors`: a u8 rgba as it is, or float [N, 3] in [0, 1] quantised as ops.scene_points does (clip(c * 255 + 0.5,
+    0, 255) truncated, in fp32) with alpha 255."""
+    if colors is None:
+        return None
+    if not colors.is_cuda:
+        raise _lib.Geo4DNativeError(f"fuse_points: `colors` lives on {colors.device}; the fusion runs only on a HIP device")
+    if colors.dtype == torch.uint8:
+        if tuple(colors.shape) != (N, 4):
+            raise ValueError(f"fuse_points: uint8 colours must be rgba [N, 4] = {(N, 4)}, got {tuple(colors.shape)}")
+        return colors.contiguous()
+    if tuple(colors.shape) != (N, 3):
+        raise ValueError(f"fuse_points: float colours must be [N, 3] = {(N, 3)}, got {tuple(colors.shape)}")
+    rgb = ((colors.float() * 255.0) + 0.5).clamp(0.0, 255.0).to(torch.uint8)
+    return torch.cat([rgb, torch.full((N, 1), 255, dtype=torch.uint8, device=device)], 1).contiguous()
+
+
+def check_fuse_args(voxel, reduce, min_count):
+    """The fp32 voxel; ValueError for a voxel that is not finite and > 0 in fp32, an unknown reduce or a min_count below 1."""
+    try:
+        v = torch.tensor(float(voxel), dtype=torch.float32).item()
+    except (TypeError, ValueError):
+        v = math.nan
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"fuse_points: voxel must be finite and > 0 in fp32, got {voxel!r}")
+    if reduce not in REDUCE:
+        raise ValueError(f"fuse_points: reduce must be one of {REDUCE}, got {reduce!r}")
+    if int(min_count) != min_count or min_count < 1:
+        raise ValueError(f"fuse_points: min_count must be an integer >= 1, got {min_count!r}")
+    return v
+
+
+@torch.no_grad()
+def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="mean", min_count=1, capacity=None):
+    """dict(points fp32 [M, 3], rgba uint8 [M, 4] or None, weight fp32 [M], count int32 [M], voxel): one row per occupied voxel, in
+    (cx, cy, cz) order, on the device.
+
+    points [N, 3] fp32; colors float [N, 3] in [0, 1] or uint8 rgba [N, 4] (None: no colours, `rgba` None); weight [N] fp32 (None:
+    every weight is 1); mask [N] bool (None: all), all on the HIP device. A point takes part when its mask is set, its coordinates are
+    finite and its weight is finite and > 0. reduce "mean": the weighted mean position and colour and the mean weight of the voxel's
+    points; "best": the voxel's point of highest weight (the lowest row on ties), copied bit for bit. `count` is the number of points
+    in the voxel; voxels with fewer than `min_count` are left out. `capacity` overrides the hash table's size (a power of two >= N).
+    Raises ValueError when a point's cell index floor(x / voxel) reaches 2^20 in magnitude."""
+    v = check_fuse_args(voxel, reduce, min_count)
+    if not points.is_cuda:
+        raise _lib.Geo4DNativeError(f"fuse_points: `points` lives on {points.device}; the fusion runs only on a HIP device (there is no "
+                                    "CPU fallback)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"fuse_points: need points [N, 3], got {tuple(points.shape)}")
+    N, dev = points.shape[0], points.device
+    for t, what in ((weight, "weight"), (mask, "mask")):
+        if t is not None and tuple(t.shape) != (N,):
+            raise ValueError(f"fuse_points: {what} must be [N] = {(N,)}, got {tuple(t.shape)}")
+    pts, rgba, w, count, dropped = ops.fuse_points(points.detach().float().contiguous(), _rgba(colors, N, dev),
+                                                   None if weight is None else weight.detach().float().contiguous(),
+                                                   None if mask is None else mask.to(dev), voxel=v, reduce=reduce, capacity=capacity)
+    if dropped:
+        raise ValueError(f"fuse_points: {dropped} point(s) lie outside the voxel grid: a cell index floor(x / voxel) must stay below 2^20 "
+                         f"in magnitude, which at voxel = {v:g} means |x| < {CELL_LIMIT * v:g} on every axis; use a larger voxel or mask "
+                         "the outliers")
+    if min_count > 1:
+        keep = count >= int(min_count)
+        pts, w, count, rgba = pts[keep], w[keep], count[keep], None if rgba is None else rgba[keep]
+    return dict(points=pts, rgba=rgba, weight=w, count=count, voxel=v)
+
+
+def default_voxel(depth, focals, mask=None):
+    """2 * median(depth / focal) over the pixels of `mask` (None: all), i.e. twice the median pixel footprint, on the device: depth
+    [n, H, W], focals [n] or [n, 1]; fp32, the lower median (torch.median). None when the mask keeps no pixel."""
+    r = depth.float() / focals.float().reshape(-1, 1, 1)
+    r = r.reshape(-1) if mask is None else r[mask]
+    return 2.0 * float(torch.median(r)) if r.numel() else None
+
+
+@torch.no_grad()
+def fuse_scene(scene, *, voxel=None, motion="static", min_conf_thr=3, thr_for_init_conf=True, is_msk=True, reduce="mean", min_count=1):
+    """fuse_points on a GroupAligner; the result (see fuse_points) is also stored as scene.fused.
+
+    Points, colours and masks are taken exactly as get_3D_model_from_scene takes them: scene.get_pts3d(), scene.imgs (None: no colours)
+    and scene.get_masks() with `min_conf_thr` / `thr_for_init_conf` set on the scene (`is_msk=False`: every pixel), restricted by
+    `motion` (None, "static", "dynamic") to scene.dynamic_masks, which segment_motion makes with these thresholds when the scene has
+    none. The weight is the scene's confidence, scene.get_conf(), so a pixel whose confidence is not > 0 takes no part. `voxel=None`
+    means default_voxel: 2 * median(depth / focal) over the exported pixels, twice the median pixel footprint. That default gave 22.6
+    times fewer points on the synthetic scene of tests/motion_restatement.py; nobody has tried it on real predictions."""
+    from .scene_export import MOTION, motion_part
+    if motion not in MOTION:
+        raise ValueError(f"fuse_scene: motion must be one of {MOTION}, got {motion!r}")
+    check_fuse_args(1.0 if voxel is None else voxel, reduce, min_count)
+    scene.require_all_depthmaps("fuse_scene")
+    pts3d = scene.get_pts3d().detach().contiguous()
+    scene.min_conf_thr = min_conf_thr
+    scene.thr_for_init_conf = thr_for_init_conf
+    msk = scene.get_masks() if is_msk else None
+    if motion is not None:
+        msk = motion_part(scene, msk, motion, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+    if voxel is None:
+        voxel = default_voxel(scene.get_depthmaps().detach(), scene.get_focals().detach(), msk)
+        if voxel is None:                                           # nothing to fuse: any voxel gives the empty cloud
+            voxel = 1.0
+    colors = None if scene.imgs is None else scene.imgs.to(scene.dev).float().reshape(-1, 3)
+    scene.fused = fuse_points(pts3d.reshape(-1, 3), colors, scene.get_conf().detach().reshape(-1), None if msk is None else msk.reshape(-1),
+                              voxel=voxel, reduce=reduce, min_count=min_count)
+    return scene.fused

@@ -1288,6 +1288,95 @@ def motion_votes(pts3d, depth, valid, views, radius=8, tol=0.05, near=1e-3, ws=N
     return votes
 
 
+FUSE_REDUCE = {"mean": 0, "best": 1}
+
+
+class FuseTable:
+    """The voxel table of one fuse_insert: the workspace, its sizes, the inputs the later launches read, and `dropped` (device int64 [1])."""
+
+    def __init__(self, ws, need, capacity, reduce, voxel, points, rgba, weight, dropped):
+        self.ws, self.need, self.capacity, self.reduce, self.voxel = ws, need, capacity, reduce, voxel
+        self.points, self.rgba, self.weight, self.dropped = points, rgba, weight, dropped
+
+
+def fuse_capacity(N):
+    """The default table size: the power of two >= 2 N."""
+    return 1 << max(2 * N - 1, 0).bit_length()
+
+
+def fuse_insert(points, rgba=None, weight=None, mask=None, *, voxel, reduce="mean", capacity=None):
+    """Insert points fp32 [N, 3] into a fresh voxel table (the rule of include/geo4d_hip.h): rgba uint8 [N, 4], weight fp32 [N] and mask
+    bool [N] are optional. Returns the FuseTable for fuse_compact / fuse_finalize."""
+    lib = _lib.load()
+    _dev(points, "points")
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 and points.is_contiguous(), (points.dtype, points.shape)
+    N = points.shape[0]
+    if rgba is not None:
+        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (N, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+    if weight is not None:
+        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (N,) and weight.is_contiguous(), (weight.dtype, weight.shape)
+    if mask is not None:
+        assert tuple(_dev(mask, "mask").shape) == (N,), mask.shape
+        mask = mask.to(torch.bool).contiguous()
+    if reduce not in FUSE_REDUCE:
+        raise ValueError(f"fuse_insert: reduce must be one of {tuple(FUSE_REDUCE)}, got {reduce!r}")
+    capacity = fuse_capacity(N) if capacity is None else int(capacity)
+    need = lib.geo4d_fuse_workspace(capacity, FUSE_REDUCE[reduce])
+    if need == 0:
+        raise _lib.Geo4DNativeError(f"geo4d_fuse_workspace: capacity must be a power of two in 1 .. 2^32, got {capacity}")
+    ws = torch.empty(need // 8, device=points.device, dtype=torch.int64)
+    dropped = torch.empty(1, device=points.device, dtype=torch.int64)
+    _lib.check(lib.geo4d_fuse_insert(points.data_ptr(), _ptr(rgba), _ptr(weight), _ptr(mask), N, float(voxel), FUSE_REDUCE[reduce], capacity,
+                                     dropped.data_ptr(), ws.data_ptr(), need, _stream()), "geo4d_fuse_insert")
+    return FuseTable(ws, need, capacity, FUSE_REDUCE[reduce], float(voxel), points, rgba, weight, dropped)
+
+
+def fuse_compact(table):
+    """(keys int64 [N], slots int64 [N], count device int64 [1]) of a FuseTable: the occupied slots in arrival order; the first `count`
+    rows are written."""
+    N = table.points.shape[0]
+    dev = table.ws.device
+    keys, slots = torch.empty(N, device=dev, dtype=torch.int64), torch.empty(N, device=dev, dtype=torch.int64)
+    count = torch.empty(1, device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().geo4d_fuse_compact(table.capacity, table.reduce, keys.data_ptr(), slots.data_ptr(), N, count.data_ptr(),
+                                              table.ws.data_ptr(), table.need, _stream()), "geo4d_fuse_compact")
+    return keys, slots, count
+
+
+def fuse_finalize(table, order):
+    """(points fp32 [M, 3], rgba uint8 [M, 4] or None, weight fp32 [M], count int32 [M]): the voxels in the slots `order` int64 [M]."""
+    _dev(order, "order")
+    assert order.dtype == torch.int64 and order.dim() == 1 and order.is_contiguous(), (order.dtype, order.shape)
+    M, dev = order.shape[0], order.device
+    pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
+    rgba = None if table.rgba is None else torch.empty((M, 4), device=dev, dtype=torch.uint8)
+    weight = torch.empty(M, device=dev, dtype=torch.float32)
+    count = torch.empty(M, device=dev, dtype=torch.int32)
+    if M == 0:                                                      # no voxel: nothing to launch (an empty tensor has no address)
+        return pts, rgba, weight, count
+    _lib.check(_lib.load().geo4d_fuse_finalize(order.data_ptr(), M, table.points.data_ptr(), _ptr(table.rgba), _ptr(table.weight),
+                                               table.points.shape[0], table.voxel, table.reduce, table.capacity, pts.data_ptr(), _ptr(rgba),
+                                               weight.data_ptr(), count.data_ptr(), table.ws.data_ptr(), table.need, _stream()),
+               "geo4d_fuse_finalize")
+    return pts, rgba, weight, count
+
+
+def fuse_points(points, rgba=None, weight=None, mask=None, *, voxel, reduce="mean", capacity=None):
+    """One point per occupied voxel of side `voxel` (the rule of include/geo4d_hip.h), in key order = lexicographic (cx, cy, cz):
+    (points fp32 [M, 3], rgba uint8 [M, 4] or None, weight fp32 [M], count int32 [M], dropped int). points fp32 [N, 3], rgba uint8
+    [N, 4], weight fp32 [N], mask bool [N] on the HIP device. `capacity`: the table's size, a power of two >= N (default: >= 2 N).
+    Insert, compact and finalize are HIP launches; between them the (key, slot) pairs are sorted by key with torch.sort, because a
+    slot's position depends on the order the points arrived in. Reads two counts back (one synchronisation)."""
+    if _dev(points, "points").shape[0] == 0:                        # no point: no table
+        return (points.new_empty((0, 3)), None if rgba is None else rgba.new_empty((0, 4)), points.new_empty(0),
+                torch.empty(0, device=points.device, dtype=torch.int32), 0)
+    table = fuse_insert(points, rgba, weight, mask, voxel=voxel, reduce=reduce, capacity=capacity)
+    keys, slots, count = fuse_compact(table)
+    M, dropped = torch.cat([count, table.dropped]).tolist()
+    order = slots[:M][torch.sort(keys[:M]).indices]                 # keys < 2^63: signed order is unsigned order
+    return (*fuse_finalize(table, order.contiguous()), dropped)
+
+
 def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=None, iters=40):
     """(shift [B], focal [B] fp32, status [B] int32) of point maps `points` fp32 [B, H, W, 3] (any map stride: `pred[:, 0]` is used in
     place): the z-shift and normalised focal that minimise sum |focal * xy / (z + shift) - uv|^2 over the pixels with `weight` [B, H, W]

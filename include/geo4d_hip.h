@@ -534,6 +534,44 @@ int geo4d_motion_range(const float* depth, const unsigned char* valid, int n, in
 int geo4d_motion_votes(const float* pts3d, const float* views, int n, int H, int W, int radius, float tol, float near,
                        unsigned char* votes, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* The aligned scene's points merged into one cloud, one point per occupied voxel (geo4d_amd/csrc/fuse.hip, geo4d_amd/fusion.py). The
+ * reference has no such step; the rule is this project's own, restated in numpy in tests/fusion_restatement.py.
+ *   Device arrays: points [N][3] fp32, rgba [N][4] u8 (NULL: no colours), weight [N] fp32 (NULL: every weight is 1), mask [N] bytes
+ *   (NULL: all); 0 <= N < 2^31; voxel v > 0 finite, fp32. All float arithmetic is fp32 in the written order, no FMA; only the final
+ *   position is fp64.
+ *   Which points take part: point i takes part iff mask[i], X, Y, Z are finite, its weight w (when given) is finite and > 0, and per
+ *     axis the cell c = floorf(X / v) satisfies fabsf(c) < 2^20. A point that fails only the last condition is counted in *dropped;
+ *     the others are skipped silently.
+ *   Voxel key: (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20), below 2^63; all ones marks an empty slot. Unsigned key order is
+ *     lexicographic (cx, cy, cz) order.
+ *   Per point: offset q_a = (int)clamp(floorf((X_a - c_a v) / v * 65536.f + 0.5f), 0.f, 65535.f) (clamped as a float, then cast),
+ *     weight wq = (int)clamp(floorf(w * 128.f + 0.5f), 1.f, 32767.f).
+ *   Per voxel, integer sums: count, sw = sum wq, sq_a = sum wq q_a, sc_k = sum wq rgba_k (k = 0..2), u64 each; N < 2^31, wq < 2^15,
+ *     q < 2^16: no sum can overflow, and integer addition does not depend on the order the points arrive in.
+ *   reduce 0 (mean): pos_a = (float)(((double)c_a + (double)sq_a / ((double)sw * 65536.0)) * (double)v); colour (sc_k + sw / 2) / sw
+ *     in integers, alpha 255; weight (float)((double)sw / (128.0 * count)).
+ *   reduce 1 (best): the input point of highest weight, the lowest row on ties (the unsigned 64-bit maximum of float_bits(w) << 32 |
+ *     (0xffffffff - i)); position, colour and weight are copied bit for bit; count is still the voxel's count.
+ *   workspace: geo4d_fuse_workspace bytes (0 for a capacity that is no power of two in 1 .. 2^32 or an unknown reduce), 8-byte
+ *     aligned = an open-addressing table of `capacity` 64-bit keys (linear probing from a 64-bit mix of the key) and per slot 8 words
+ *     (mean) or 2 (best) of accumulators. capacity >= N, so an insert always finds a slot.
+ *   geo4d_fuse_insert: table := empty, *dropped := 0, then one launch over the points (64-bit vector atomics on global memory: CAS to
+ *     claim a slot, add / max into it; no lane waits for another).
+ *   geo4d_fuse_compact: *count := the number of occupied slots; their (key, slot) pairs go to keys_out / slots_out [max_pairs] in
+ *     arrival order (pairs beyond max_pairs are counted, not written). The caller sorts them by key.
+ *   geo4d_fuse_finalize: row m of the outputs = the voxel in slot order[m], 0 <= m < M <= N: points_out [M][3] fp32, rgba_out [M][4]
+ *     u8 (NULL without colours), weight_out [M] fp32, count_out [M] int32. points / rgba / weight are the insert's (read by best).
+ *   Null pointers, N < 0 or >= 2^31, a voxel that is not finite or <= 0, a capacity that is no power of two or < N, an unknown reduce
+ *   and a workspace that is too small return -EINVAL before any device work. */
+size_t geo4d_fuse_workspace(long capacity, int reduce);
+int geo4d_fuse_insert(const float* points, const unsigned char* rgba, const float* weight, const unsigned char* mask, long N, float voxel,
+                      int reduce, long capacity, long* dropped, void* workspace, size_t workspace_bytes, void* stream);
+int geo4d_fuse_compact(long capacity, int reduce, long* keys_out, long* slots_out, long max_pairs, long* count, const void* workspace,
+                       size_t workspace_bytes, void* stream);
+int geo4d_fuse_finalize(const long* order, long M, const float* points, const unsigned char* rgba, const float* weight, long N, float voxel,
+                        int reduce, long capacity, float* points_out, unsigned char* rgba_out, float* weight_out, int* count_out,
+                        const void* workspace, size_t workspace_bytes, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
