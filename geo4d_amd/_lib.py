@@ -224,6 +224,15 @@ SIGNATURES = {
     "geo4d_fuse_compact": (C.c_int, [C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "geo4d_fuse_finalize": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_long,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_tsdf_workspace": (C.c_size_t, [C.c_long]),
+    "geo4d_tsdf_mark": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                  C.c_long, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_tsdf_compact": (C.c_int, [C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "geo4d_tsdf_integrate": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_count": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_write": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -255,6 +255,7 @@ class GroupAligner:
         self.imgs = None                         # [n, H, W, 3] RGB in [0, 1] (post_optimization(imgs=...))
         self.dynamic_masks = None                # [n, H, W] bool: the moving pixels (geo4d_amd.motion.segment_motion)
         self.fused = None                        # the voxel-merged cloud of geo4d_amd.fusion.fuse_scene (a dict)
+        self.tsdf = None                         # the TSDF surface points of geo4d_amd.tsdf.tsdf_scene (a dict)
         self._conf_maps = None                   # (im_conf, init_conf_maps)
         self._all_depthmaps = True               # False while a sharded alignment holds only this rank's images' final depth maps
 

@@ -1377,6 +1377,154 @@ def fuse_points(points, rgba=None, weight=None, mask=None, *, voxel, reduce="mea
     return (*fuse_finalize(table, order.contiguous()), dropped)
 
 
+class TsdfTableFull(RuntimeError):
+    """The TSDF's voxel table was too small for the scene: nothing was computed; pass the capacity the message names."""
+
+
+def tsdf_capacity(taking_part):
+    """The default table size: the power of two >= 4 x the taking-part pixels."""
+    return 1 << max(4 * int(taking_part) - 1, 0).bit_length()
+
+
+def _tsdf_maps(pts3d, depth, valid, rgba, weight):
+    """The checked per-pixel inputs of the tsdf ops: (n, H, W, valid as bool or None)."""
+    _dev(pts3d, "pts3d"), _dev(depth, "depth")
+    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous(), (pts3d.dtype, pts3d.shape)
+    n, H, W, _ = pts3d.shape
+    assert depth.dtype == torch.float32 and tuple(depth.shape) == (n, H, W) and depth.is_contiguous(), (depth.dtype, depth.shape)
+    if valid is not None:
+        _dev(valid, "valid")
+    if rgba is not None:
+        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (n, H, W, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+    if weight is not None:
+        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (n, H, W) and weight.is_contiguous(), \
+            (weight.dtype, weight.shape)
+    return n, H, W, _scene_mask(valid, (n, H, W), pts3d.device)
+
+
+def tsdf_mark(pts3d, depth, valid, centres, *, voxel, trunc=4, near=1e-3, capacity):
+    """Mark the voxels within `trunc` voxels of every taking-part pixel's point along its ray (the rule of include/geo4d_hip.h) in a
+    fresh table of `capacity` keys: (table int64 [capacity], counters device int64 [2] = dropped, overflow)."""
+    lib = _lib.load()
+    n, H, W, valid = _tsdf_maps(pts3d, depth, valid, None, None)
+    assert _dev(centres, "centres").dtype == torch.float32 and tuple(centres.shape) == (n, 3) and centres.is_contiguous(), (centres.dtype, centres.shape)
+    need = lib.geo4d_tsdf_workspace(int(capacity))
+    if need == 0:
+        raise _lib.Geo4DNativeError(f"geo4d_tsdf_workspace: capacity must be a power of two in 1 .. 2^32, got {capacity}")
+    table = torch.empty(need // 8, device=pts3d.device, dtype=torch.int64)
+    counters = torch.empty(2, device=pts3d.device, dtype=torch.int64)
+    _lib.check(lib.geo4d_tsdf_mark(pts3d.data_ptr(), depth.data_ptr(), _ptr(valid), centres.data_ptr(), n, H, W, float(voxel), int(trunc),
+                                   float(near), int(capacity), counters.data_ptr(), table.data_ptr(), need, _stream()), "geo4d_tsdf_mark")
+    return table, counters
+
+
+def tsdf_compact(table, max_keys=None):
+    """(keys int64 [max_keys], count device int64 [1]) of a tsdf_mark table: the marked keys in arrival order; the first `count` rows
+    are written (max_keys None: room for a full table)."""
+    _dev(table, "table")
+    capacity = table.numel()
+    assert table.dtype == torch.int64 and table.dim() == 1 and capacity >= 1 and table.is_contiguous(), (table.dtype, table.shape)
+    max_keys = capacity if max_keys is None else max(int(max_keys), 1)
+    keys = torch.empty(max_keys, device=table.device, dtype=torch.int64)
+    count = torch.empty(1, device=table.device, dtype=torch.int64)
+    _lib.check(_lib.load().geo4d_tsdf_compact(capacity, keys.data_ptr(), max_keys, count.data_ptr(), table.data_ptr(), capacity * 8,
+                                              _stream()), "geo4d_tsdf_compact")
+    return keys, count
+
+
+def _tsdf_keys(keys):
+    _dev(keys, "keys")
+    assert keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous(), (keys.dtype, keys.shape)
+    return keys.shape[0]
+
+
+def tsdf_integrate(keys, depth, valid, views, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3):
+    """(f fp32 [M], Wt fp32 [M], rgba uint8 [M, 4] or None) of the voxels `keys` int64 [M]: the truncated signed distance averaged over
+    the images in the order 0 .. n-1, its weight and the averaged colour (the rule of include/geo4d_hip.h)."""
+    lib = _lib.load()
+    M, dev = _tsdf_keys(keys), keys.device
+    _dev(depth, "depth"), _dev(views, "views")
+    assert depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous(), (depth.dtype, depth.shape)
+    n, H, W = depth.shape
+    assert views.dtype == torch.float32 and tuple(views.shape) == (n, 16) and views.is_contiguous(), (views.dtype, views.shape)
+    if valid is not None:
+        _dev(valid, "valid")
+    valid = _scene_mask(valid, (n, H, W), dev)
+    if rgba is not None:
+        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (n, H, W, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+    if weight is not None:
+        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (n, H, W) and weight.is_contiguous(), \
+            (weight.dtype, weight.shape)
+    f = torch.empty(M, device=dev, dtype=torch.float32)
+    wt = torch.empty(M, device=dev, dtype=torch.float32)
+    col = None if rgba is None else torch.empty((M, 4), device=dev, dtype=torch.uint8)
+    if M == 0:                                                      # no voxel: nothing to launch (an empty tensor has no address)
+        return f, wt, col
+    _lib.check(lib.geo4d_tsdf_integrate(keys.data_ptr(), M, depth.data_ptr(), _ptr(valid), _ptr(weight), _ptr(rgba), views.data_ptr(), n, H, W,
+                                        float(voxel), int(trunc), float(near), f.data_ptr(), wt.data_ptr(), _ptr(col), _stream()),
+               "geo4d_tsdf_integrate")
+    return f, wt, col
+
+
+def tsdf_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
+    """(points fp32 [P, 3], rgba uint8 [P, 4] or None, weight fp32 [P]): one point per sign change of f between two live voxels that are
+    neighbours along an axis, in (voxel, axis) order. keys int64 [M] sorted, f / wt / rgba as tsdf_integrate returns them. A count
+    launch, torch.cumsum, a write launch; reads P back (one synchronisation)."""
+    lib = _lib.load()
+    M, dev = _tsdf_keys(keys), keys.device
+    for t, what in ((f, "f"), (wt, "wt")):
+        assert _dev(t, what).dtype == torch.float32 and tuple(t.shape) == (M,) and t.is_contiguous(), (what, t.dtype, t.shape)
+    if rgba is not None:
+        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (M, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+    empty = lambda: (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+                     torch.empty(0, device=dev, dtype=torch.float32))
+    if M == 0:
+        return empty()
+    counts = torch.empty(M, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_tsdf_count(keys.data_ptr(), M, f.data_ptr(), wt.data_ptr(), float(min_weight), counts.data_ptr(), _stream()),
+               "geo4d_tsdf_count")
+    last = torch.cumsum(counts, 0, dtype=torch.int64)
+    P = int(last[-1])
+    if P == 0:
+        return empty()
+    first = (last - counts).contiguous()
+    pts = torch.empty((P, 3), device=dev, dtype=torch.float32)
+    col = None if rgba is None else torch.empty((P, 4), device=dev, dtype=torch.uint8)
+    w = torch.empty(P, device=dev, dtype=torch.float32)
+    _lib.check(lib.geo4d_tsdf_write(keys.data_ptr(), M, f.data_ptr(), wt.data_ptr(), _ptr(rgba), first.data_ptr(), P, float(voxel),
+                                    float(min_weight), pts.data_ptr(), _ptr(col), w.data_ptr(), _stream()), "geo4d_tsdf_write")
+    return pts, col, w
+
+
+def tsdf_points(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
+    """The surface points of the TSDF of a scene (the rule of include/geo4d_hip.h): (points fp32 [P, 3], rgba uint8 [P, 4] or None,
+    weight fp32 [P], voxels, dropped). pts3d fp32 [n, H, W, 3], depth fp32 [n, H, W], valid bool [n, H, W] or None, views fp32 [n, 16],
+    centres fp32 [n, 3], rgba uint8 [n, H, W, 4], weight fp32 [n, H, W] on the HIP device. `capacity`: the table's size, a power of two
+    (default: >= 4 x the taking-part pixels, which are counted with torch). Mark, compact, integrate, count and write are HIP launches;
+    the marked keys are sorted with torch.sort. Raises TsdfTableFull when the table overflowed."""
+    n, H, W, valid = _tsdf_maps(pts3d, depth, valid, rgba, weight)
+    dev = pts3d.device
+    none = (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+            torch.empty(0, device=dev, dtype=torch.float32), 0, 0)
+    if capacity is None:
+        part = torch.isfinite(pts3d).all(-1) & torch.isfinite(depth) & (depth > torch.tensor(float(near), dtype=torch.float32, device=dev))
+        taking = int((part if valid is None else part & valid).sum())
+        if taking == 0:                                             # no pixel: no table
+            return none
+        capacity = tsdf_capacity(taking)
+    table, counters = tsdf_mark(pts3d, depth, valid, centres, voxel=voxel, trunc=trunc, near=near, capacity=capacity)
+    keys, count = tsdf_compact(table)
+    M, dropped, overflow = torch.cat([count, counters]).tolist()
+    if overflow:
+        raise TsdfTableFull(f"tsdf_points: overflow = {overflow} > 0: that many samples found no free slot among the table's capacity = "
+                            f"{capacity}; pass capacity >= {1 << (int(capacity) + overflow - 1).bit_length()}")
+    if M == 0:
+        return (*none[:3], 0, dropped)
+    K = torch.sort(keys[:M]).values.contiguous()                    # keys < 2^63: signed order is unsigned order
+    f, wt, col = tsdf_integrate(K, depth, valid, views, rgba, weight, voxel=voxel, trunc=trunc, near=near)
+    return (*tsdf_extract(K, f, wt, col, voxel=voxel, min_weight=min_weight), M, dropped)
+
+
 def focal_shift(points, weight=None, thr=0.5, downsample_size=None, z_offset=None, iters=40):
     """(shift [B], focal [B] fp32, status [B] int32) of point maps `points` fp32 [B, H, W, 3] (any map stride: `pred[:, 0]` is used in
     place): the z-shift and normalised focal that minimise sum |focal * xy / (z + shift) - uv|^2 over the pixels with `weight` [B, H, W]

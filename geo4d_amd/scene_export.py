@@ -67,7 +67,7 @@ def motion_part(scene, msk, motion, **seg_kw):
 
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
                             transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
-                            motion=None, fuse_voxel=None):
+                            motion=None, fuse_voxel=None, tsdf_voxel=None):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
@@ -78,12 +78,22 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     faces that are not dynamic, "dynamic" only the dynamic ones; the masks are scene.dynamic_masks, made by
     geo4d_amd.motion.segment_motion with this call's thresholds and its default rule when the scene has none yet. `fuse_voxel`: None
     (or False) exports every pixel's point; a voxel size, or True for geo4d_amd.fusion.fuse_scene's default, exports the voxel-merged
-    cloud of fuse_scene (same masks, thresholds and `motion`; also left in scene.fused) and needs as_pointcloud=True."""
+    cloud of fuse_scene (same masks, thresholds and `motion`; also left in scene.fused) and needs as_pointcloud=True. `tsdf_voxel`:
+    None (or False) likewise; a voxel size, or True for geo4d_amd.tsdf.tsdf_scene's default, exports the surface points of tsdf_scene
+    (same masks and thresholds, `motion` None or "static"; also left in scene.tsdf); it needs as_pointcloud=True and excludes
+    `fuse_voxel`."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
     fuse = fuse_voxel is not None and fuse_voxel is not False
     if fuse and not as_pointcloud:
         raise ValueError("get_3D_model_from_scene: fuse_voxel merges points and has no faces to give: it needs as_pointcloud=True")
+    tsdf = tsdf_voxel is not None and tsdf_voxel is not False
+    if tsdf and fuse:
+        raise ValueError("get_3D_model_from_scene: fuse_voxel and tsdf_voxel are two different clouds of the same points: give one of them")
+    if tsdf and not as_pointcloud:
+        raise ValueError("get_3D_model_from_scene: tsdf_voxel gives surface points and has no faces to give: it needs as_pointcloud=True")
+    if tsdf and motion == "dynamic":
+        raise ValueError("get_3D_model_from_scene: tsdf_voxel with motion='dynamic': the moving part has no TSDF")
     if scene is None:
         return None
     if mask_sky:
@@ -110,6 +120,11 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
             fused = fuse_scene(scene, voxel=None if fuse_voxel is True else fuse_voxel, motion=motion, min_conf_thr=min_conf_thr,
                                thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
             geometry = [dict(mode=0, positions=fused["points"].cpu().numpy(), colors=fused["rgba"].cpu().numpy())] if len(fused["points"]) else []
+        elif tsdf:
+            from .tsdf import tsdf_scene
+            surf = tsdf_scene(scene, voxel=None if tsdf_voxel is True else tsdf_voxel, motion=motion, min_conf_thr=min_conf_thr,
+                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+            geometry = [dict(mode=0, positions=surf["points"].cpu().numpy(), colors=surf["rgba"].cpu().numpy())] if len(surf["points"]) else []
         elif as_pointcloud:
             pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
             c = int(count.item())
@@ -126,7 +141,8 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
                               cam_color=camera_colors(n))
 
 
-def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynamic_masks=False, fuse_static=None, **glb_kw):
+def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynamic_masks=False, fuse_static=None, tsdf_static=None,
+               **glb_kw):
     """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
     cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
     previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
@@ -136,7 +152,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     <seq>_static.glb, the glb without the moving points. `fuse_static`: a voxel size, or True for fuse_scene's default, also writes
     <seq>_static_fused.glb, the static points merged into one cloud (get_3D_model_from_scene(motion="static", fuse_voxel=...), always a
     point cloud); it segments motion first when the scene has no masks, and writes no other file: the dynamic_mask PNGs and
-    <seq>_static.glb stay with `dynamic_masks`. Returns the directory."""
+    <seq>_static.glb stay with `dynamic_masks`. `tsdf_static`: a voxel size, or True for tsdf_scene's default, likewise also writes
+    <seq>_static_tsdf.glb, the surface points of the static part's TSDF (get_3D_model_from_scene(motion="static", tsdf_voxel=...)), and
+    nothing else. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -156,6 +174,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     if fuse_static is not None and fuse_static is not False:
         get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_fused",
                                 **dict(kw, motion="static", as_pointcloud=True, fuse_voxel=fuse_static))
+    if tsdf_static is not None and tsdf_static is not False:
+        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf",
+                                **dict(kw, motion="static", as_pointcloud=True, tsdf_voxel=tsdf_static))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())

@@ -572,6 +572,49 @@ int geo4d_fuse_finalize(const long* order, long M, const float* points, const un
                         int reduce, long capacity, float* points_out, unsigned char* rgba_out, float* weight_out, int* count_out,
                         const void* workspace, size_t workspace_bytes, void* stream);
 
+/* The static scene denoised: a truncated signed distance function (TSDF) over the voxels near a surface, averaged over every image that
+ * sees them, and the surface points where it crosses zero (geo4d_amd/csrc/tsdf.hip, geo4d_amd/tsdf.py). The reference has no such step;
+ * the rule is this project's own, restated in numpy in tests/tsdf_restatement.py.
+ *   Device arrays: pts3d [n][H][W][3] fp32, depth [n][H][W] fp32, valid [n][H][W] bytes (NULL: all), views [n][16] fp32 exactly as
+ *   geo4d_motion_votes takes them, centres [n][3] fp32 (the camera centres), rgba [n][H][W][4] u8 (NULL: no colours), weight [n][H][W]
+ *   fp32 (NULL: every weight is 1); n, H, W > 0, n H W < 2^31; voxel v > 0 finite; truncation T = 1 .. 8 voxels, trunc = (float)T * v;
+ *   near >= 0; min_weight > 0. All float arithmetic is fp32 in the written order, no FMA; only division, no sqrt.
+ *   geo4d_tsdf_mark: table := empty, counters[0] (dropped) := counters[1] (overflow) := 0, then one launch over the pixels. Pixel (i, p)
+ *     takes part iff it is valid, its point P and depth are finite and depth > near. d = P - C_i, s = (v * 0.5f) / depth; for
+ *     k = -2T .. 2T the sample is P_a + ((float)k * s) * d_a (a step of v / 2 in camera z) and its cell floorf(sample_a / v). Keys are
+ *     geo4d_fuse_insert's: (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20), |c| < 2^20, all ones = empty, unsigned order = (cx, cy,
+ *     cz) order; a sample whose cell is out of range is counted in dropped. workspace: geo4d_tsdf_workspace bytes (0 for a capacity
+ *     that is no power of two in 1 .. 2^32), 8-byte aligned = `capacity` 64-bit keys, open addressing with linear probing from a 64-bit
+ *     mix of the key: a relaxed read, a 64-bit CAS only on an empty slot, forward probing, no lane waits for another. A sample that
+ *     has probed `capacity` slots without a home is counted in overflow and gives up (as does every lane that then sees overflow != 0):
+ *     the caller must refuse the table. The marked set is a set: its content depends neither on arrival order nor on capacity.
+ *   geo4d_tsdf_compact: *count := the number of occupied slots; their keys go to keys_out [max_keys] in arrival order (keys beyond
+ *     max_keys are counted, not written). The caller sorts them: K[0..M).
+ *   geo4d_tsdf_integrate: one thread per voxel m with centre X_a = ((float)c_a + 0.5f) * v; for j = 0 .. n-1 in that order:
+ *     xc = ((r00 X + r01 Y) + r02 Z) + t0, likewise yc, zc; skipped unless all three are finite and zc > near; u = fx (xc / zc) + cx,
+ *     v = fy (yc / zc) + cy; column = floorf(u + 0.5f), row = floorf(v + 0.5f), inside / outside decided in float before any cast;
+ *     skipped unless j's pixel there is valid, its depth finite and its weight w finite and > 0; sd = depth - zc; skipped if
+ *     sd < -trunc; t = fminf(1.f, sd / trunc); D += w * t; Wt += w; if also sd <= trunc: C_k += w * (float)rgba_k (k = 0..2), Wc += w.
+ *     f_out[m] = D / Wt, weight_out[m] = Wt, rgba_out[m] = (u8)clamp(floorf(C_k / Wc + 0.5f), 0, 255) (0 when Wc == 0), alpha 255.
+ *   geo4d_tsdf_count / geo4d_tsdf_write: voxel m is live iff Wt >= min_weight and |f| < 1. For live m and axis a = 0, 1, 2: m' = the
+ *     row of key K[m] + (1 << 42, 1 << 21, 1)[a], by binary search; if it exists, is live and (f >= 0) != (f' >= 0), one point:
+ *     X_a + (f / (f - f')) * v on axis a and the centre's coordinates on the other two, the colour of the voxel of smaller |f| (m on
+ *     ties), weight fminf(Wt, Wt'). count writes counts[m] = 0 .. 3; write puts voxel m's points at rows first_row[m] .. of points_out
+ *     [P][3], rgba_out [P][4] (NULL without colours) and weight_out [P], first_row = the exclusive prefix sum of counts and P their sum:
+ *     rows in (m, a) order.
+ *   Null pointers, bad sizes, a voxel that is not finite or <= 0, T outside 1 .. 8, near < 0, min_weight <= 0, a capacity that is no
+ *   power of two and a workspace that is too small return -EINVAL before any device work. */
+size_t geo4d_tsdf_workspace(long capacity);
+int geo4d_tsdf_mark(const float* pts3d, const float* depth, const unsigned char* valid, const float* centres, int n, int H, int W, float voxel,
+                    int trunc, float near, long capacity, long* counters, void* workspace, size_t workspace_bytes, void* stream);
+int geo4d_tsdf_compact(long capacity, long* keys_out, long max_keys, long* count, const void* workspace, size_t workspace_bytes, void* stream);
+int geo4d_tsdf_integrate(const long* keys, long M, const float* depth, const unsigned char* valid, const float* weight,
+                         const unsigned char* rgba, const float* views, int n, int H, int W, float voxel, int trunc, float near, float* f_out,
+                         float* weight_out, unsigned char* rgba_out, void* stream);
+int geo4d_tsdf_count(const long* keys, long M, const float* f, const float* weight, float min_weight, int* counts, void* stream);
+int geo4d_tsdf_write(const long* keys, long M, const float* f, const float* weight, const unsigned char* rgba, const long* first_row, long P,
+                     float voxel, float min_weight, float* points_out, unsigned char* rgba_out, float* weight_out, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:

@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""Time of the TSDF (geo4d_amd/tsdf.py, csrc/tsdf.hip) on the static part of a 64-image 320 x 512 synthetic scene
+(tools/scene_export_bench.py's: a wavy wall with a box sliding in front; the static part by geo4d_amd.motion's default rule), at the
+default voxel 2 * median(depth / focal), truncation 4 voxels, with colours and unit weights.
+
+Device time by HIP events round --inner back-to-back warm calls each of mark (the table reset included), compact, the torch.sort of the
+keys, integrate, extract (count, cumsum, write and the read-back of P) and the whole ops.tsdf_points (which also counts the taking-part
+pixels with torch and reads the counts back); median and best of --reps such windows. The baseline is the same rule written with torch
+ops (torch.unique for the marked set, one pass of elementwise kernels per image for the integration, torch.searchsorted for the
+neighbours) on the same device in the same process, and its result is compared with the kernels'. Prints one JSON line.
+usage: tsdf_bench.py [--frames 64] [--trunc 4] [--reps 20] [--inner 5]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from geo4d_amd import fusion, motion, ops  # noqa: E402
+from geo4d_amd.render import _views  # noqa: E402
+from tools.motion_bench import device_ms  # noqa: E402
+from tools.scene_export_bench import synthetic_scene  # noqa: E402
+
+LIMIT = 1 << 20
+
+
+def torch_tsdf(pts3d, depth, valid, views, centres, rgba, voxel, T, min_weight, near):
+    """The rule of include/geo4d_hip.h with torch ops, unit weights (no range check: the scene is inside). views: host [n, 16]."""
+    dev = pts3d.device
+    n, H, W = depth.shape
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32, device=dev)
+    v, trunc = f32(voxel), f32(float(T)) * f32(voxel)
+    part = valid & torch.isfinite(pts3d).all(-1) & torch.isfinite(depth) & (depth > f32(near))
+    img = part.nonzero()[:, 0]
+    P = pts3d[part]
+    d = P - centres[img]
+    s = (v * 0.5) / depth[part]
+    k = torch.arange(-2 * T, 2 * T + 1, device=dev, dtype=torch.float32)
+    ks = k[None, :] * s[:, None]
+    S = P[:, None, :] + ks[:, :, None] * d[:, None, :]
+    c = torch.floor(S / v).long().reshape(-1, 3) + LIMIT
+    K = torch.unique((c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2])
+    del S, c, ks
+    M = K.shape[0]
+    cells = torch.stack([(K >> 42) - LIMIT, ((K >> 21) & 0x1fffff) - LIMIT, (K & 0x1fffff) - LIMIT], 1)
+    X = (cells.float() + 0.5) * v
+    x, y, z = X[:, 0].contiguous(), X[:, 1].contiguous(), X[:, 2].contiguous()
+    D, Wt, Wc = (torch.zeros(M, device=dev) for _ in range(3))
+    C = torch.zeros((M, 3), device=dev)
+    one = f32(1.0)
+    for j in range(n):
+        V = [f32(a) for a in views[j].tolist()]
+        xc = ((V[0] * x + V[1] * y) + V[2] * z) + V[3]
+        yc = ((V[4] * x + V[5] * y) + V[6] * z) + V[7]
+        zc = ((V[8] * x + V[9] * y) + V[10] * z) + V[11]
+        ok = torch.isfinite(xc) & torch.isfinite(yc) & torch.isfinite(zc) & (zc > f32(near))
+        col = torch.floor((V[12] * (xc / zc) + V[14]) + 0.5)
+        row = torch.floor((V[13] * (yc / zc) + V[15]) + 0.5)
+        ok &= (col >= 0) & (col < W) & (row >= 0) & (row < H)
+        q = torch.where(ok, row * W + col, torch.zeros_like(col)).long()
+        dj = depth[j].reshape(-1)[q]
+        ok &= valid[j].reshape(-1)[q] & torch.isfinite(dj)
+        sd = dj - zc
+        ok &= ~(sd < -trunc)
+        t = torch.minimum(one, sd / trunc)
+        D = torch.where(ok, D + t, D)                                                # w = 1: w * t = t exactly
+        Wt = torch.where(ok, Wt + 1.0, Wt)
+        inner = ok & (sd <= trunc)
+        C = torch.where(inner[:, None], C + rgba[j].reshape(-1, 4)[q][:, :3].float(), C)
+        Wc = torch.where(inner, Wc + 1.0, Wc)
+    f = D / Wt
+    colq = torch.floor(C / Wc[:, None] + 0.5).clamp(0.0, 255.0)
+    colq = torch.where(Wc[:, None] > 0, colq, torch.zeros_like(colq)).to(torch.uint8)
+    colq = torch.cat([colq, torch.full((M, 1), 255, dtype=torch.uint8, device=dev)], 1)
+    live = (Wt >= f32(min_weight)) & (f.abs() < 1)
+    hit, other = [], []
+    for a in range(3):
+        target = K + (1 << (42 - 21 * a))
+        at = torch.searchsorted(K, target).clamp(max=M - 1)
+        ok = (cells[:, a] + 1 < LIMIT) & (K[at] == target)
+        hit.append(ok & live & live[at] & ((f >= 0) != (f[at] >= 0)))
+        other.append(at)
+    m, a = torch.stack(hit, 1).nonzero().unbind(1)                                   # row-major: (m, a) order
+    m2 = torch.stack(other, 1)[m, a]
+    pts = X[m].clone()
+    pts[torch.arange(len(m), device=dev), a] = X[m, a] + (f[m] / (f[m] - f[m2])) * v
+    pick = torch.where(f[m2].abs() < f[m].abs(), m2, m)
+    return pts, colq[pick], torch.minimum(Wt[m], Wt[m2]), M
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--trunc", type=int, default=4)
+    ap.add_argument("--min-weight", type=float, default=4.0)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    n, H, W, T, near = args.frames, 320, 512, args.trunc, 1e-3
+    s = synthetic_scene(n, H, W, dev)
+    pts3d, depth = s["pts3d"].contiguous(), s["depth"].contiguous()
+    every = torch.ones((n, H, W), dtype=torch.bool, device=dev)
+    c2w, K = s["c2w"].double().cpu(), s["K"].double().cpu()
+    static = (~motion.dynamic_mask(motion.motion_votes(pts3d, depth, every, c2w, K))).contiguous()
+    views_host = _views(c2w, K)
+    views, centres = views_host.to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
+    rgba = torch.randint(0, 256, (n, H, W, 4), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).to(dev)
+    voxel = torch.tensor(fusion.default_voxel(depth, torch.full((n,), s["f"], device=dev), static), dtype=torch.float32).item()
+    taking = int(static.sum())
+    capacity = ops.tsdf_capacity(taking)
+    kw = dict(voxel=voxel, trunc=T, near=near)
+
+    table, counters = ops.tsdf_mark(pts3d, depth, static, centres, capacity=capacity, **kw)
+    keys, count = ops.tsdf_compact(table)
+    M = int(count)
+    assert counters.tolist() == [0, 0], counters
+    sort = lambda: torch.sort(keys[:M]).values.contiguous()
+    Ks = sort()
+    f, wt, col = ops.tsdf_integrate(Ks, depth, static, views, rgba, None, **kw)
+    got = ops.tsdf_extract(Ks, f, wt, col, voxel=voxel, min_weight=args.min_weight)
+    P = len(got[0])
+    out = {"frames": n, "H": H, "W": W, "trunc": T, "min_weight": args.min_weight, "pixels_M": n * H * W / 1e6, "taking_part_M": taking / 1e6,
+           "voxel": voxel, "voxels": M, "points_P": P, "capacity": capacity, "load": M / capacity,
+           "workspace_GB": (table.numel() * 8 + keys.numel() * 8 + M * (8 + 4 + 4 + 4 + 4 + 8)) / 1e9, "reps": args.reps,
+           "calls_per_window": args.inner, "device": torch.cuda.get_device_name(0)}
+    for name, fn in (("mark", lambda: ops.tsdf_mark(pts3d, depth, static, centres, capacity=capacity, **kw)),
+                     ("reset", lambda: ops.tsdf_mark(pts3d, depth, torch.zeros_like(static), centres, capacity=capacity, **kw)),
+                     ("compact", lambda: ops.tsdf_compact(table)), ("sort", sort),
+                     ("integrate", lambda: ops.tsdf_integrate(Ks, depth, static, views, rgba, None, **kw)),
+                     ("integrate_no_colour", lambda: ops.tsdf_integrate(Ks, depth, static, views, None, None, **kw)),
+                     ("extract", lambda: ops.tsdf_extract(Ks, f, wt, col, voxel=voxel, min_weight=args.min_weight)),
+                     ("tsdf_points", lambda: ops.tsdf_points(pts3d, depth, static, views, centres, rgba, None, min_weight=args.min_weight, **kw)),
+                     ("tsdf_points_given_capacity", lambda: ops.tsdf_points(pts3d, depth, static, views, centres, rgba, None, capacity=capacity,
+                                                                            min_weight=args.min_weight, **kw))):
+        out[name + "_ms"], out[name + "_ms_best"] = device_ms(fn, args.reps, args.inner)
+    samples = taking * (4 * T + 1)
+    out["samples_M"] = samples / 1e6
+    out["samples_G_per_s"] = samples / ((out["mark_ms"] - out["reset_ms"]) * 1e-3) / 1e9
+    out["projections_G"] = n * M / 1e9
+    out["projections_G_per_s"] = n * M / (out["integrate_ms"] * 1e-3) / 1e9
+    whole = ops.tsdf_points(pts3d, depth, static, views, centres, rgba, None, min_weight=args.min_weight, **kw)
+    out["stages_equal_whole"] = all(torch.equal(a, b) for a, b in zip(got, whole[:3])) and whole[3] == M
+    if not args.no_torch:
+        targs = (pts3d, depth, static, views_host, centres, rgba, voxel, T, args.min_weight, near)
+        ref = torch_tsdf(*targs)
+        out["torch_voxels_equal"] = ref[3] == M
+        out["torch_equal"] = ref[3] == M and all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(got, ref[:3]))
+        if not out["torch_equal"] and ref[0].shape == got[0].shape:
+            out["torch_rows_differing"] = int(((ref[0] != got[0]).any(1) | (ref[1] != got[1]).any(1) | (ref[2] != got[2])).sum())
+        out["torch_ms"], out["torch_ms_best"] = device_ms(lambda: torch_tsdf(*targs), 3, 1)
+        out["speedup_vs_torch"] = out["torch_ms"] / out["tsdf_points_ms"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
