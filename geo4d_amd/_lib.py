@@ -233,6 +233,12 @@ SIGNATURES = {
     "geo4d_tsdf_count": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "geo4d_tsdf_write": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_mesh_cells": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_mesh_count": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_mesh_vertices": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_tsdf_mesh_faces": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long,
+                                        C.c_void_p, C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

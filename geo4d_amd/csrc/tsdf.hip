@@ -34,12 +34,11 @@
 #include <cmath>
 #include "common.h"
 #include "geo4d_hip.h"
+#include "tsdf_field.h"                                                              // u64, centre_of, live, find_key, voxel_ok, refuse
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr u64 EMPTY = ~0ull;
 constexpr int VIEW_FLOATS = 16;
@@ -145,13 +144,6 @@ __global__ __launch_bounds__(256) void tsdf_compact_kernel(const u64* __restrict
     }
 }
 
-__device__ __forceinline__ void centre_of(u64 key, float v, float& X, float& Y, float& Z) {
-    const int cx = (int)(key >> 42) - (1 << 20), cy = (int)((key >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(key & 0x1fffffu) - (1 << 20);
-    X = ((float)cx + 0.5f) * v;
-    Y = ((float)cy + 0.5f) * v;
-    Z = ((float)cz + 0.5f) * v;
-}
-
 __device__ __forceinline__ unsigned colour_byte(float c, float wc) {
     if (!(wc > 0.f)) return 0u;
     float t = floorf(c / wc + 0.5f);
@@ -204,19 +196,6 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const long* __restr
     wt_out[m] = Wt;
     if (rgba_out)
         *(unsigned*)(rgba_out + m * 4) = colour_byte(C0, Wc) | (colour_byte(C1, Wc) << 8) | (colour_byte(C2, Wc) << 16) | (255u << 24);
-}
-
-__device__ __forceinline__ bool live(float f, float wt, float min_weight) { return wt >= min_weight && fabsf(f) < 1.f; }
-
-// the row of `target` in K[lo..M), or -1; unsigned order, so a key with bit 63 set (a carry out of the x field) is beyond every row
-__device__ __forceinline__ long find_key(const long* __restrict__ K, long lo, long M, u64 target) {
-    long hi = M;
-    while (lo < hi) {
-        const long mid = lo + ((hi - lo) >> 1);
-        if ((u64)K[mid] < target) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < M && (u64)K[lo] == target ? lo : -1;
 }
 
 // the live neighbours of live voxel m across which f changes sign: nb[a] = the row, or -1
@@ -278,15 +257,7 @@ __global__ __launch_bounds__(256) void tsdf_write_kernel(const long* __restrict_
 
 bool dims_ok(int n, int H, int W) { return n > 0 && H > 0 && W > 0 && (long)n * H * W < (1L << 31); }
 bool capacity_ok(long capacity) { return capacity >= 1 && capacity <= (1L << 32) && (capacity & (capacity - 1)) == 0; }
-bool voxel_ok(float voxel) { return voxel > 0.f && voxel < INFINITY; }
 bool trunc_ok(int T) { return T >= 1 && T <= MAX_TRUNC; }
-
-int refuse(const char* who, const char* what) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    geo4d_set_error(msg);
-    return GEO4D_EINVAL;
-}
 
 }  // namespace
 

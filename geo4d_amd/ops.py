@@ -1496,21 +1496,57 @@ def tsdf_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
     return pts, col, w
 
 
-def tsdf_points(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
-    """The surface points of the TSDF of a scene (the rule of include/geo4d_hip.h): (points fp32 [P, 3], rgba uint8 [P, 4] or None,
-    weight fp32 [P], voxels, dropped). pts3d fp32 [n, H, W, 3], depth fp32 [n, H, W], valid bool [n, H, W] or None, views fp32 [n, 16],
-    centres fp32 [n, 3], rgba uint8 [n, H, W, 4], weight fp32 [n, H, W] on the HIP device. `capacity`: the table's size, a power of two
-    (default: >= 4 x the taking-part pixels, which are counted with torch). Mark, compact, integrate, count and write are HIP launches;
-    the marked keys are sorted with torch.sort. Raises TsdfTableFull when the table overflowed."""
+def tsdf_mesh_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
+    """(vertices fp32 [V, 3], rgba uint8 [V, 4] or None, weight fp32 [V], faces int32 [T, 3]): the surface of the field as one indexed
+    triangle mesh by naive surface nets (the rule of include/geo4d_hip.h): one vertex per used cell in key order, two triangles per
+    sign-changing pair of live neighbours whose four surrounding cells are complete, in (voxel, axis) order, front faces toward positive
+    f. keys int64 [M] sorted, f / wt / rgba as tsdf_integrate returns them. A cells and a count launch, two torch.cumsum, a vertices
+    and a faces launch; reads (Q, V) back (one synchronisation)."""
+    lib = _lib.load()
+    M, dev = _tsdf_keys(keys), keys.device
+    for t, what in ((f, "f"), (wt, "wt")):
+        assert _dev(t, what).dtype == torch.float32 and tuple(t.shape) == (M,) and t.is_contiguous(), (what, t.dtype, t.shape)
+    if rgba is not None:
+        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (M, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+    empty = lambda: (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+                     torch.empty(0, device=dev, dtype=torch.float32), torch.empty((0, 3), device=dev, dtype=torch.int32))
+    if M == 0:
+        return empty()
+    complete = torch.empty(M, device=dev, dtype=torch.uint8)
+    used = torch.empty(M, device=dev, dtype=torch.uint8)
+    counts = torch.empty(M, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_tsdf_mesh_cells(keys.data_ptr(), M, f.data_ptr(), wt.data_ptr(), float(min_weight), complete.data_ptr(), _stream()),
+               "geo4d_tsdf_mesh_cells")
+    _lib.check(lib.geo4d_tsdf_mesh_count(keys.data_ptr(), M, complete.data_ptr(), counts.data_ptr(), used.data_ptr(), _stream()),
+               "geo4d_tsdf_mesh_count")
+    last_quad = torch.cumsum(counts, 0, dtype=torch.int64)
+    last_vertex = torch.cumsum(used, 0, dtype=torch.int64)
+    Q, V = torch.stack([last_quad[-1], last_vertex[-1]]).tolist()
+    if Q == 0:
+        return empty()
+    first_quad, first_vertex = (last_quad - counts).contiguous(), (last_vertex - used).contiguous()
+    vertices = torch.empty((V, 3), device=dev, dtype=torch.float32)
+    col = None if rgba is None else torch.empty((V, 4), device=dev, dtype=torch.uint8)
+    w = torch.empty(V, device=dev, dtype=torch.float32)
+    faces = torch.empty((2 * Q, 3), device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_tsdf_mesh_vertices(keys.data_ptr(), M, f.data_ptr(), wt.data_ptr(), _ptr(rgba), used.data_ptr(), first_vertex.data_ptr(),
+                                            V, float(voxel), vertices.data_ptr(), _ptr(col), w.data_ptr(), _stream()), "geo4d_tsdf_mesh_vertices")
+    _lib.check(lib.geo4d_tsdf_mesh_faces(keys.data_ptr(), M, f.data_ptr(), complete.data_ptr(), counts.data_ptr(), first_quad.data_ptr(),
+                                         first_vertex.data_ptr(), Q, V, faces.data_ptr(), _stream()), "geo4d_tsdf_mesh_faces")
+    return vertices, col, w, faces
+
+
+def tsdf_field(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3, capacity=None):
+    """The TSDF field of a scene (the rule of include/geo4d_hip.h): (K int64 [M] sorted keys, f fp32 [M], wt fp32 [M], col uint8 [M, 4]
+    or None, M, dropped); K, f, wt and col are None when no voxel was marked. Inputs as tsdf_points takes them. Mark, compact and
+    integrate are HIP launches; the marked keys are sorted with torch.sort. Raises TsdfTableFull when the table overflowed."""
     n, H, W, valid = _tsdf_maps(pts3d, depth, valid, rgba, weight)
     dev = pts3d.device
-    none = (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
-            torch.empty(0, device=dev, dtype=torch.float32), 0, 0)
     if capacity is None:
         part = torch.isfinite(pts3d).all(-1) & torch.isfinite(depth) & (depth > torch.tensor(float(near), dtype=torch.float32, device=dev))
         taking = int((part if valid is None else part & valid).sum())
         if taking == 0:                                             # no pixel: no table
-            return none
+            return None, None, None, None, 0, 0
         capacity = tsdf_capacity(taking)
     table, counters = tsdf_mark(pts3d, depth, valid, centres, voxel=voxel, trunc=trunc, near=near, capacity=capacity)
     keys, count = tsdf_compact(table)
@@ -1519,9 +1555,23 @@ def tsdf_points(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, 
         raise TsdfTableFull(f"tsdf_points: overflow = {overflow} > 0: that many samples found no free slot among the table's capacity = "
                             f"{capacity}; pass capacity >= {1 << (int(capacity) + overflow - 1).bit_length()}")
     if M == 0:
-        return (*none[:3], 0, dropped)
+        return None, None, None, None, 0, dropped
     K = torch.sort(keys[:M]).values.contiguous()                    # keys < 2^63: signed order is unsigned order
-    f, wt, col = tsdf_integrate(K, depth, valid, views, rgba, weight, voxel=voxel, trunc=trunc, near=near)
+    return (K, *tsdf_integrate(K, depth, valid, views, rgba, weight, voxel=voxel, trunc=trunc, near=near), M, dropped)
+
+
+def tsdf_points(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
+    """The surface points of the TSDF of a scene (the rule of include/geo4d_hip.h): (points fp32 [P, 3], rgba uint8 [P, 4] or None,
+    weight fp32 [P], voxels, dropped). pts3d fp32 [n, H, W, 3], depth fp32 [n, H, W], valid bool [n, H, W] or None, views fp32 [n, 16],
+    centres fp32 [n, 3], rgba uint8 [n, H, W, 4], weight fp32 [n, H, W] on the HIP device. `capacity`: the table's size, a power of two
+    (default: >= 4 x the taking-part pixels, which are counted with torch). Mark, compact, integrate (tsdf_field), count and write are
+    HIP launches; the marked keys are sorted with torch.sort. Raises TsdfTableFull when the table overflowed."""
+    K, f, wt, col, M, dropped = tsdf_field(pts3d, depth, valid, views, centres, rgba, weight, voxel=voxel, trunc=trunc, near=near,
+                                           capacity=capacity)
+    if M == 0:
+        dev = pts3d.device
+        return (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+                torch.empty(0, device=dev, dtype=torch.float32), 0, dropped)
     return (*tsdf_extract(K, f, wt, col, voxel=voxel, min_weight=min_weight), M, dropped)
 
 

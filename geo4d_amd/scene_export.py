@@ -67,7 +67,7 @@ def motion_part(scene, msk, motion, **seg_kw):
 
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
                             transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
-                            motion=None, fuse_voxel=None, tsdf_voxel=None):
+                            motion=None, fuse_voxel=None, tsdf_voxel=None, tsdf_mesh=None):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
@@ -81,7 +81,10 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     cloud of fuse_scene (same masks, thresholds and `motion`; also left in scene.fused) and needs as_pointcloud=True. `tsdf_voxel`:
     None (or False) likewise; a voxel size, or True for geo4d_amd.tsdf.tsdf_scene's default, exports the surface points of tsdf_scene
     (same masks and thresholds, `motion` None or "static"; also left in scene.tsdf); it needs as_pointcloud=True and excludes
-    `fuse_voxel`."""
+    `fuse_voxel`. `tsdf_mesh`: None (or False) likewise; a voxel size, or True for tsdf_scene's default, exports the surface of
+    tsdf_scene(mesh=True) as one indexed TRIANGLES primitive (one clean surface in place of the n overlapping per-image sheets; same
+    masks and thresholds, `motion` None or "static"; also left in scene.tsdf); it needs as_pointcloud=False and excludes `fuse_voxel`
+    and `tsdf_voxel`."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
     fuse = fuse_voxel is not None and fuse_voxel is not False
@@ -94,6 +97,13 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         raise ValueError("get_3D_model_from_scene: tsdf_voxel gives surface points and has no faces to give: it needs as_pointcloud=True")
     if tsdf and motion == "dynamic":
         raise ValueError("get_3D_model_from_scene: tsdf_voxel with motion='dynamic': the moving part has no TSDF")
+    surface = tsdf_mesh is not None and tsdf_mesh is not False
+    if surface and (fuse or tsdf):
+        raise ValueError("get_3D_model_from_scene: tsdf_mesh writes triangles, fuse_voxel and tsdf_voxel write points: give one of them")
+    if surface and as_pointcloud:
+        raise ValueError("get_3D_model_from_scene: tsdf_mesh writes triangles: it needs as_pointcloud=False (tsdf_voxel gives the points)")
+    if surface and motion == "dynamic":
+        raise ValueError("get_3D_model_from_scene: tsdf_mesh with motion='dynamic': the moving part has no TSDF")
     if scene is None:
         return None
     if mask_sky:
@@ -125,6 +135,12 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
             surf = tsdf_scene(scene, voxel=None if tsdf_voxel is True else tsdf_voxel, motion=motion, min_conf_thr=min_conf_thr,
                               thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
             geometry = [dict(mode=0, positions=surf["points"].cpu().numpy(), colors=surf["rgba"].cpu().numpy())] if len(surf["points"]) else []
+        elif surface:
+            from .tsdf import tsdf_scene
+            surf = tsdf_scene(scene, voxel=None if tsdf_mesh is True else tsdf_mesh, motion=motion, min_conf_thr=min_conf_thr,
+                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, mesh=True)
+            geometry = [io.mesh_geometry(surf["vertices"].cpu().numpy(), surf["vertex_rgba"].cpu().numpy(), surf["faces"].cpu().numpy())] \
+                if len(surf["faces"]) else []
         elif as_pointcloud:
             pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
             c = int(count.item())
@@ -142,7 +158,7 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
 
 
 def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynamic_masks=False, fuse_static=None, tsdf_static=None,
-               **glb_kw):
+               tsdf_mesh_static=None, **glb_kw):
     """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
     cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
     previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
@@ -154,7 +170,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     point cloud); it segments motion first when the scene has no masks, and writes no other file: the dynamic_mask PNGs and
     <seq>_static.glb stay with `dynamic_masks`. `tsdf_static`: a voxel size, or True for tsdf_scene's default, likewise also writes
     <seq>_static_tsdf.glb, the surface points of the static part's TSDF (get_3D_model_from_scene(motion="static", tsdf_voxel=...)), and
-    nothing else. Returns the directory."""
+    nothing else. `tsdf_mesh_static`: a voxel size, or True for tsdf_scene's default, likewise also writes <seq>_static_tsdf_mesh.glb,
+    the static part's TSDF surface as a triangle mesh (get_3D_model_from_scene(motion="static", as_pointcloud=False, tsdf_mesh=...)),
+    and nothing else. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -177,6 +195,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     if tsdf_static is not None and tsdf_static is not False:
         get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf",
                                 **dict(kw, motion="static", as_pointcloud=True, tsdf_voxel=tsdf_static))
+    if tsdf_mesh_static is not None and tsdf_mesh_static is not False:
+        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf_mesh",
+                                **dict(kw, motion="static", as_pointcloud=False, tsdf_mesh=tsdf_mesh_static))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())

@@ -14,8 +14,17 @@ out ordered by voxel (cx, cy, cz), then axis.
 The defaults (voxel = ``fusion.default_voxel``, truncation 4 voxels, at least 4 observations) were chosen on the synthetic scene of
 tests/motion_restatement.py: at 2 % depth noise the surface points lie 0.025 RMS from the wall against 0.079 for the raw points, and with
 fewer than 4 observations a handful of points survive from the sphere pixels ``segment_motion`` leaves in the static part. Nobody has
-tried them on real predictions. Limits: points only, no triangles and no normals; one resolution; cell indices must stay below 2^20 in
-magnitude (samples beyond are refused, not clipped); a surface seen by fewer than ``min_weight`` images (in weight) gives no point; the
+tried them on real predictions.
+
+``tsdf_mesh`` (and ``tsdf_scene(mesh=True)``) turns the same field into one indexed triangle mesh by naive surface nets
+(csrc/tsdf_mesh.hip, restated in tests/tsdf_mesh_restatement.py): one vertex per cell of eight live voxels the surface passes through,
+at the mean of the cell's edge crossings, and two triangles per sign change between two neighbouring voxels, front faces toward the
+cameras; ``get_3D_model_from_scene(tsdf_mesh=...)`` and ``save_scene(tsdf_mesh_static=...)`` write it as a glb. On the synthetic scene
+at 2 % depth noise its vertices lie 0.017 RMS from the wall (the points: 0.025).
+
+Limits: no normals; the mesh is neither simplified nor smoothed, and where a grid face has four sign changes a mesh edge is shared by
+four triangles (a property of surface nets); one resolution; cell indices must stay below 2^20 in magnitude (samples beyond are refused,
+not clipped); a surface seen by fewer than ``min_weight`` images (in weight) gives no point, and a cell with such a voxel no vertex; the
 moving part has no TSDF (``motion="dynamic"`` is refused); the voxel table must hold every marked voxel, and a table that is too small
 is refused with the capacity to pass, never grown silently.
 """
@@ -81,6 +90,23 @@ def tsdf_points(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, vo
     of voxels marked and integrated. `capacity` overrides the voxel table's size (a power of two; default: >= 4 x the taking-part
     pixels); a table that is too small raises ops.TsdfTableFull naming the capacity to pass. Raises ValueError when a sample's cell
     index floor(x / voxel) reaches 2^20 in magnitude."""
+    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=True, mesh=False)
+
+
+@torch.no_grad()
+def tsdf_mesh(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
+    """dict(vertices fp32 [V, 3], rgba uint8 [V, 4] or None, weight fp32 [V], faces int32 [T, 3], voxels, dropped, overflow, voxel): the
+    surface of the TSDF as one indexed triangle mesh, on the device: naive surface nets (ops.tsdf_mesh_extract), about one vertex per
+    cell the surface passes through, ordered by cell (cx, cy, cz); two triangles per sign change between two neighbouring voxels whose
+    four surrounding cells are complete, ordered by voxel and axis, front faces toward the cameras. Inputs, checks and errors are
+    tsdf_points'. `weight` of a vertex is the smallest weight of its cell's eight voxels, its colour that of the voxel nearest the
+    surface."""
+    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=False, mesh=True)
+
+
+def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, *, points, mesh):
+    """The checks of tsdf_points, one field (ops.tsdf_field), and what is asked for of its surface: the points (`points`, rgba,
+    weight), the mesh, or both (then the mesh's colours and weights are `vertex_rgba`, `vertex_weight`)."""
     v = check_tsdf_args(voxel, trunc, min_weight, near, capacity)
     for t, what in ((pts3d, "pts3d"), (depth, "depth")):
         if not t.is_cuda:
@@ -96,22 +122,33 @@ def tsdf_points(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, vo
     if len(views) != shape[0]:
         raise ValueError(f"tsdf_points: {len(views)} cameras for {shape[0]} images")
     centres = torch.as_tensor(cams2world).detach().double().cpu().reshape(-1, 4, 4)[:, :3, 3].float().contiguous()
-    pts, rgba, w, voxels, dropped = ops.tsdf_points(pts3d.detach().float().contiguous(), depth.detach().float().contiguous(),
-                                                    None if valid is None else valid.to(dev), views.to(dev), centres.to(dev),
-                                                    _rgba(rgb, shape, dev), None if weight is None else weight.detach().float().contiguous(),
-                                                    voxel=v, trunc=int(trunc), min_weight=float(min_weight), near=float(near),
-                                                    capacity=None if capacity is None else int(capacity))
+    rgba = _rgba(rgb, shape, dev)
+    Kv, f, wt, col, voxels, dropped = ops.tsdf_field(pts3d.detach().float().contiguous(), depth.detach().float().contiguous(),
+                                                     None if valid is None else valid.to(dev), views.to(dev), centres.to(dev), rgba,
+                                                     None if weight is None else weight.detach().float().contiguous(), voxel=v,
+                                                     trunc=int(trunc), near=float(near), capacity=None if capacity is None else int(capacity))
     if dropped:
         raise ValueError(f"tsdf_points: {dropped} sample(s) lie outside the voxel grid: a cell index floor(x / voxel) must stay below 2^20 "
                          f"in magnitude, which at voxel = {v:g} means |x| < {(1 << 20) * v:g} on every axis; use a larger voxel or mask "
                          "the outliers")
-    return dict(points=pts, rgba=rgba, weight=w, voxels=voxels, dropped=0, overflow=0, voxel=v)
+    if voxels == 0:                                                 # no voxel: the empty field gives the empty outputs
+        Kv, f, wt = torch.empty(0, device=dev, dtype=torch.int64), torch.empty(0, device=dev), torch.empty(0, device=dev)
+        col = None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8)
+    out = {}
+    if points:
+        out["points"], out["rgba"], out["weight"] = ops.tsdf_extract(Kv, f, wt, col, voxel=v, min_weight=float(min_weight))
+    out.update(voxels=voxels, dropped=0, overflow=0, voxel=v)
+    if mesh:
+        vertices, vcol, vw, faces = ops.tsdf_mesh_extract(Kv, f, wt, col, voxel=v, min_weight=float(min_weight))
+        out.update(vertices=vertices, faces=faces, **(dict(vertex_rgba=vcol, vertex_weight=vw) if points else dict(rgba=vcol, weight=vw)))
+    return out
 
 
 @torch.no_grad()
 def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_init_conf=True, is_msk=True, use_conf=False, trunc=4,
-               min_weight=4.0, near=1e-3, capacity=None):
-    """tsdf_points on a GroupAligner; the result (see tsdf_points) is also stored as scene.tsdf.
+               min_weight=4.0, near=1e-3, capacity=None, mesh=False):
+    """tsdf_points on a GroupAligner; the result (see tsdf_points) is also stored as scene.tsdf. `mesh=True`: the dict additionally holds
+    the surface as a triangle mesh (see tsdf_mesh) from the same field: `vertices`, `faces`, `vertex_rgba`, `vertex_weight`.
 
     Points, colours and masks are taken exactly as fusion.fuse_scene and get_3D_model_from_scene take them: scene.get_pts3d(),
     scene.get_depthmaps(), scene.imgs (None: no colours) and scene.get_masks() with `min_conf_thr` / `thr_for_init_conf` set on the scene
@@ -138,6 +175,6 @@ def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_in
             voxel = 1.0
     c2w, K = _scene_cameras(scene)
     rgb = None if scene.imgs is None else scene.imgs.to(scene.dev).float()
-    scene.tsdf = tsdf_points(pts3d, depth, msk, c2w, K, rgb, scene.get_conf().detach() if use_conf else None, voxel=voxel, trunc=trunc,
-                             min_weight=min_weight, near=near, capacity=capacity)
+    scene.tsdf = _tsdf(pts3d, depth, msk, c2w, K, rgb, scene.get_conf().detach() if use_conf else None, voxel, trunc, min_weight, near,
+                       capacity, points=True, mesh=bool(mesh))
     return scene.tsdf

@@ -615,6 +615,47 @@ int geo4d_tsdf_count(const long* keys, long M, const float* f, const float* weig
 int geo4d_tsdf_write(const long* keys, long M, const float* f, const float* weight, const unsigned char* rgba, const long* first_row, long P,
                      float voxel, float min_weight, float* points_out, unsigned char* rgba_out, float* weight_out, void* stream);
 
+/* The TSDF's surface as one indexed triangle mesh: naive surface nets, the dual method (geo4d_amd/csrc/tsdf_mesh.hip, geo4d_amd/tsdf.py
+ * tsdf_mesh). The reference has no such step; the rule is this project's own, restated in numpy in tests/tsdf_mesh_restatement.py.
+ *   Inputs: exactly what geo4d_tsdf_integrate leaves: keys K int64 [M] sorted (cell index + 2^20 in three 21-bit fields), f fp32 [M],
+ *   weight Wt fp32 [M], rgba u8 [M][4] (NULL: no colours), plus the voxel v and min_weight. All arithmetic is fp32 in the written order,
+ *   no FMA; only + - * / are used.
+ *   Live is geo4d_tsdf_count's (Wt >= min_weight and |f| < 1); s(m) = f[m] >= 0; the step along axis a is E_a = (1 << 42, 1 << 21, 1)[a].
+ *     A key field holds 1 .. 2^21 - 1 for a real cell: + E_a out of a full field carries into a field of value 0 and - E_a from 1 gives
+ *     0, and no cell has either key, so no edge-of-grid test is needed in either direction.
+ *   Cell m is the cube whose eight corners are the voxel centres with keys K[m] + ox E_0 + oy E_1 + oz E_2, o in {0, 1}^3, corner index
+ *     4 ox + 2 oy + oz. It is complete iff all eight keys are in K and all eight voxels are live.
+ *   Face: for voxel m and axis a let m' = the row of K[m] + E_a; the pair qualifies if m and m' are live and s(m) != s(m'). With
+ *     b = (a + 1) % 3 and c = (a + 2) % 3 the four cells sharing that grid edge are r0 = m, r1 = m - E_b, r2 = m - E_b - E_c,
+ *     r3 = m - E_c; one quad is emitted iff all four exist in K and are complete. If f[m] < 0 the ring is (r0, r1, r2, r3) (positive f
+ *     is the free space in front of the surface, which is then on the + a side, and this ring is counter-clockwise seen from + a),
+ *     otherwise (r0, r3, r2, r1); the two triangles are (q0, q1, q2) and (q0, q2, q3) of the ring, so front faces look toward the
+ *     cameras. Quads are ordered by (m, a); triangle rows are 2 quad and 2 quad + 1.
+ *   Vertex: a cell is used iff an emitted quad names it; used cells get the ids 0 .. V - 1 in order of m. A complete cell with a sign
+ *     change but no emitted quad gets no vertex. For a = 0, 1, 2 and, within a, the four edges with the other two axes' offsets (0, 0),
+ *     (1, 0), (0, 1), (1, 1) (lower axis first): p = the corner with o_a = 0, q = the corner with o_a = 1; if s(p) != s(q):
+ *     t = f_p / (f_p - f_q), o with o_a replaced by t is added to S componentwise (S starts at 0, in this order), cnt += 1. The vertex is
+ *     X0_k + (S_k / (float)cnt) * v with X0 = ((float)cell + 0.5f) * v. Colour: that of the corner with the smallest |f|, the lowest
+ *     corner index on ties. Weight: the minimum Wt of the eight corners, by fminf in corner order.
+ *   geo4d_tsdf_mesh_cells: complete[m] = 0 for a cell that is not complete, else 1 | 2 x0 | 4 x1 | 8 x2 with x_a = s(m) != s(m + E_a)
+ *     (m + E_a is a corner of cell m). geo4d_tsdf_mesh_count: used := 0, then counts[m] = the quads of voxel m (0 .. 3) and used[r] = 1
+ *     for the four ring cells of each. The caller forms first_quad and first_vertex = the exclusive prefix sums of counts
+ *     and used, and Q, V = their sums. geo4d_tsdf_mesh_vertices writes vertex first_vertex[m] of every used cell to vertices_out [V][3],
+ *     rgba_out [V][4] (NULL without colours) and weight_out [V]; geo4d_tsdf_mesh_faces writes the triangles of quad first_quad[m] .. to
+ *     faces_out [2 Q][3] int32. One writer per row, no atomics: the output is a function of the inputs alone. A row offset outside the
+ *     output writes nothing.
+ *   Limits: M < 2^31, T = 2 Q. A grid face with four sign changes gives a mesh edge shared by four triangles: a property of the method.
+ *   Null pointers, M < 0 or >= 2^31, Q > 3 M, V > M, a voxel that is not finite or <= 0 and min_weight <= 0 return -EINVAL before any
+ *   device work. */
+int geo4d_tsdf_mesh_cells(const long* keys, long M, const float* f, const float* weight, float min_weight, unsigned char* complete,
+                          void* stream);
+int geo4d_tsdf_mesh_count(const long* keys, long M, const unsigned char* complete, int* counts, unsigned char* used, void* stream);
+int geo4d_tsdf_mesh_vertices(const long* keys, long M, const float* f, const float* weight, const unsigned char* rgba,
+                             const unsigned char* used, const long* first_vertex, long V, float voxel, float* vertices_out,
+                             unsigned char* rgba_out, float* weight_out, void* stream);
+int geo4d_tsdf_mesh_faces(const long* keys, long M, const float* f, const unsigned char* complete, const int* counts, const long* first_quad,
+                          const long* first_vertex, long Q, long V, int* faces_out, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
