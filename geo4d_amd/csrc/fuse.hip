@@ -7,8 +7,8 @@
 // Which points take part: point i takes part iff mask[i] (when given), X, Y, Z are finite, its weight w (when given; else 1) is finite
 //   and > 0, and per axis the cell c = floorf(X / v) satisfies fabsf(c) < 2^20. A point that fails only the last condition is counted
 //   in `dropped`; the others are skipped silently, as the renderer skips them.
-// Voxel key: (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20), below 2^63; all ones marks an empty slot. Unsigned key order is
-//   lexicographic (cx, cy, cz) order, the order of the output.
+// Voxel key (voxel_table.h): (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20), below 2^63; all ones marks an empty slot. Unsigned
+//   key order is lexicographic (cx, cy, cz) order, the order of the output.
 // Per point: offset q_a = (int)clamp(floorf((X_a - c_a v) / v * 65536.f + 0.5f), 0.f, 65535.f) (clamped as a float, then cast),
 //   weight wq = (int)clamp(floorf(w * 128.f + 0.5f), 1.f, 32767.f).
 // Per voxel, integer sums: count, sw = sum wq, sq_a = sum wq q_a, sc_k = sum wq rgba_k (k = 0..2), u64 each. N < 2^31, wq < 2^15 and
@@ -20,45 +20,27 @@
 //   float_bits(w) << 32 | (0xffffffff - i), the way the splat takes a minimum. Position, colour and weight are copied bit for bit;
 //   count is still the voxel's count.
 //
-// insert:   keys := all ones, accumulators := 0 (hipMemsetAsync), then one thread per point. The table is open addressing with linear
-//           probing from a 64-bit mix of the key, its capacity a power of two >= N. A lane reads the slot's key; on its own key it
-//           has found its slot, on an empty slot it tries a 64-bit atomicCAS (which succeeds or shows who won), otherwise it moves on.
-//           A lane only ever probes forward and waits for nobody; keys change once, from empty to their value, so a stale read can only
-//           cost a CAS. There are never more voxels than taking-part points, so a slot is always found. The sums are integer atomicAdd
-//           (atomicMax for best) whose results are not used; all eight of a voxel share one 64-byte line, and for mean a wave issues
-//           them line by line (see the kernel).
-// compact:  16 slots per thread; the occupied ones go out as (key, slot) pairs behind a device count, one atomicAdd per workgroup
-//           (one per wave serialised on the counter: 5.1 ms against 0.11 ms for 2^25 slots); pairs beyond the caller's max_pairs are
-//           counted and not written. Slot positions depend on arrival order, so the caller sorts the pairs by key before
+// insert:   keys := all ones, accumulators := 0 (hipMemsetAsync), then one thread per point. The table is voxel_table.h's: open
+//           addressing with linear probing from a 64-bit mix of the key, a 64-bit atomicCAS only on an empty slot, forward probing, no
+//           lane waits for another; its capacity is a power of two >= N. There are never more voxels than taking-part points, so a slot
+//           is always found. The sums are integer atomicAdd (atomicMax for best) whose results are not used; all eight of a voxel share
+//           one 64-byte line, and for mean a wave issues them line by line (see the kernel).
+// compact:  voxel_table.h's: 16 slots per thread; the occupied ones go out as (key, slot) pairs behind a device count, one atomicAdd
+//           per workgroup; pairs beyond the caller's max_pairs are counted and not written. Slot positions depend on arrival order, so
+//           the caller sorts the pairs by key before
 // finalize: one thread per output row, in the caller's order of slots.
 #include <cmath>
 #include "common.h"
 #include "geo4d_hip.h"
+#include "voxel_table.h"                                                             // u64, the key, the table and its checks, refuse
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr u64 EMPTY = ~0ull;
 constexpr int MEAN = 0, BEST = 1;
 constexpr int MEAN_WORDS = 8;       // sw, sq[3], sc[3], count
 constexpr int BEST_WORDS = 2;       // winner, count
-constexpr float CELL_LIMIT = 1048576.f;   // 2^20
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-    return fabsf(a) < INFINITY && fabsf(b) < INFINITY && fabsf(c) < INFINITY;      // NaN fails the comparison
-}
-
-__device__ __forceinline__ u64 mix64(u64 h) {
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
-}
 
 __device__ __forceinline__ u64 offset_q(float X, float c, float v) {
     float t = (X - c * v) / v * 65536.f + 0.5f;
@@ -87,25 +69,10 @@ __global__ __launch_bounds__(256) void fuse_insert_kernel(u64* __restrict__ keys
         const float w = weight ? weight[i] : 1.f;
         if (finite3(X, Y, Z) && w > 0.f && w < INFINITY) {
             const float cx = floorf(X / v), cy = floorf(Y / v), cz = floorf(Z / v);
-            if (!(fabsf(cx) < CELL_LIMIT && fabsf(cy) < CELL_LIMIT && fabsf(cz) < CELL_LIMIT)) {
+            if (!cell_ok(cx, cy, cz)) {
                 atomicAdd(dropped, 1ull);
             } else {
-                const u64 key = ((u64)((int)cx + (1 << 20)) << 42) | ((u64)((int)cy + (1 << 20)) << 21) | (u64)((int)cz + (1 << 20));
-                u64 at = mix64(key) & (capacity - 1);
-                // a slot is always found within `capacity` steps (see above); the bound only keeps a lane from spinning on a table it
-                // did not set up
-                for (u64 step = 0; step < capacity; ++step) {
-                    u64 seen = __atomic_load_n(keys + at, __ATOMIC_RELAXED);
-                    if (seen == EMPTY) {
-                        seen = atomicCAS(keys + at, EMPTY, key);
-                        if (seen == EMPTY) seen = key;
-                    }
-                    if (seen == key) {
-                        slot = at;
-                        break;
-                    }
-                    at = (at + 1) & (capacity - 1);
-                }
+                slot = claim_slot(keys, capacity, key_of(cx, cy, cz), nullptr);      // always found (see above)
                 if (WORDS == MEAN_WORDS) {
                     float t = floorf(w * 128.f + 0.5f);
                     t = t < 1.f ? 1.f : (t > 32767.f ? 32767.f : t);
@@ -150,47 +117,6 @@ __global__ __launch_bounds__(256) void fuse_insert_kernel(u64* __restrict__ keys
     }
 }
 
-constexpr int COMPACT_ROUNDS = 16;                                                   // slots per thread: one atomicAdd per 4 096 slots
-
-__global__ __launch_bounds__(256) void fuse_compact_kernel(const u64* __restrict__ keys, u64 capacity, long* __restrict__ key_out,
-                                                           long* __restrict__ slot_out, u64 max_pairs, u64* __restrict__ count) {
-    __shared__ unsigned wave_sum[4];
-    __shared__ u64 base_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 s0 = (u64)blockIdx.x * (256 * COMPACT_ROUNDS) + threadIdx.x;           // round r looks at slot s0 + 256 r
-    u64 key[COMPACT_ROUNDS];
-    unsigned mine = 0;
-#pragma unroll
-    for (int r = 0; r < COMPACT_ROUNDS; ++r) {
-        const u64 s = s0 + 256 * r;
-        key[r] = s < capacity ? keys[s] : EMPTY;
-        mine += key[r] != EMPTY;
-    }
-    unsigned incl = mine;                                                            // inclusive scan inside the wave
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-        base_s = total ? atomicAdd(count, (u64)total) : 0;
-    }
-    __syncthreads();
-    u64 pos = base_s + incl - mine;
-    for (int k = 0; k < wave; ++k) pos += wave_sum[k];
-#pragma unroll
-    for (int r = 0; r < COMPACT_ROUNDS; ++r) {
-        if (key[r] == EMPTY) continue;
-        if (pos < max_pairs) {                                                       // the count still says how many there were
-            key_out[pos] = (long)key[r];
-            slot_out[pos] = (long)(s0 + 256 * r);
-        }
-        ++pos;
-    }
-}
-
 __global__ __launch_bounds__(256) void fuse_finalize_kernel(const u64* __restrict__ keys, const u64* __restrict__ acc,
                                                             const long* __restrict__ order, long M, u64 capacity,
                                                             const float* __restrict__ points, const unsigned char* __restrict__ rgba,
@@ -207,7 +133,8 @@ __global__ __launch_bounds__(256) void fuse_finalize_kernel(const u64* __restric
         const u64 sw = a[0], n = a[7];
         if (key == EMPTY || sw == 0) return;                                         // an empty slot: likewise
         const double dv = (double)v, den = (double)sw * 65536.0;
-        const int c[3] = {(int)(key >> 42) - (1 << 20), (int)((key >> 21) & 0x1fffffu) - (1 << 20), (int)(key & 0x1fffffu) - (1 << 20)};
+        int c[3];
+        cell_of(key, c);
         for (int k = 0; k < 3; ++k) pts_out[m * 3 + k] = (float)(((double)c[k] + (double)a[1 + k] / den) * dv);
         if (rgba_out)
             *(unsigned*)(rgba_out + m * 4) = (unsigned)((a[4] + sw / 2) / sw) | ((unsigned)((a[5] + sw / 2) / sw) << 8) |
@@ -226,21 +153,15 @@ __global__ __launch_bounds__(256) void fuse_finalize_kernel(const u64* __restric
 }
 
 bool reduce_ok(int reduce) { return reduce == MEAN || reduce == BEST; }
-bool capacity_ok(long capacity) { return capacity >= 1 && capacity <= (1L << 32) && (capacity & (capacity - 1)) == 0; }
 size_t acc_words(int reduce) { return reduce == MEAN ? MEAN_WORDS : BEST_WORDS; }
 
-// the checks the three launches share; `who` prefixes the message
-int table_ok(const char* who, const void* workspace, size_t workspace_bytes, long capacity, int reduce) {
-    char msg[160];
-    const char* what = nullptr;
-    if (!workspace || (size_t)workspace % 8) what = "an 8-byte aligned workspace is required";
-    else if (!capacity_ok(capacity)) what = "capacity must be a power of two, 1 <= capacity <= 2^32";
-    else if (!reduce_ok(reduce)) what = "unknown reduce (0 mean, 1 best)";
-    else if (workspace_bytes < geo4d_fuse_workspace(capacity, reduce)) what = "workspace too small (geo4d_fuse_workspace bytes)";
-    if (!what) return GEO4D_OK;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    geo4d_set_error(msg);
-    return GEO4D_EINVAL;
+// the checks the three launches share. An unknown reduce makes geo4d_fuse_workspace 0, so it passes the table's last check and is
+// refused right after it: the refusals come in the order workspace, capacity, reduce, bytes.
+int fuse_table_ok(const char* who, const void* workspace, size_t workspace_bytes, long capacity, int reduce) {
+    if (int rc = table_ok(who, workspace, workspace_bytes, capacity, geo4d_fuse_workspace(capacity, reduce),
+                          "workspace too small (geo4d_fuse_workspace bytes)"))
+        return rc;
+    return reduce_ok(reduce) ? GEO4D_OK : refuse(who, "unknown reduce (0 mean, 1 best)");
 }
 
 }  // namespace
@@ -254,23 +175,12 @@ extern "C" size_t geo4d_fuse_workspace(long capacity, int reduce) {
 extern "C" int geo4d_fuse_insert(const float* points, const unsigned char* rgba, const float* weight, const unsigned char* mask, long N,
                                  float voxel, int reduce, long capacity, long* dropped, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-    if (!points || !dropped) {
-        geo4d_set_error("fuse_insert: points and dropped are required");
-        return GEO4D_EINVAL;
-    }
-    if (N < 0 || N >= (1L << 31)) {
-        geo4d_set_error("fuse_insert: need 0 <= N < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (!(voxel > 0.f && voxel < INFINITY)) {
-        geo4d_set_error("fuse_insert: voxel must be finite and > 0");
-        return GEO4D_EINVAL;
-    }
-    if (int rc = table_ok("fuse_insert", workspace, workspace_bytes, capacity, reduce)) return rc;
-    if (capacity < N) {
-        geo4d_set_error("fuse_insert: capacity must be >= N (there can be as many voxels as points)");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "fuse_insert";
+    if (!points || !dropped) return refuse(who, "points and dropped are required");
+    if (N < 0 || N >= (1L << 31)) return refuse(who, "need 0 <= N < 2^31");
+    if (!voxel_ok(voxel)) return refuse(who, "voxel must be finite and > 0");
+    if (int rc = fuse_table_ok(who, workspace, workspace_bytes, capacity, reduce)) return rc;
+    if (capacity < N) return refuse(who, "capacity must be >= N (there can be as many voxels as points)");
     hipStream_t s = (hipStream_t)stream;
     u64* keys = (u64*)workspace;
     if (hipMemsetAsync(keys, 0xff, (size_t)capacity * 8, s) != hipSuccess ||
@@ -293,42 +203,22 @@ extern "C" int geo4d_fuse_insert(const float* points, const unsigned char* rgba,
 
 extern "C" int geo4d_fuse_compact(long capacity, int reduce, long* keys_out, long* slots_out, long max_pairs, long* count, const void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    if (!keys_out || !slots_out || !count || max_pairs < 0) {
-        geo4d_set_error("fuse_compact: keys_out, slots_out [max_pairs >= 0] and count are required");
-        return GEO4D_EINVAL;
-    }
-    if (int rc = table_ok("fuse_compact", workspace, workspace_bytes, capacity, reduce)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(count, 0, sizeof(long), s) != hipSuccess) {
-        geo4d_set_error("fuse_compact: hipMemsetAsync failed");
-        return GEO4D_EIO;
-    }
-    hipLaunchKernelGGL(fuse_compact_kernel, dim3((unsigned)((capacity + 256 * COMPACT_ROUNDS - 1) / (256 * COMPACT_ROUNDS))), dim3(256), 0, s,
-                       (const u64*)workspace, (u64)capacity, keys_out, slots_out, (u64)max_pairs, (u64*)count);
-    GEO4D_CHECK_LAUNCH();
-    return GEO4D_OK;
+    const char* who = "fuse_compact";
+    if (!keys_out || !slots_out || !count || max_pairs < 0) return refuse(who, "keys_out, slots_out [max_pairs >= 0] and count are required");
+    if (int rc = fuse_table_ok(who, workspace, workspace_bytes, capacity, reduce)) return rc;
+    return table_compact<true>(who, workspace, capacity, keys_out, slots_out, max_pairs, count, (hipStream_t)stream);
 }
 
 extern "C" int geo4d_fuse_finalize(const long* order, long M, const float* points, const unsigned char* rgba, const float* weight, long N,
                                    float voxel, int reduce, long capacity, float* points_out, unsigned char* rgba_out, float* weight_out,
                                    int* count_out, const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!order || !points || !points_out || !weight_out || !count_out || (rgba_out && !rgba)) {
-        geo4d_set_error("fuse_finalize: order, points, points_out, weight_out and count_out are required, and rgba with rgba_out");
-        return GEO4D_EINVAL;
-    }
-    if (N < 0 || N >= (1L << 31) || M < 0 || M > N) {
-        geo4d_set_error("fuse_finalize: need 0 <= M <= N < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (!(voxel > 0.f && voxel < INFINITY)) {
-        geo4d_set_error("fuse_finalize: voxel must be finite and > 0");
-        return GEO4D_EINVAL;
-    }
-    if (int rc = table_ok("fuse_finalize", workspace, workspace_bytes, capacity, reduce)) return rc;
-    if (capacity < N) {
-        geo4d_set_error("fuse_finalize: capacity must be >= N (there can be as many voxels as points)");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "fuse_finalize";
+    if (!order || !points || !points_out || !weight_out || !count_out || (rgba_out && !rgba))
+        return refuse(who, "order, points, points_out, weight_out and count_out are required, and rgba with rgba_out");
+    if (N < 0 || N >= (1L << 31) || M < 0 || M > N) return refuse(who, "need 0 <= M <= N < 2^31");
+    if (!voxel_ok(voxel)) return refuse(who, "voxel must be finite and > 0");
+    if (int rc = fuse_table_ok(who, workspace, workspace_bytes, capacity, reduce)) return rc;
+    if (capacity < N) return refuse(who, "capacity must be >= N (there can be as many voxels as points)");
     if (M == 0) return GEO4D_OK;
     const u64* keys = (const u64*)workspace;
     hipLaunchKernelGGL(fuse_finalize_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys, keys + capacity,

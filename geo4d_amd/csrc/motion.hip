@@ -9,8 +9,8 @@
 //        pixel q carries dmin = NaN, which no range of a valid pixel can be (its own depth, when NaN, never wins a comparison and the
 //        range stays (+inf, -inf)), so the mask byte is folded into the gather.
 // votes: one thread per (image i, pixel p), blocks image-uniform, so voter j's 16 view floats are wave-uniform (scalar loads). For
-//        every j with 0 < |j - i| <= radius the world point goes to j's camera and pixel with the project's pixel rule (pixel k sits
-//        at coordinate k, inside / outside decided in float before any cast) and counts as
+//        every j with 0 < |j - i| <= radius the world point goes to j's camera and pixel with the project's pixel rule (scene_view.h:
+//        pixel k sits at coordinate k, inside / outside decided in float before any cast) and counts as
 //          free       zc < dmin lo   j sees past the place where the point was: it is not there at time j
 //          occluded   zc > dmax hi   something is in front: no evidence either way
 //          consistent otherwise
@@ -21,17 +21,13 @@
 #include <cmath>
 #include "common.h"
 #include "geo4d_hip.h"
+#include "scene_view.h"                                                              // the view, to_camera, project, pixel_of, dims_ok, refuse
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int VIEW_FLOATS = 16;      // world-to-camera rows 0..2 (12), then fx, fy, cx, cy
 constexpr int MAX_RADIUS = 127;      // counts <= 2 radius <= 254 fit a byte
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-    return fabsf(a) < INFINITY && fabsf(b) < INFINITY && fabsf(c) < INFINITY;      // NaN fails the comparison
-}
 
 __global__ __launch_bounds__(256) void motion_range_kernel(float2* __restrict__ range, const float* __restrict__ depth,
                                                            const unsigned char* __restrict__ valid, long total, int H, int W) {
@@ -73,14 +69,10 @@ __global__ __launch_bounds__(256) void motion_votes_kernel(unsigned char* __rest
         for (int j = j0; j <= j1; ++j) {
             if (j == i) continue;
             const float* M = views + (long)j * VIEW_FLOATS;
-            const float xc = ((M[0] * X + M[1] * Y) + M[2] * Z) + M[3];
-            const float yc = ((M[4] * X + M[5] * Y) + M[6] * Z) + M[7];
-            const float zc = ((M[8] * X + M[9] * Y) + M[10] * Z) + M[11];
-            if (!finite3(xc, yc, zc) || !(zc > near)) continue;
-            const float u = M[12] * (xc / zc) + M[14];
-            const float v = M[13] * (yc / zc) + M[15];
-            const float col = floorf(u + 0.5f), row = floorf(v + 0.5f);
-            if (!(col >= 0.f && col < fW && row >= 0.f && row < fH)) continue;     // outside, or NaN / Inf
+            float xc, yc, zc, u, v, col, row;
+            to_camera(M, X, Y, Z, xc, yc, zc);
+            if (!project(M, xc, yc, zc, near, u, v)) continue;
+            if (!pixel_of(u, v, fW, fH, col, row)) continue;
             const float2 r = range[(long)j * pts_per_image + (long)(int)row * W + (int)col];
             if (r.x != r.x) continue;                                               // j's pixel there is invalid
             if (zc < r.x * lo) ++free_;
@@ -93,8 +85,6 @@ __global__ __launch_bounds__(256) void motion_votes_kernel(unsigned char* __rest
     votes[id * 3 + 2] = (unsigned char)occluded;
 }
 
-bool dims_ok(int n, int H, int W) { return n > 0 && H > 0 && W > 0 && (long)n * H * W < (1L << 31); }
-
 }  // namespace
 
 // the depth ranges: one float2 (dmin, dmax) per pixel of every image
@@ -105,18 +95,10 @@ extern "C" size_t geo4d_motion_workspace(int n, int H, int W) {
 
 extern "C" int geo4d_motion_range(const float* depth, const unsigned char* valid, int n, int H, int W, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    if (!depth || !workspace || (size_t)workspace % 8) {
-        geo4d_set_error("motion_range: depth and an 8-byte aligned workspace are required");
-        return GEO4D_EINVAL;
-    }
-    if (!dims_ok(n, H, W)) {
-        geo4d_set_error("motion_range: need n, H, W > 0 and n * H * W < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (workspace_bytes < geo4d_motion_workspace(n, H, W)) {
-        geo4d_set_error("motion_range: workspace too small (geo4d_motion_workspace bytes)");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "motion_range";
+    if (!depth || !workspace || (size_t)workspace % 8) return refuse(who, "depth and an 8-byte aligned workspace are required");
+    if (!dims_ok(n, H, W)) return refuse(who, "need n, H, W > 0 and n * H * W < 2^31");
+    if (workspace_bytes < geo4d_motion_workspace(n, H, W)) return refuse(who, "workspace too small (geo4d_motion_workspace bytes)");
     const long total = (long)n * H * W;
     hipLaunchKernelGGL(motion_range_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float2*)workspace,
                        depth, valid, total, H, W);
@@ -126,26 +108,13 @@ extern "C" int geo4d_motion_range(const float* depth, const unsigned char* valid
 
 extern "C" int geo4d_motion_votes(const float* pts3d, const float* views, int n, int H, int W, int radius, float tol, float near,
                                   unsigned char* votes, const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!pts3d || !views || !votes || !workspace || (size_t)workspace % 8) {
-        geo4d_set_error("motion_votes: pts3d, views, votes and the 8-byte aligned workspace geo4d_motion_range wrote are required");
-        return GEO4D_EINVAL;
-    }
-    if (!dims_ok(n, H, W)) {
-        geo4d_set_error("motion_votes: need n, H, W > 0 and n * H * W < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (radius < 1 || radius > MAX_RADIUS) {
-        geo4d_set_error("motion_votes: need 1 <= radius <= 127 (the counts are bytes)");
-        return GEO4D_EINVAL;
-    }
-    if (!(tol > 0.f && tol < 1.f) || !(near >= 0.f)) {
-        geo4d_set_error("motion_votes: need 0 < tol < 1 and near >= 0");
-        return GEO4D_EINVAL;
-    }
-    if (workspace_bytes < geo4d_motion_workspace(n, H, W)) {
-        geo4d_set_error("motion_votes: workspace too small (geo4d_motion_workspace bytes)");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "motion_votes";
+    if (!pts3d || !views || !votes || !workspace || (size_t)workspace % 8)
+        return refuse(who, "pts3d, views, votes and the 8-byte aligned workspace geo4d_motion_range wrote are required");
+    if (!dims_ok(n, H, W)) return refuse(who, "need n, H, W > 0 and n * H * W < 2^31");
+    if (radius < 1 || radius > MAX_RADIUS) return refuse(who, "need 1 <= radius <= 127 (the counts are bytes)");
+    if (!(tol > 0.f && tol < 1.f) || !(near >= 0.f)) return refuse(who, "need 0 < tol < 1 and near >= 0");
+    if (workspace_bytes < geo4d_motion_workspace(n, H, W)) return refuse(who, "workspace too small (geo4d_motion_workspace bytes)");
     const long hw = (long)H * W, bpi = (hw + 255) / 256;                            // n * bpi <= n * H * W < 2^31
     const float lo = 1.f - tol, hi = 1.f + tol;
     hipLaunchKernelGGL(motion_votes_kernel, dim3((unsigned)(n * bpi)), dim3(256), 0, (hipStream_t)stream, votes, pts3d, views,

@@ -3,8 +3,8 @@
 // The reference shows a reconstruction in a browser (viser, WebGL); nothing of that is ported. This is the project's own renderer and
 // every rule is stated here, in include/geo4d_hip.h and, in numpy, in tests/render_restatement.py.
 //
-// splat:   one thread per (view, source image, point of that image). The point goes to camera space, is dropped when masked out,
-//          non-finite or not beyond `near`, and is projected with the project's pixel rule (pixel i sits at coordinate i). Its square
+// splat:   one thread per (view, source image, point of that image). The point goes to camera space (scene_view.h), is dropped when masked
+//          out, non-finite or not beyond `near`, and is projected with the project's pixel rule (pixel i sits at coordinate i). Its square
 //          footprint of side s (1, or from a world radius) is clipped to the image and every covered pixel gets one 64-bit atomicMin of
 //          key = float_bits(zc) << 32 | point id. Positive floats order as unsigned integers, so the minimum key is the nearest point and
 //          at equal depth the lower id: the buffer does not depend on the order the atomics arrive in, and is bitwise reproducible.
@@ -17,19 +17,14 @@
 #include <vector>
 #include "common.h"
 #include "geo4d_hip.h"
+#include "scene_view.h"                                                              // u64, the view, to_camera, dims_ok, refuse
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 EMPTY = ~0ull;
-constexpr int VIEW_FLOATS = 16;      // world-to-camera rows 0..2 (12), then fx, fy, cx, cy
+constexpr u64 EMPTY = ~0ull;         // a pixel no point has landed on
 constexpr int MAX_FOOTPRINT = 64;
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) {
-    return fabsf(a) < INFINITY && fabsf(b) < INFINITY && fabsf(c) < INFINITY;      // NaN fails the comparison
-}
 
 // first covered pixel and count along one axis: c0 = floor(u - 0.5 (s - 1) + 0.5), pixels c0 .. c0 + s - 1 clipped to [0, size).
 // Decided in float before any cast, so a far-away projection cannot overflow the int.
@@ -57,9 +52,10 @@ __global__ __launch_bounds__(256) void render_splat_kernel(u64* __restrict__ zbu
     const float X = points[id * 3], Y = points[id * 3 + 1], Z = points[id * 3 + 2];
     if (!finite3(X, Y, Z)) return;
     const float* M = views + (long)view * VIEW_FLOATS;
-    const float xc = ((M[0] * X + M[1] * Y) + M[2] * Z) + M[3];
-    const float yc = ((M[4] * X + M[5] * Y) + M[6] * Z) + M[7];
-    const float zc = ((M[8] * X + M[9] * Y) + M[10] * Z) + M[11];
+    float xc, yc, zc;
+    to_camera(M, X, Y, Z, xc, yc, zc);
+    // scene_view.h's project(), written out: through the helper this kernel compiles to other code than it had (same registers, one
+    // timed row 0.03 % over its margin, profiles/scene_shared.md), and so the lines stay here
     if (!finite3(xc, yc, zc) || zc <= near) return;
     const float fx = M[12], fy = M[13];
     const float u = fx * (xc / zc) + M[14];
@@ -116,8 +112,6 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const u64* __restri
     if (index) index[i] = id;
 }
 
-bool dims_ok(int V, int H, int W) { return V > 0 && H > 0 && W > 0 && (long)V * H * W < (1L << 31); }
-
 size_t zbuf_bytes(int V, int H, int W) { return (size_t)V * H * W * sizeof(u64); }
 
 }  // namespace
@@ -131,40 +125,21 @@ extern "C" size_t geo4d_render_workspace(int V, int H, int W, long n_entries) {
 extern "C" int geo4d_render_splat(const float* points, const unsigned char* mask, const float* radius, long N, long pts_per_image,
                                   const float* views, const int* view_src_ptr, const int* view_src, int V, int H, int W, float near,
                                   int max_size, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!points || !views || !view_src_ptr || !workspace || (size_t)workspace % 8) {
-        geo4d_set_error("render_splat: points, views, view_src_ptr and an 8-byte aligned workspace are required");
-        return GEO4D_EINVAL;
-    }
-    if (!dims_ok(V, H, W)) {
-        geo4d_set_error("render_splat: need V, H, W > 0 and V * H * W < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (N <= 0 || N >= (1L << 32) - 1 || pts_per_image <= 0 || N % pts_per_image) {
-        geo4d_set_error("render_splat: need 0 < N < 2^32 - 1 points in whole images of pts_per_image points");
-        return GEO4D_EINVAL;
-    }
-    if (!(near >= 0.f) || max_size < 1 || max_size > MAX_FOOTPRINT) {
-        geo4d_set_error("render_splat: need near >= 0 and 1 <= max_size <= 64");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "render_splat";
+    if (!points || !views || !view_src_ptr || !workspace || (size_t)workspace % 8)
+        return refuse(who, "points, views, view_src_ptr and an 8-byte aligned workspace are required");
+    if (!dims_ok(V, H, W)) return refuse(who, "need V, H, W > 0 and V * H * W < 2^31");
+    if (N <= 0 || N >= (1L << 32) - 1 || pts_per_image <= 0 || N % pts_per_image)
+        return refuse(who, "need 0 < N < 2^32 - 1 points in whole images of pts_per_image points");
+    if (!(near >= 0.f) || max_size < 1 || max_size > MAX_FOOTPRINT) return refuse(who, "need near >= 0 and 1 <= max_size <= 64");
     const long n_img = N / pts_per_image, E = view_src_ptr[V];
     bool ok = view_src_ptr[0] == 0 && E >= 0 && (E == 0 || view_src);
     for (int v = 0; ok && v < V; ++v) ok = view_src_ptr[v] <= view_src_ptr[v + 1];
     for (long k = 0; ok && k < E; ++k) ok = view_src[k] >= 0 && view_src[k] < n_img;
-    if (!ok) {
-        geo4d_set_error("render_splat: view_src_ptr must rise from 0 and every source index must name one of the N / pts_per_image images");
-        return GEO4D_EINVAL;
-    }
+    if (!ok) return refuse(who, "view_src_ptr must rise from 0 and every source index must name one of the N / pts_per_image images");
     const long bpi = (pts_per_image + 255) / 256;
-    if (E * bpi >= (1L << 31)) {
-        geo4d_set_error("render_splat: too many (view, source image) blocks for one launch; render fewer views per call");
-        return GEO4D_EINVAL;
-    }
-    const size_t need = geo4d_render_workspace(V, H, W, E);
-    if (workspace_bytes < need) {
-        geo4d_set_error("render_splat: workspace too small (geo4d_render_workspace bytes)");
-        return GEO4D_EINVAL;
-    }
+    if (E * bpi >= (1L << 31)) return refuse(who, "too many (view, source image) blocks for one launch; render fewer views per call");
+    if (workspace_bytes < geo4d_render_workspace(V, H, W, E)) return refuse(who, "workspace too small (geo4d_render_workspace bytes)");
     hipStream_t s = (hipStream_t)stream;
     u64* zbuf = (u64*)workspace;
     if (hipMemsetAsync(zbuf, 0xff, zbuf_bytes(V, H, W), s) != hipSuccess) {
@@ -193,11 +168,9 @@ extern "C" int geo4d_render_splat(const float* points, const unsigned char* mask
 }
 
 extern "C" int geo4d_render_fill(int V, int H, int W, int passes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!workspace || (size_t)workspace % 8 || !dims_ok(V, H, W) || passes < 0 || workspace_bytes < 2 * zbuf_bytes(V, H, W)) {
-        geo4d_set_error("render_fill: need an 8-byte aligned workspace of geo4d_render_workspace bytes, V, H, W > 0, V * H * W < 2^31, "
-                        "passes >= 0");
-        return GEO4D_EINVAL;
-    }
+    if (!workspace || (size_t)workspace % 8 || !dims_ok(V, H, W) || passes < 0 || workspace_bytes < 2 * zbuf_bytes(V, H, W))
+        return refuse("render_fill", "need an 8-byte aligned workspace of geo4d_render_workspace bytes, V, H, W > 0, V * H * W < 2^31, "
+                                     "passes >= 0");
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)V * H * W;
     u64 *a = (u64*)workspace, *b = a + total;
@@ -215,14 +188,11 @@ extern "C" int geo4d_render_fill(int V, int H, int W, int passes, void* workspac
 
 extern "C" int geo4d_render_resolve(const float* colors, long N, const float* background, int V, int H, int W, unsigned char* rgb,
                                     float* depth, int* index, const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!workspace || (size_t)workspace % 8 || !dims_ok(V, H, W) || workspace_bytes < zbuf_bytes(V, H, W)) {
-        geo4d_set_error("render_resolve: need the 8-byte aligned workspace geo4d_render_splat wrote, V, H, W > 0, V * H * W < 2^31");
-        return GEO4D_EINVAL;
-    }
-    if (!colors || !background || N <= 0 || N >= (1L << 31) || (!rgb && !depth && !index)) {
-        geo4d_set_error("render_resolve: need colors [N][3], a host background [3], 0 < N < 2^31 (index is int32) and at least one output");
-        return GEO4D_EINVAL;
-    }
+    const char* who = "render_resolve";
+    if (!workspace || (size_t)workspace % 8 || !dims_ok(V, H, W) || workspace_bytes < zbuf_bytes(V, H, W))
+        return refuse(who, "need the 8-byte aligned workspace geo4d_render_splat wrote, V, H, W > 0, V * H * W < 2^31");
+    if (!colors || !background || N <= 0 || N >= (1L << 31) || (!rgb && !depth && !index))
+        return refuse(who, "need colors [N][3], a host background [3], 0 < N < 2^31 (index is int32) and at least one output");
     const long total = (long)V * H * W;
     hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const u64*)workspace, colors, N, total, background[0], background[1], background[2], rgb, depth, index);

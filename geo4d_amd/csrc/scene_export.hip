@@ -17,6 +17,7 @@
 #include "common.h"
 #include "compact.h"
 #include "geo4d_hip.h"
+#include "scene_view.h"                                                              // dims_ok
 
 #pragma clang fp contract(off)
 
@@ -141,8 +142,6 @@ int run_compaction(const Op& op, long n, long* count, void* workspace, hipStream
 }
 
 long n_faces_max(int n, int H, int W) { return 4L * n * (H - 1) * (W - 1); }
-
-bool dims_ok(int n, int H, int W) { return n > 0 && H > 0 && W > 0 && (long)n * H * W < (1L << 31); }
 
 }  // namespace
 

@@ -10,15 +10,15 @@
 //   every weight is 1), voxel v > 0, truncation T in 1..8 voxels with trunc = (float)T * v, near >= 0, min_weight > 0.
 // mark:      pixel (i, p) takes part iff it is valid, its point P and depth are finite and depth > near. d = P - C_i,
 //            s = (v * 0.5f) / depth; for k = -2T .. 2T the sample is P_a + ((float)k * s) * d_a, a step of v / 2 in camera z, and its
-//            cell floorf(sample_a / v). Keys are fuse.hip's: (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20) with |c| < 2^20, all
-//            ones = empty; a sample whose cell is out of range is counted in `dropped`. One thread per pixel, blocks image-uniform (C_i
-//            through scalar loads). The table holds keys only: open addressing, linear probing from a 64-bit mix of the key, a relaxed
-//            read, a 64-bit CAS only on an empty slot, forward probing, no lane waits for another. A sample that has probed `capacity`
-//            slots without a home is counted in `overflow` and gives up; once the count is not zero the table is known to be full and
-//            every lane that looks (each 256 probes) gives up as well, so a full table ends in the host's refusal and not in
-//            samples x capacity probes. A sample in the cell of the lane's previous sample is already there and does not probe.
-// compact:   fuse.hip's: 16 slots per thread, one atomicAdd per workgroup; keys only, no slots (nothing hangs on a slot here). The caller
-//            sorts the keys: K[0..M).
+//            cell floorf(sample_a / v). Keys are voxel_table.h's: (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20) with |c| < 2^20,
+//            all ones = empty; a sample whose cell is out of range is counted in `dropped`. One thread per pixel, blocks image-uniform
+//            (C_i through scalar loads). The table (voxel_table.h) holds keys only: open addressing, linear probing from a 64-bit mix of
+//            the key, a relaxed read, a 64-bit CAS only on an empty slot, forward probing, no lane waits for another. A sample that has
+//            probed `capacity` slots without a home is counted in `overflow` and gives up; once the count is not zero the table is known
+//            to be full and every lane that looks (each 256 probes) gives up as well, so a full table ends in the host's refusal and not
+//            in samples x capacity probes. A sample in the cell of the lane's previous sample is already there and does not probe.
+// compact:   voxel_table.h's: 16 slots per thread, one atomicAdd per workgroup; keys only, no slots (nothing hangs on a slot here). The
+//            caller sorts the keys: K[0..M).
 // integrate: one thread per voxel m, centre X_a = ((float)c_a + 0.5f) * v. For j = 0 .. n-1 in that order (the sums are a function of
 //            the inputs alone; j is uniform, so the view floats are scalar loads): xc = ((r00 X + r01 Y) + r02 Z) + t0, likewise yc,
 //            zc; skip unless all are finite and zc > near; u = fx (xc / zc) + cx, likewise v; column = floorf(u + 0.5f), row =
@@ -34,29 +34,13 @@
 #include <cmath>
 #include "common.h"
 #include "geo4d_hip.h"
-#include "tsdf_field.h"                                                              // u64, centre_of, live, find_key, voxel_ok, refuse
+#include "tsdf_field.h"                                                              // centre_of, live, find_key; the view and the table
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr u64 EMPTY = ~0ull;
-constexpr int VIEW_FLOATS = 16;
 constexpr int MAX_TRUNC = 8;
-constexpr float CELL_LIMIT = 1048576.f;   // 2^20
-constexpr int GIVE_UP_EVERY = 256;        // probes between two looks at the overflow count
-
-__device__ __forceinline__ bool finite1(float a) { return fabsf(a) < INFINITY; }                       // NaN fails the comparison
-__device__ __forceinline__ bool finite3(float a, float b, float c) { return finite1(a) && finite1(b) && finite1(c); }
-
-__device__ __forceinline__ u64 mix64(u64 h) {
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
-}
 
 __global__ __launch_bounds__(256) void tsdf_mark_kernel(u64* __restrict__ keys, u64* __restrict__ counters, const float* __restrict__ pts3d,
                                                         const float* __restrict__ depth, const unsigned char* __restrict__ valid,
@@ -78,70 +62,16 @@ __global__ __launch_bounds__(256) void tsdf_mark_kernel(u64* __restrict__ keys, 
         const float ks = (float)k * s;
         const float sx = X + ks * dx, sy = Y + ks * dy, sz = Z + ks * dz;
         const float cx = floorf(sx / v), cy = floorf(sy / v), cz = floorf(sz / v);
-        if (!(fabsf(cx) < CELL_LIMIT && fabsf(cy) < CELL_LIMIT && fabsf(cz) < CELL_LIMIT)) {
+        if (!cell_ok(cx, cy, cz)) {
             ++dropped;
             continue;
         }
-        const u64 key = ((u64)((int)cx + (1 << 20)) << 42) | ((u64)((int)cy + (1 << 20)) << 21) | (u64)((int)cz + (1 << 20));
+        const u64 key = key_of(cx, cy, cz);
         if (key == last) continue;                                                   // this lane has put it there already
-        u64 at = mix64(key) & (capacity - 1);
-        bool home = false;
-        for (u64 step = 0; step < capacity; ++step) {
-            u64 seen = __atomic_load_n(keys + at, __ATOMIC_RELAXED);
-            if (seen == EMPTY) {
-                seen = atomicCAS(keys + at, EMPTY, key);
-                if (seen == EMPTY) seen = key;
-            }
-            if (seen == key) {
-                home = true;
-                break;
-            }
-            // keys never leave: once one sample has seen `capacity` full slots the table stays full, and nobody needs to see it again
-            if ((step & (GIVE_UP_EVERY - 1)) == GIVE_UP_EVERY - 1 && __atomic_load_n(counters + 1, __ATOMIC_RELAXED) != 0) break;
-            at = (at + 1) & (capacity - 1);
-        }
-        if (home) last = key;
+        if (claim_slot(keys, capacity, key, counters + 1) != EMPTY) last = key;
         else atomicAdd(counters + 1, 1ull);                                          // at once: the others look at it
     }
     if (dropped) atomicAdd(counters, (u64)dropped);
-}
-
-constexpr int COMPACT_ROUNDS = 16;                                                   // slots per thread: one atomicAdd per 4 096 slots
-
-__global__ __launch_bounds__(256) void tsdf_compact_kernel(const u64* __restrict__ keys, u64 capacity, long* __restrict__ key_out,
-                                                           u64 max_keys, u64* __restrict__ count) {
-    __shared__ unsigned wave_sum[4];
-    __shared__ u64 base_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 s0 = (u64)blockIdx.x * (256 * COMPACT_ROUNDS) + threadIdx.x;           // round r looks at slot s0 + 256 r
-    u64 key[COMPACT_ROUNDS];
-    unsigned mine = 0;
-#pragma unroll
-    for (int r = 0; r < COMPACT_ROUNDS; ++r) {
-        const u64 s = s0 + 256 * r;
-        key[r] = s < capacity ? keys[s] : EMPTY;
-        mine += key[r] != EMPTY;
-    }
-    unsigned incl = mine;                                                            // inclusive scan inside the wave
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-        base_s = total ? atomicAdd(count, (u64)total) : 0;
-    }
-    __syncthreads();
-    u64 pos = base_s + incl - mine;
-    for (int k = 0; k < wave; ++k) pos += wave_sum[k];
-#pragma unroll
-    for (int r = 0; r < COMPACT_ROUNDS; ++r) {
-        if (key[r] == EMPTY) continue;
-        if (pos < max_keys) key_out[pos] = (long)key[r];                             // the count still says how many there were
-        ++pos;
-    }
 }
 
 __device__ __forceinline__ unsigned colour_byte(float c, float wc) {
@@ -165,14 +95,10 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const long* __restr
     float D = 0.f, Wt = 0.f, Wc = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
     for (int j = 0; j < n; ++j) {
         const float* V = views + (long)j * VIEW_FLOATS;
-        const float xc = ((V[0] * X + V[1] * Y) + V[2] * Z) + V[3];
-        const float yc = ((V[4] * X + V[5] * Y) + V[6] * Z) + V[7];
-        const float zc = ((V[8] * X + V[9] * Y) + V[10] * Z) + V[11];
-        if (!finite3(xc, yc, zc) || !(zc > near)) continue;
-        const float u = V[12] * (xc / zc) + V[14];
-        const float w_ = V[13] * (yc / zc) + V[15];
-        const float col = floorf(u + 0.5f), row = floorf(w_ + 0.5f);
-        if (!(col >= 0.f && col < fW && row >= 0.f && row < fH)) continue;         // outside, or NaN / Inf
+        float xc, yc, zc, u, w_, col, row;
+        to_camera(V, X, Y, Z, xc, yc, zc);
+        if (!project(V, xc, yc, zc, near, u, w_)) continue;
+        if (!pixel_of(u, w_, fW, fH, col, row)) continue;
         const long q = (long)j * pts_per_image + (long)(int)row * W + (int)col;
         if (valid && !valid[q]) continue;
         const float dj = depth[q];
@@ -208,7 +134,7 @@ __device__ __forceinline__ int crossings(const long* __restrict__ K, long M, con
     const u64 key = (u64)K[m];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const long m2 = find_key(K, m + 1, M, key + (1ull << (42 - 21 * a)));
+        const long m2 = find_key(K, m + 1, M, key + axis_step(a));
         if (m2 < 0) continue;
         const float f2 = f[m2];
         if (!live(f2, wt[m2], min_weight) || (fm >= 0.f) == (f2 >= 0.f)) continue;
@@ -255,9 +181,11 @@ __global__ __launch_bounds__(256) void tsdf_write_kernel(const long* __restrict_
     }
 }
 
-bool dims_ok(int n, int H, int W) { return n > 0 && H > 0 && W > 0 && (long)n * H * W < (1L << 31); }
-bool capacity_ok(long capacity) { return capacity >= 1 && capacity <= (1L << 32) && (capacity & (capacity - 1)) == 0; }
 bool trunc_ok(int T) { return T >= 1 && T <= MAX_TRUNC; }
+
+int tsdf_table_ok(const char* who, const void* workspace, size_t workspace_bytes, long capacity) {
+    return table_ok(who, workspace, workspace_bytes, capacity, geo4d_tsdf_workspace(capacity), "workspace too small (geo4d_tsdf_workspace bytes)");
+}
 
 }  // namespace
 
@@ -273,9 +201,7 @@ extern "C" int geo4d_tsdf_mark(const float* pts3d, const float* depth, const uns
     if (!voxel_ok(voxel)) return refuse(who, "voxel must be finite and > 0");
     if (!trunc_ok(trunc)) return refuse(who, "the truncation must be 1 .. 8 voxels");
     if (!(near >= 0.f)) return refuse(who, "need near >= 0");
-    if (!workspace || (size_t)workspace % 8) return refuse(who, "an 8-byte aligned workspace is required");
-    if (!capacity_ok(capacity)) return refuse(who, "capacity must be a power of two, 1 <= capacity <= 2^32");
-    if (workspace_bytes < geo4d_tsdf_workspace(capacity)) return refuse(who, "workspace too small (geo4d_tsdf_workspace bytes)");
+    if (int rc = tsdf_table_ok(who, workspace, workspace_bytes, capacity)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(workspace, 0xff, (size_t)capacity * 8, s) != hipSuccess || hipMemsetAsync(counters, 0, 2 * sizeof(long), s) != hipSuccess) {
         geo4d_set_error("tsdf_mark: hipMemsetAsync failed");
@@ -292,18 +218,8 @@ extern "C" int geo4d_tsdf_compact(long capacity, long* keys_out, long max_keys, 
                                   void* stream) {
     const char* who = "tsdf_compact";
     if (!keys_out || !count || max_keys < 0) return refuse(who, "keys_out [max_keys >= 0] and count are required");
-    if (!workspace || (size_t)workspace % 8) return refuse(who, "an 8-byte aligned workspace is required");
-    if (!capacity_ok(capacity)) return refuse(who, "capacity must be a power of two, 1 <= capacity <= 2^32");
-    if (workspace_bytes < geo4d_tsdf_workspace(capacity)) return refuse(who, "workspace too small (geo4d_tsdf_workspace bytes)");
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(count, 0, sizeof(long), s) != hipSuccess) {
-        geo4d_set_error("tsdf_compact: hipMemsetAsync failed");
-        return GEO4D_EIO;
-    }
-    hipLaunchKernelGGL(tsdf_compact_kernel, dim3((unsigned)((capacity + 256 * COMPACT_ROUNDS - 1) / (256 * COMPACT_ROUNDS))), dim3(256), 0, s,
-                       (const u64*)workspace, (u64)capacity, keys_out, (u64)max_keys, (u64*)count);
-    GEO4D_CHECK_LAUNCH();
-    return GEO4D_OK;
+    if (int rc = tsdf_table_ok(who, workspace, workspace_bytes, capacity)) return rc;
+    return table_compact<false>(who, workspace, capacity, keys_out, nullptr, max_keys, count, (hipStream_t)stream);
 }
 
 extern "C" int geo4d_tsdf_integrate(const long* keys, long M, const float* depth, const unsigned char* valid, const float* weight,

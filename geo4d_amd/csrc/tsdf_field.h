@@ -1,23 +1,19 @@
 // geo4d_amd/csrc/tsdf_field.h — what the readers of a TSDF field (sorted keys K[0..M), f, Wt) share: tsdf.hip's surface points and
-// tsdf_mesh.hip's surface nets. Keys are (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20) with |c| < 2^20, so a field of a real cell
-// holds 1 .. 2^21 - 1 and unsigned key order is (cx, cy, cz) order.
+// tsdf_mesh.hip's surface nets. Keys are voxel_table.h's, so unsigned key order is (cx, cy, cz) order.
 #pragma once
-#include <cmath>
-#include <cstdio>
-#include "common.h"
+#include "voxel_table.h"                                                             // u64, cell_of, axis_step, voxel_ok, refuse
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
-
 // the centre of the voxel with this key
 __device__ __forceinline__ void centre_of(u64 key, float v, float& X, float& Y, float& Z) {
-    const int cx = (int)(key >> 42) - (1 << 20), cy = (int)((key >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(key & 0x1fffffu) - (1 << 20);
-    X = ((float)cx + 0.5f) * v;
-    Y = ((float)cy + 0.5f) * v;
-    Z = ((float)cz + 0.5f) * v;
+    int c[3];
+    cell_of(key, c);
+    X = ((float)c[0] + 0.5f) * v;
+    Y = ((float)c[1] + 0.5f) * v;
+    Z = ((float)c[2] + 0.5f) * v;
 }
 
 __device__ __forceinline__ bool live(float f, float wt, float min_weight) { return wt >= min_weight && fabsf(f) < 1.f; }
@@ -31,15 +27,6 @@ __device__ __forceinline__ long find_key(const long* __restrict__ K, long lo, lo
         else hi = mid;
     }
     return lo < M && (u64)K[lo] == target ? lo : -1;
-}
-
-bool voxel_ok(float voxel) { return voxel > 0.f && voxel < INFINITY; }
-
-int refuse(const char* who, const char* what) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    geo4d_set_error(msg);
-    return GEO4D_EINVAL;
 }
 
 }  // namespace

@@ -6,9 +6,9 @@
 // as in tsdf.hip; only + - * / are used. No table of cases, no atomics: every output row has one writer and its place is a function of
 // the inputs alone.
 //
-// Inputs: exactly what geo4d_tsdf_integrate leaves: K int64 [M] sorted keys ((c + 2^20) in three 21-bit fields, tsdf_field.h), f fp32
+// Inputs: exactly what geo4d_tsdf_integrate leaves: K int64 [M] sorted keys ((c + 2^20) in three 21-bit fields, voxel_table.h), f fp32
 //   [M], Wt fp32 [M], rgba u8 [M][4] (NULL: no colours), plus the voxel v and min_weight.
-// live, s, E: live is tsdf.hip's live(f, Wt, min_weight); s(m) = f[m] >= 0; the step along axis a is E_a = (1 << 42, 1 << 21, 1)[a]. A
+// live, s, E: live is tsdf_field.h's live(f, Wt, min_weight); s(m) = f[m] >= 0; the step along axis a is E_a = (1 << 42, 1 << 21, 1)[a]. A
 //   key field holds 1 .. 2^21 - 1 for a real cell: + E_a out of a full field carries into a field of value 0 and - E_a from 1 gives 0,
 //   and no cell has either key, so no edge-of-grid test is needed in either direction.
 // cell:   cell m is the cube whose eight corners are the voxel centres with keys K[m] + ox E_0 + oy E_1 + oz E_2, o in {0, 1}^3, corner
@@ -40,8 +40,6 @@
 
 namespace {
 
-__device__ __forceinline__ u64 step_of(int a) { return 1ull << (42 - 21 * a); }
-
 // find_key in K[lo..M) after a look at row lo, and in K[0..hi) after a look at row hi - 1: z is the lowest key field, so the + z
 // neighbour of a voxel is the next row and its - z neighbour the row before, if they exist at all; half the searches end there
 __device__ __forceinline__ long find_from(const long* __restrict__ K, long lo, long M, u64 target) {
@@ -59,7 +57,7 @@ __device__ __forceinline__ bool corners_of(const long* __restrict__ K, long M, l
     c[0] = m;
 #pragma unroll
     for (int i = 1; i < 8; ++i) {
-        c[i] = find_from(K, c[i - 1] + 1, M, key + (u64)(i >> 2) * step_of(0) + (u64)((i >> 1) & 1) * step_of(1) + (u64)(i & 1));
+        c[i] = find_from(K, c[i - 1] + 1, M, key + (u64)(i >> 2) * axis_step(0) + (u64)((i >> 1) & 1) * axis_step(1) + (u64)(i & 1));
         if (c[i] < 0) return false;
     }
     return true;
@@ -96,7 +94,7 @@ __device__ __forceinline__ int quads_of(const long* __restrict__ K, const unsign
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         if (!(cell & (2u << a))) continue;                                           // m' is a corner of the complete cell m: it is live
-        const u64 eb = step_of((a + 1) % 3), ec = step_of((a + 2) % 3);
+        const u64 eb = axis_step((a + 1) % 3), ec = axis_step((a + 2) % 3);
         const long r1 = find_below(K, m, key - eb);
         if (r1 < 0 || !complete[r1]) continue;
         const long r3 = find_below(K, m, key - ec);

@@ -19,26 +19,10 @@ import math
 import torch
 
 from . import _lib, ops
+from .render import _rgba
 
 REDUCE = tuple(ops.FUSE_REDUCE)
 CELL_LIMIT = 1 << 20
-
-
-def _rgba(colors, N, device):
-    """u8 [N, 4] of `colors`: a u8 rgba as it is, or float [N, 3] in [0, 1] quantised as ops.scene_points does (clip(c * 255 + 0.5,
-    0, 255) truncated, in fp32) with alpha 255."""
-    if colors is None:
-        return None
-    if not colors.is_cuda:
-        raise _lib.Geo4DNativeError(f"fuse_points: `colors` lives on {colors.device}; the fusion runs only on a HIP device")
-    if colors.dtype == torch.uint8:
-        if tuple(colors.shape) != (N, 4):
-            raise ValueError(f"fuse_points: uint8 colours must be rgba [N, 4] = {(N, 4)}, got {tuple(colors.shape)}")
-        return colors.contiguous()
-    if tuple(colors.shape) != (N, 3):
-        raise ValueError(f"fuse_points: float colours must be [N, 3] = {(N, 3)}, got {tuple(colors.shape)}")
-    rgb = ((colors.float() * 255.0) + 0.5).clamp(0.0, 255.0).to(torch.uint8)
-    return torch.cat([rgb, torch.full((N, 1), 255, dtype=torch.uint8, device=device)], 1).contiguous()
 
 
 def check_fuse_args(voxel, reduce, min_count):
@@ -77,7 +61,8 @@ def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="m
     for t, what in ((weight, "weight"), (mask, "mask")):
         if t is not None and tuple(t.shape) != (N,):
             raise ValueError(f"fuse_points: {what} must be [N] = {(N,)}, got {tuple(t.shape)}")
-    pts, rgba, w, count, dropped = ops.fuse_points(points.detach().float().contiguous(), _rgba(colors, N, dev),
+    rgba = _rgba(colors, (N,), dev, "fuse_points", "colors", "the fusion", "[N, {}] = ")
+    pts, rgba, w, count, dropped = ops.fuse_points(points.detach().float().contiguous(), rgba,
                                                    None if weight is None else weight.detach().float().contiguous(),
                                                    None if mask is None else mask.to(dev), voxel=v, reduce=reduce, capacity=capacity)
     if dropped:

@@ -1135,15 +1135,27 @@ def depth_metrics(pred, gt, st, *, max_depth=None, custom_mask=None, pre_clip_mi
     return sums, err, al
 
 
+def _want(t, what, dtype, shape):
+    """`t`, which must be on the HIP device (_dev), of `dtype`, contiguous and of `shape`, where None stands for any extent. The
+    AssertionError says what was found."""
+    _dev(t, what)
+    assert t.dtype == dtype and t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)) and t.is_contiguous(), \
+        (what, t.dtype, tuple(t.shape))
+    return t
+
+
+def _no_rows(dev, rgba, *more):
+    """The result of an op that found nothing: (points fp32 [0, 3], rgba uint8 [0, 4] or None as `rgba` is, weight fp32 [0], *more)."""
+    return (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+            torch.empty(0, device=dev, dtype=torch.float32), *more)
+
+
 def scene_clean(conf, pts3d, depth, mats, tol=0.001, bad_conf=0.0):
     """clean_pointcloud (base_opt_group.py:630-665) in place on conf fp32 [n, H, W]: pts3d [n, H, W, 3] world points, depth [n, H, W],
     mats [n, 21] = rows 0..2 of each world-to-camera matrix then its intrinsics, row-major. Returns conf."""
     lib = _lib.load()
-    for t, what in ((conf, "conf"), (pts3d, "pts3d"), (depth, "depth"), (mats, "mats")):
-        _dev(t, what)
-        assert t.dtype == torch.float32 and t.is_contiguous(), (what, t.dtype, t.shape)
-    n, H, W = conf.shape
-    assert pts3d.shape == (n, H, W, 3) and depth.shape == (n, H, W) and mats.shape == (n, 21), (pts3d.shape, depth.shape, mats.shape)
+    n, H, W = _want(conf, "conf", torch.float32, (None, None, None)).shape
+    _want(pts3d, "pts3d", torch.float32, (n, H, W, 3)), _want(depth, "depth", torch.float32, (n, H, W)), _want(mats, "mats", torch.float32, (n, 21))
     _lib.check(lib.geo4d_scene_clean(conf.data_ptr(), pts3d.data_ptr(), depth.data_ptr(), mats.data_ptr(), n, H, W, float(tol), float(bad_conf),
                                      _stream()), "geo4d_scene_clean")
     return conf
@@ -1160,12 +1172,9 @@ def scene_points(pts3d, rgb=None, mask=None):
     """(pts [n H W, 3] fp32, rgba [n H W, 4] uint8 or None, count device int64 [1]): pts3d[mask] and the matching colours of rgb
     [n, H, W, 3] in [0, 1], image-major raster order (= torch boolean indexing); the first `count` rows are written. mask None = all."""
     lib = _lib.load()
-    _dev(pts3d, "pts3d")
-    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous()
-    n, H, W, _ = pts3d.shape
+    n, H, W, _ = _want(pts3d, "pts3d", torch.float32, (None, None, None, 3)).shape
     if rgb is not None:
-        _dev(rgb, "rgb")
-        assert rgb.dtype == torch.float32 and rgb.shape == pts3d.shape and rgb.is_contiguous(), (rgb.dtype, rgb.shape)
+        _want(rgb, "rgb", torch.float32, (n, H, W, 3))
     m = _scene_mask(mask, (n, H, W), pts3d.device)
     pts = torch.empty((n * H * W, 3), device=pts3d.device, dtype=torch.float32)
     rgba = None if rgb is None else torch.empty((n * H * W, 4), device=pts3d.device, dtype=torch.uint8)
@@ -1209,15 +1218,13 @@ def render_splat(points, views, view_src_ptr, view_src, size, ws, mask=None, rad
     consecutive points (None: all N are one image). mask [N] bool, radius [N] fp32 world radii (None: one pixel per point)."""
     lib = _lib.load()
     H, W = size
-    _dev(points, "points"), _dev(views, "views"), _dev(ws, "ws")
-    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 and points.is_contiguous(), (points.dtype, points.shape)
-    assert views.dtype == torch.float32 and views.dim() == 2 and views.shape[1] == 16 and views.is_contiguous(), (views.dtype, views.shape)
-    N, V = points.shape[0], views.shape[0]
+    _dev(ws, "ws")
+    N, V = _want(points, "points", torch.float32, (None, 3)).shape[0], _want(views, "views", torch.float32, (None, 16)).shape[0]
     if mask is not None:
         assert tuple(_dev(mask, "mask").shape) == (N,), mask.shape
         mask = mask.to(torch.bool).contiguous()
     if radius is not None:
-        assert tuple(_dev(radius, "radius").shape) == (N,) and radius.dtype == torch.float32 and radius.is_contiguous(), (radius.dtype, radius.shape)
+        _want(radius, "radius", torch.float32, (N,))
     assert len(view_src_ptr) == V + 1 and len(view_src) == view_src_ptr[-1], (len(view_src_ptr), len(view_src), V)
     ptr = (C.c_int * (V + 1))(*view_src_ptr)
     src = (C.c_int * max(len(view_src), 1))(*view_src)
@@ -1239,8 +1246,7 @@ def render_resolve(ws, colors, V, size, background=(1.0, 1.0, 1.0)):
     (colors fp32 [N, 3] in [0, 1], scene_points' rounding), camera depth and id; background / 0 / -1 where no point landed."""
     lib = _lib.load()
     H, W = size
-    _dev(ws, "ws"), _dev(colors, "colors")
-    assert colors.dtype == torch.float32 and colors.dim() == 2 and colors.shape[1] == 3 and colors.is_contiguous(), (colors.dtype, colors.shape)
+    _dev(ws, "ws"), _want(colors, "colors", torch.float32, (None, 3))
     rgb = torch.empty((V, H, W, 3), device=ws.device, dtype=torch.uint8)
     depth = torch.empty((V, H, W), device=ws.device, dtype=torch.float32)
     index = torch.empty((V, H, W), device=ws.device, dtype=torch.int32)
@@ -1254,9 +1260,7 @@ def motion_range(depth, valid=None):
     """The motion rule's workspace for depth fp32 [n, H, W] and valid bool [n, H, W] (None: every pixel): per pixel the (dmin, dmax) of
     the valid depths in its 3 x 3 neighbourhood, dmin = NaN on invalid pixels; fp32 [n, H, W, 2]."""
     lib = _lib.load()
-    _dev(depth, "depth")
-    assert depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous(), (depth.dtype, depth.shape)
-    n, H, W = depth.shape
+    n, H, W = _want(depth, "depth", torch.float32, (None, None, None)).shape
     if valid is not None:
         _dev(valid, "valid")
     valid = _scene_mask(valid, (n, H, W), depth.device)
@@ -1273,15 +1277,12 @@ def motion_votes(pts3d, depth, valid, views, radius=8, tol=0.05, near=1e-3, ws=N
     include/geo4d_hip.h): pts3d fp32 [n, H, W, 3] world points, depth fp32 [n, H, W], valid bool [n, H, W] or None, views fp32 [n, 16]
     (world-to-camera rows 0..2, then fx, fy, cx, cy). `ws`: a motion_range result to reuse instead of computing the depth ranges."""
     lib = _lib.load()
-    _dev(pts3d, "pts3d"), _dev(views, "views")
-    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous(), (pts3d.dtype, pts3d.shape)
-    n, H, W, _ = pts3d.shape
-    assert views.dtype == torch.float32 and tuple(views.shape) == (n, 16) and views.is_contiguous(), (views.dtype, views.shape)
+    n, H, W, _ = _want(pts3d, "pts3d", torch.float32, (None, None, None, 3)).shape
+    _want(views, "views", torch.float32, (n, 16))
     if ws is None:
         assert tuple(depth.shape) == (n, H, W), (depth.shape, pts3d.shape)
         ws = motion_range(depth, valid)
-    _dev(ws, "ws")
-    assert ws.dtype == torch.float32 and tuple(ws.shape) == (n, H, W, 2) and ws.is_contiguous(), (ws.dtype, ws.shape)
+    _want(ws, "ws", torch.float32, (n, H, W, 2))
     votes = torch.empty((n, H, W, 3), device=pts3d.device, dtype=torch.uint8)
     _lib.check(lib.geo4d_motion_votes(pts3d.data_ptr(), views.data_ptr(), n, H, W, int(radius), float(tol), float(near), votes.data_ptr(),
                                       ws.data_ptr(), ws.numel() * 4, _stream()), "geo4d_motion_votes")
@@ -1308,13 +1309,11 @@ def fuse_insert(points, rgba=None, weight=None, mask=None, *, voxel, reduce="mea
     """Insert points fp32 [N, 3] into a fresh voxel table (the rule of include/geo4d_hip.h): rgba uint8 [N, 4], weight fp32 [N] and mask
     bool [N] are optional. Returns the FuseTable for fuse_compact / fuse_finalize."""
     lib = _lib.load()
-    _dev(points, "points")
-    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 and points.is_contiguous(), (points.dtype, points.shape)
-    N = points.shape[0]
+    N = _want(points, "points", torch.float32, (None, 3)).shape[0]
     if rgba is not None:
-        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (N, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+        _want(rgba, "rgba", torch.uint8, (N, 4))
     if weight is not None:
-        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (N,) and weight.is_contiguous(), (weight.dtype, weight.shape)
+        _want(weight, "weight", torch.float32, (N,))
     if mask is not None:
         assert tuple(_dev(mask, "mask").shape) == (N,), mask.shape
         mask = mask.to(torch.bool).contiguous()
@@ -1345,9 +1344,7 @@ def fuse_compact(table):
 
 def fuse_finalize(table, order):
     """(points fp32 [M, 3], rgba uint8 [M, 4] or None, weight fp32 [M], count int32 [M]): the voxels in the slots `order` int64 [M]."""
-    _dev(order, "order")
-    assert order.dtype == torch.int64 and order.dim() == 1 and order.is_contiguous(), (order.dtype, order.shape)
-    M, dev = order.shape[0], order.device
+    M, dev = _want(order, "order", torch.int64, (None,)).shape[0], order.device
     pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
     rgba = None if table.rgba is None else torch.empty((M, 4), device=dev, dtype=torch.uint8)
     weight = torch.empty(M, device=dev, dtype=torch.float32)
@@ -1386,20 +1383,22 @@ def tsdf_capacity(taking_part):
     return 1 << max(4 * int(taking_part) - 1, 0).bit_length()
 
 
-def _tsdf_maps(pts3d, depth, valid, rgba, weight):
-    """The checked per-pixel inputs of the tsdf ops: (n, H, W, valid as bool or None)."""
-    _dev(pts3d, "pts3d"), _dev(depth, "depth")
-    assert pts3d.dtype == torch.float32 and pts3d.dim() == 4 and pts3d.shape[-1] == 3 and pts3d.is_contiguous(), (pts3d.dtype, pts3d.shape)
-    n, H, W, _ = pts3d.shape
-    assert depth.dtype == torch.float32 and tuple(depth.shape) == (n, H, W) and depth.is_contiguous(), (depth.dtype, depth.shape)
+def _tsdf_images(depth, valid, rgba, weight):
+    """The checked per-pixel inputs every tsdf op takes: (n, H, W, valid as bool or None) of depth fp32 [n, H, W]."""
+    n, H, W = _want(depth, "depth", torch.float32, (None, None, None)).shape
     if valid is not None:
         _dev(valid, "valid")
     if rgba is not None:
-        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (n, H, W, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
+        _want(rgba, "rgba", torch.uint8, (n, H, W, 4))
     if weight is not None:
-        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (n, H, W) and weight.is_contiguous(), \
-            (weight.dtype, weight.shape)
-    return n, H, W, _scene_mask(valid, (n, H, W), pts3d.device)
+        _want(weight, "weight", torch.float32, (n, H, W))
+    return n, H, W, _scene_mask(valid, (n, H, W), depth.device)
+
+
+def _tsdf_maps(pts3d, depth, valid, rgba, weight):
+    """_tsdf_images, with the point maps pts3d fp32 [n, H, W, 3] checked first."""
+    _want(depth, "depth", torch.float32, _want(pts3d, "pts3d", torch.float32, (None, None, None, 3)).shape[:3])
+    return _tsdf_images(depth, valid, rgba, weight)
 
 
 def tsdf_mark(pts3d, depth, valid, centres, *, voxel, trunc=4, near=1e-3, capacity):
@@ -1407,7 +1406,7 @@ def tsdf_mark(pts3d, depth, valid, centres, *, voxel, trunc=4, near=1e-3, capaci
     fresh table of `capacity` keys: (table int64 [capacity], counters device int64 [2] = dropped, overflow)."""
     lib = _lib.load()
     n, H, W, valid = _tsdf_maps(pts3d, depth, valid, None, None)
-    assert _dev(centres, "centres").dtype == torch.float32 and tuple(centres.shape) == (n, 3) and centres.is_contiguous(), (centres.dtype, centres.shape)
+    _want(centres, "centres", torch.float32, (n, 3))
     need = lib.geo4d_tsdf_workspace(int(capacity))
     if need == 0:
         raise _lib.Geo4DNativeError(f"geo4d_tsdf_workspace: capacity must be a power of two in 1 .. 2^32, got {capacity}")
@@ -1421,9 +1420,8 @@ def tsdf_mark(pts3d, depth, valid, centres, *, voxel, trunc=4, near=1e-3, capaci
 def tsdf_compact(table, max_keys=None):
     """(keys int64 [max_keys], count device int64 [1]) of a tsdf_mark table: the marked keys in arrival order; the first `count` rows
     are written (max_keys None: room for a full table)."""
-    _dev(table, "table")
-    capacity = table.numel()
-    assert table.dtype == torch.int64 and table.dim() == 1 and capacity >= 1 and table.is_contiguous(), (table.dtype, table.shape)
+    capacity = _want(table, "table", torch.int64, (None,)).numel()
+    assert capacity >= 1, (table.dtype, table.shape)
     max_keys = capacity if max_keys is None else max(int(max_keys), 1)
     keys = torch.empty(max_keys, device=table.device, dtype=torch.int64)
     count = torch.empty(1, device=table.device, dtype=torch.int64)
@@ -1432,29 +1430,22 @@ def tsdf_compact(table, max_keys=None):
     return keys, count
 
 
-def _tsdf_keys(keys):
-    _dev(keys, "keys")
-    assert keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous(), (keys.dtype, keys.shape)
-    return keys.shape[0]
+def _tsdf_voxels(keys, f, wt, rgba):
+    """M of a field as tsdf_integrate leaves it: keys int64 [M], f and wt fp32 [M], rgba uint8 [M, 4] or None."""
+    M = _want(keys, "keys", torch.int64, (None,)).shape[0]
+    _want(f, "f", torch.float32, (M,)), _want(wt, "wt", torch.float32, (M,))
+    if rgba is not None:
+        _want(rgba, "rgba", torch.uint8, (M, 4))
+    return M
 
 
 def tsdf_integrate(keys, depth, valid, views, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3):
     """(f fp32 [M], Wt fp32 [M], rgba uint8 [M, 4] or None) of the voxels `keys` int64 [M]: the truncated signed distance averaged over
     the images in the order 0 .. n-1, its weight and the averaged colour (the rule of include/geo4d_hip.h)."""
     lib = _lib.load()
-    M, dev = _tsdf_keys(keys), keys.device
-    _dev(depth, "depth"), _dev(views, "views")
-    assert depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous(), (depth.dtype, depth.shape)
-    n, H, W = depth.shape
-    assert views.dtype == torch.float32 and tuple(views.shape) == (n, 16) and views.is_contiguous(), (views.dtype, views.shape)
-    if valid is not None:
-        _dev(valid, "valid")
-    valid = _scene_mask(valid, (n, H, W), dev)
-    if rgba is not None:
-        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (n, H, W, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
-    if weight is not None:
-        assert _dev(weight, "weight").dtype == torch.float32 and tuple(weight.shape) == (n, H, W) and weight.is_contiguous(), \
-            (weight.dtype, weight.shape)
+    M, dev = _want(keys, "keys", torch.int64, (None,)).shape[0], keys.device
+    n, H, W, valid = _tsdf_images(depth, valid, rgba, weight)
+    _want(views, "views", torch.float32, (n, 16))
     f = torch.empty(M, device=dev, dtype=torch.float32)
     wt = torch.empty(M, device=dev, dtype=torch.float32)
     col = None if rgba is None else torch.empty((M, 4), device=dev, dtype=torch.uint8)
@@ -1471,22 +1462,16 @@ def tsdf_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
     neighbours along an axis, in (voxel, axis) order. keys int64 [M] sorted, f / wt / rgba as tsdf_integrate returns them. A count
     launch, torch.cumsum, a write launch; reads P back (one synchronisation)."""
     lib = _lib.load()
-    M, dev = _tsdf_keys(keys), keys.device
-    for t, what in ((f, "f"), (wt, "wt")):
-        assert _dev(t, what).dtype == torch.float32 and tuple(t.shape) == (M,) and t.is_contiguous(), (what, t.dtype, t.shape)
-    if rgba is not None:
-        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (M, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
-    empty = lambda: (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
-                     torch.empty(0, device=dev, dtype=torch.float32))
+    M, dev = _tsdf_voxels(keys, f, wt, rgba), keys.device
     if M == 0:
-        return empty()
+        return _no_rows(dev, rgba)
     counts = torch.empty(M, device=dev, dtype=torch.int32)
     _lib.check(lib.geo4d_tsdf_count(keys.data_ptr(), M, f.data_ptr(), wt.data_ptr(), float(min_weight), counts.data_ptr(), _stream()),
                "geo4d_tsdf_count")
     last = torch.cumsum(counts, 0, dtype=torch.int64)
     P = int(last[-1])
     if P == 0:
-        return empty()
+        return _no_rows(dev, rgba)
     first = (last - counts).contiguous()
     pts = torch.empty((P, 3), device=dev, dtype=torch.float32)
     col = None if rgba is None else torch.empty((P, 4), device=dev, dtype=torch.uint8)
@@ -1503,15 +1488,10 @@ def tsdf_mesh_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
     f. keys int64 [M] sorted, f / wt / rgba as tsdf_integrate returns them. A cells and a count launch, two torch.cumsum, a vertices
     and a faces launch; reads (Q, V) back (one synchronisation)."""
     lib = _lib.load()
-    M, dev = _tsdf_keys(keys), keys.device
-    for t, what in ((f, "f"), (wt, "wt")):
-        assert _dev(t, what).dtype == torch.float32 and tuple(t.shape) == (M,) and t.is_contiguous(), (what, t.dtype, t.shape)
-    if rgba is not None:
-        assert _dev(rgba, "rgba").dtype == torch.uint8 and tuple(rgba.shape) == (M, 4) and rgba.is_contiguous(), (rgba.dtype, rgba.shape)
-    empty = lambda: (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
-                     torch.empty(0, device=dev, dtype=torch.float32), torch.empty((0, 3), device=dev, dtype=torch.int32))
+    M, dev = _tsdf_voxels(keys, f, wt, rgba), keys.device
+    no_faces = torch.empty((0, 3), device=dev, dtype=torch.int32)
     if M == 0:
-        return empty()
+        return _no_rows(dev, rgba, no_faces)
     complete = torch.empty(M, device=dev, dtype=torch.uint8)
     used = torch.empty(M, device=dev, dtype=torch.uint8)
     counts = torch.empty(M, device=dev, dtype=torch.int32)
@@ -1523,7 +1503,7 @@ def tsdf_mesh_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
     last_vertex = torch.cumsum(used, 0, dtype=torch.int64)
     Q, V = torch.stack([last_quad[-1], last_vertex[-1]]).tolist()
     if Q == 0:
-        return empty()
+        return _no_rows(dev, rgba, no_faces)
     first_quad, first_vertex = (last_quad - counts).contiguous(), (last_vertex - used).contiguous()
     vertices = torch.empty((V, 3), device=dev, dtype=torch.float32)
     col = None if rgba is None else torch.empty((V, 4), device=dev, dtype=torch.uint8)
@@ -1569,9 +1549,7 @@ def tsdf_points(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, 
     K, f, wt, col, M, dropped = tsdf_field(pts3d, depth, valid, views, centres, rgba, weight, voxel=voxel, trunc=trunc, near=near,
                                            capacity=capacity)
     if M == 0:
-        dev = pts3d.device
-        return (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
-                torch.empty(0, device=dev, dtype=torch.float32), 0, dropped)
+        return _no_rows(pts3d.device, rgba, 0, dropped)
     return (*tsdf_extract(K, f, wt, col, voxel=voxel, min_weight=min_weight), M, dropped)
 
 

@@ -29,6 +29,24 @@ def _views(cams2world, K):
     return torch.from_numpy(v.astype(np.float32))
 
 
+def _rgba(colors, lead, device, who, arg, step, named=""):
+    """u8 [*lead, 4] of `colors`: a u8 rgba as it is, or float [*lead, 3] in [0, 1] quantised as ops.scene_points does (clip(c * 255 +
+    0.5, 0, 255) truncated, in fp32) with alpha 255. The messages speak as `who` of its argument `arg` and of `step`, the thing that
+    runs; `named` puts a name in front of the shapes they quote ("[N, {}] = ")."""
+    if colors is None:
+        return None
+    if not colors.is_cuda:
+        raise _lib.Geo4DNativeError(f"{who}: `{arg}` lives on {colors.device}; {step} runs only on a HIP device")
+    if colors.dtype == torch.uint8:
+        if tuple(colors.shape) != (*lead, 4):
+            raise ValueError(f"{who}: uint8 colours must be rgba {named.format(4)}{(*lead, 4)}, got {tuple(colors.shape)}")
+        return colors.contiguous()
+    if tuple(colors.shape) != (*lead, 3):
+        raise ValueError(f"{who}: float colours must be {named.format(3)}{(*lead, 3)}, got {tuple(colors.shape)}")
+    rgb = ((colors.float() * 255.0) + 0.5).clamp(0.0, 255.0).to(torch.uint8)
+    return torch.cat([rgb, torch.full((*lead, 1), 255, dtype=torch.uint8, device=device)], -1).contiguous()
+
+
 def _scene_cameras(scene):
     """(cams2world [n, 4, 4], K [n, 3, 3]) fp64 on the host from a GroupAligner's poses, focals and principal points."""
     n = scene.n

@@ -33,7 +33,7 @@ import math
 import torch
 
 from . import _lib, ops
-from .render import _scene_cameras, _views
+from .render import _rgba, _scene_cameras, _views
 
 MOTION = (None, "static")
 MAX_TRUNC = 8
@@ -57,23 +57,6 @@ def check_tsdf_args(voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
     if capacity is not None and (int(capacity) != capacity or not 1 <= capacity <= 1 << 32 or int(capacity) & (int(capacity) - 1)):
         raise ValueError(f"tsdf_points: capacity must be a power of two in 1 .. 2^32, got {capacity!r}")
     return v
-
-
-def _rgba(rgb, shape, device):
-    """u8 [n, H, W, 4] of `rgb`: a u8 rgba as it is, or float [n, H, W, 3] in [0, 1] quantised as ops.scene_points does
-    (clip(c * 255 + 0.5, 0, 255) truncated, in fp32) with alpha 255."""
-    if rgb is None:
-        return None
-    if not rgb.is_cuda:
-        raise _lib.Geo4DNativeError(f"tsdf_points: `rgb` lives on {rgb.device}; the TSDF runs only on a HIP device")
-    if rgb.dtype == torch.uint8:
-        if tuple(rgb.shape) != (*shape, 4):
-            raise ValueError(f"tsdf_points: uint8 colours must be rgba {(*shape, 4)}, got {tuple(rgb.shape)}")
-        return rgb.contiguous()
-    if tuple(rgb.shape) != (*shape, 3):
-        raise ValueError(f"tsdf_points: float colours must be {(*shape, 3)}, got {tuple(rgb.shape)}")
-    q = ((rgb.float() * 255.0) + 0.5).clamp(0.0, 255.0).to(torch.uint8)
-    return torch.cat([q, torch.full((*shape, 1), 255, dtype=torch.uint8, device=device)], -1).contiguous()
 
 
 @torch.no_grad()
@@ -122,7 +105,7 @@ def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_wei
     if len(views) != shape[0]:
         raise ValueError(f"tsdf_points: {len(views)} cameras for {shape[0]} images")
     centres = torch.as_tensor(cams2world).detach().double().cpu().reshape(-1, 4, 4)[:, :3, 3].float().contiguous()
-    rgba = _rgba(rgb, shape, dev)
+    rgba = _rgba(rgb, shape, dev, "tsdf_points", "rgb", "the TSDF")
     Kv, f, wt, col, voxels, dropped = ops.tsdf_field(pts3d.detach().float().contiguous(), depth.detach().float().contiguous(),
                                                      None if valid is None else valid.to(dev), views.to(dev), centres.to(dev), rgba,
                                                      None if weight is None else weight.detach().float().contiguous(), voxel=v,
