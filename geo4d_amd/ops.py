@@ -1256,6 +1256,70 @@ def render_resolve(ws, colors, V, size, background=(1.0, 1.0, 1.0)):
     return rgb, depth, index
 
 
+RASTER_LARGE_AREA = 16           # from tools/render_mesh_bench.py's sweep (profiles/render_mesh.md)
+RASTER_LIST_CAPACITY = 1 << 16
+
+
+def _mesh(vertices, faces):
+    """(Nv, T) of vertices fp32 [Nv, 3] and faces int32 [T, 3] on the HIP device."""
+    return (_want(vertices, "vertices", torch.float32, (None, 3)).shape[0], _want(faces, "faces", torch.int32, (None, 3)).shape[0])
+
+
+def render_raster(vertices, faces, views, size, ws, face_mask=None, near=1e-3, cull_back=False, id_base=0, clear=True, *,
+                  large_area=None, capacity=None):
+    """Rasterise the mesh (vertices fp32 [Nv, 3] world, faces int32 [T, 3], face_mask [T] bool or None) into the key buffer of `ws`
+    (render_workspace) for views fp32 [V, 16]: per covered pixel the minimum of float_bits(zc) << 32 | (id_base + t). `clear=False` draws
+    into what render_splat / render_fill left. A triangle whose clipped bounding box holds more than `large_area` pixels goes through a
+    list of `capacity` entries that one wave per entry draws (a full list: the thread draws it itself); the image depends on neither."""
+    lib = _lib.load()
+    H, W = size
+    _dev(ws, "ws")
+    Nv, T = _mesh(vertices, faces)
+    V = _want(views, "views", torch.float32, (None, 16)).shape[0]
+    if face_mask is not None:
+        assert tuple(_dev(face_mask, "face_mask").shape) == (T,), face_mask.shape
+        face_mask = face_mask.to(torch.bool).contiguous()
+    capacity = RASTER_LIST_CAPACITY if capacity is None else int(capacity)
+    need = lib.geo4d_render_raster_workspace(capacity)
+    if need == 0:
+        raise _lib.Geo4DNativeError(f"geo4d_render_raster_workspace: need 0 <= capacity <= 2^28, got {capacity}")
+    lst = torch.empty((need + 7) // 8, device=ws.device, dtype=torch.int64)
+    _lib.check(lib.geo4d_render_raster(_ptr(vertices) if Nv else 0, Nv, _ptr(faces) if T else 0, T, _ptr(face_mask), views.data_ptr(), V, H, W,
+                                       float(near), int(bool(cull_back)), int(id_base), int(bool(clear)),
+                                       RASTER_LARGE_AREA if large_area is None else int(large_area), ws.data_ptr(), ws.numel() * 8,
+                                       lst.data_ptr(), need, _stream()), "geo4d_render_raster")
+    return ws
+
+
+def render_resolve_mesh(ws, colors, vertices, faces, views, size, vertex_colors=None, mesh_color=(0.7, 0.7, 0.7), shade=0.0, near=1e-3,
+                        background=(1.0, 1.0, 1.0)):
+    """(rgb uint8 [V, H, W, 3], depth fp32 [V, H, W], index int32 [V, H, W], face int32 [V, H, W]) of the key buffer of `ws` after
+    render_raster with id_base = N: colors fp32 [N, 3] of the points (None: no points, N = 0), the mesh and the views as render_raster
+    took them, vertex_colors uint8 rgba [Nv, 4] or fp32 [Nv, 3] (None: `mesh_color`), flat headlight shading of strength `shade`."""
+    lib = _lib.load()
+    H, W = size
+    _dev(ws, "ws")
+    N = 0 if colors is None else _want(colors, "colors", torch.float32, (None, 3)).shape[0]
+    Nv, T = _mesh(vertices, faces)
+    V = _want(views, "views", torch.float32, (None, 16)).shape[0]
+    rgba = rgbf = None
+    if vertex_colors is not None and vertex_colors.dtype == torch.uint8:
+        rgba = _want(vertex_colors, "vertex_colors", torch.uint8, (Nv, 4))
+    elif vertex_colors is not None:
+        rgbf = _want(vertex_colors, "vertex_colors", torch.float32, (Nv, 3))
+    rgb = torch.empty((V, H, W, 3), device=ws.device, dtype=torch.uint8)
+    depth = torch.empty((V, H, W), device=ws.device, dtype=torch.float32)
+    index = torch.empty((V, H, W), device=ws.device, dtype=torch.int32)
+    face = torch.empty((V, H, W), device=ws.device, dtype=torch.int32)
+    bg = (C.c_float * 3)(*[float(c) for c in background])
+    mc = (C.c_float * 3)(*[float(c) for c in mesh_color])
+    _lib.check(lib.geo4d_render_resolve_mesh(_ptr(colors) if N else 0, N, _ptr(vertices) if Nv else 0, Nv, _ptr(faces) if T else 0, T,
+                                             _ptr(rgba) if Nv else 0, _ptr(rgbf) if Nv else 0, mc, views.data_ptr(), float(near),
+                                             float(shade), bg, V, H, W, rgb.data_ptr(), depth.data_ptr(), index.data_ptr(),
+                                             face.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "geo4d_render_resolve_mesh")
+    return rgb, depth, index, face
+
+
 def motion_range(depth, valid=None):
     """The motion rule's workspace for depth fp32 [n, H, W] and valid bool [n, H, W] (None: every pixel): per pixel the (dmin, dmax) of
     the valid depths in its 3 x 3 neighbourhood, dmin = NaN on invalid pixels; fp32 [n, H, W, 2]."""

@@ -6,6 +6,8 @@ include/geo4d_hip.h and restated in numpy in tests/render_restatement.py. ``rend
 ``render_scene`` a ``GroupAligner`` in three modes (its own cameras, 4-D playback, a turntable), ``save_render`` writes PNG frames and
 a GIF. Pixel convention as everywhere in the project: pixel i sits at coordinate i, the principal point defaults to (W/2, H/2).
 Images are identical from run to run, bit for bit: the depth test is an integer minimum, which no arrival order changes.
+``render_mesh`` draws a triangle mesh, alone or under points, into the same buffer (csrc/render_mesh.hip: exact integer coverage,
+restated in tests/render_mesh_restatement.py), and ``render_scene(static_mesh=True)`` the static background as its TSDF surface.
 """
 import math
 import os
@@ -107,6 +109,80 @@ def render_points(points, colors, cams2world, K, size, *, mask=None, radius=None
     return dict(rgb=rgb, depth=depth, index=index)
 
 
+@torch.no_grad()
+def render_mesh(vertices, faces, cams2world, K, size, *, colors=None, mesh_color=(0.7, 0.7, 0.7), shade=0.0, cull_back=False,
+                face_mask=None, points=None, point_colors=None, mask=None, radius=None, sources=None, max_size=9, fill=0, near=1e-3,
+                background=(1, 1, 1)):
+    """Draw a triangle mesh, alone or under points, into V views; returns dict(rgb, depth, index as render_points gives them, face int32
+    [V, H, W]) on the device.
+
+    vertices [Nv, 3] fp32 world coordinates and faces [T, 3] integer on the HIP device; colors uint8 rgba [Nv, 4] (as tsdf_mesh returns
+    them, alpha ignored) or float [Nv, 3] in [0, 1], interpolated perspective-correctly, None: the uniform `mesh_color`. `shade` in
+    [0, 1] mixes in flat headlight shading (colour * ((1 - shade) + shade |n_z| / |n|), n the face normal in camera space).
+    `cull_back=True` drops the faces seen from behind (a front face is counter-clockwise as seen); face_mask [T] bool drops faces.
+    Every view draws the whole mesh. A triangle with a vertex not beyond `near` is dropped whole (no clipping), as is one that
+    projects more than 65536 pixels off; H and W may be at most 16384. Coverage is exact: a pixel belongs to a triangle iff its centre,
+    on a 1/256-pixel grid, is inside or on an edge; there is no anti-aliasing. points / point_colors / mask / radius / sources /
+    max_size / fill: points drawn into the same frames exactly as render_points draws them (hole filling acts on the points only);
+    per pixel the nearest of everything wins, at equal depth a point beats a triangle and a lower face a higher one. `index` is the
+    winning point's row or -1, `face` the winning triangle's row or -1. T = 0 or Nv = 0 gives what the points alone give."""
+    who = "render_mesh"
+    for t, what in ((vertices, "vertices"), (faces, "faces"), (points, "points"), (point_colors, "point_colors"), (face_mask, "face_mask")):
+        if t is not None and not t.is_cuda:
+            raise _lib.Geo4DNativeError(f"{who}: `{what}` lives on {t.device}; rendering runs only on a HIP device (there is no CPU "
+                                        "fallback)")
+    if vertices.dim() != 2 or vertices.shape[-1] != 3 or faces.dim() != 2 or faces.shape[-1] != 3 or faces.is_floating_point():
+        raise ValueError(f"{who}: need vertices [Nv, 3] and integer faces [T, 3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if (points is None) != (point_colors is None):
+        raise ValueError(f"{who}: points and point_colors go together")
+    if not 0.0 <= float(shade) <= 1.0:
+        raise ValueError(f"{who}: shade must lie in [0, 1], got {shade}")
+    dev = vertices.device
+    H, W = int(size[0]), int(size[1])
+    if H > 16384 or W > 16384:
+        raise ValueError(f"{who}: frames may be at most 16384 x 16384, got {(H, W)}")
+    vert = vertices.detach().float().contiguous()
+    tri = faces.to(torch.int32).contiguous()
+    Nv, T = vert.shape[0], tri.shape[0]
+    vcol = None
+    if colors is not None:
+        vcol = _rgba(colors, (Nv,), dev, who, "colors", "rendering", "[Nv, {}] = ") if colors.dtype == torch.uint8 else None
+        if vcol is None:
+            if not colors.is_cuda:
+                raise _lib.Geo4DNativeError(f"{who}: `colors` lives on {colors.device}; rendering runs only on a HIP device")
+            if tuple(colors.shape) != (Nv, 3):
+                raise ValueError(f"{who}: float colours must be [Nv, 3] = {(Nv, 3)}, got {tuple(colors.shape)}")
+            vcol = colors.detach().float().contiguous()
+    if face_mask is not None and tuple(face_mask.shape) != (T,):
+        raise ValueError(f"{who}: face_mask must be [T] = {(T,)}, got {tuple(face_mask.shape)}")
+    views = _views(cams2world, K)
+    V = len(views)
+    dviews = views.to(dev)
+    N, col = 0, None
+    if points is not None:
+        if points.shape[-1] != 3 or point_colors.shape != points.shape:
+            raise ValueError(f"{who}: points and point_colors must both be [..., 3], got {tuple(points.shape)} and "
+                             f"{tuple(point_colors.shape)}")
+        n_img = points.shape[0] if points.dim() > 2 else 1
+        pts = points.reshape(-1, 3).float().contiguous()
+        col = point_colors.reshape(-1, 3).float().contiguous()
+        N = pts.shape[0]
+    if N:
+        ptr, idx = _csr(sources, V, n_img)
+        flat = lambda t, dt: None if t is None else t.to(dev).reshape(-1).to(dt).contiguous()
+        ws = ops.render_workspace(V, H, W, len(idx), dev)
+        ops.render_splat(pts, dviews, ptr, idx, (H, W), ws, mask=flat(mask, torch.bool), radius=flat(radius, torch.float32),
+                         pts_per_image=N // n_img, near=near, max_size=max_size)
+        if fill:
+            ops.render_fill(ws, V, (H, W), fill)                 # before the raster: a copied triangle key would have no barycentrics
+    else:
+        ws, col = ops.render_workspace(V, H, W, 0, dev), None
+    ops.render_raster(vert, tri, dviews, (H, W), ws, face_mask=face_mask, near=near, cull_back=cull_back, id_base=N, clear=not N)
+    rgb, depth, index, face = ops.render_resolve_mesh(ws, col, vert, tri, dviews, (H, W), vertex_colors=vcol, mesh_color=mesh_color,
+                                                      shade=shade, near=near, background=background)
+    return dict(rgb=rgb, depth=depth, index=index, face=face)
+
+
 def orbit_cameras(center, radius, n, elevation=0.0, up=(0.0, -1.0, 0.0)):
     """[n, 4, 4] fp64 camera-to-world poses on a circle of `radius` round `center`, raised by `elevation` radians above the plane
     normal to `up`, each looking at `center`. OpenCV convention: x right, y down, z forward, so the image's top points along `up`
@@ -134,7 +210,7 @@ def orbit_cameras(center, radius, n, elevation=0.0, up=(0.0, -1.0, 0.0)):
 @torch.no_grad()
 def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=True, thr_for_init_conf=True, point_size=0, trail=0,
                  path=None, sources=None, n_views=24, elevation=0.3, orbit_radius=None, near=1e-3, max_size=9, fill=0,
-                 background=(1, 1, 1), persist_static=False):
+                 background=(1, 1, 1), persist_static=False, static_mesh=None, shade=0.0, cull_back=False):
     """Frames of a GroupAligner: dict(rgb, depth, index) as render_points returns them, one view per frame.
 
     Points, colours and masks are those get_3D_model_from_scene exports (get_pts3d, scene.imgs, get_masks with `min_conf_thr` /
@@ -147,9 +223,16 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
     `persist_static=True`: every view draws the static points of ALL images and the dynamic points (scene.dynamic_masks, made by
     geo4d_amd.motion.segment_motion with this call's thresholds when the scene has none) only of the images in its source list, so
     playback shows the current frame's movers over a background that is complete from the first frame and cameras / turntable
-    show the movers of no frame unless `sources` names some; `index` still counts rows of the scene's pts3d.reshape(-1, 3)."""
+    show the movers of no frame unless `sources` names some; `index` still counts rows of the scene's pts3d.reshape(-1, 3).
+    `static_mesh=True`, or a voxel size: the static background is drawn as the TSDF surface mesh instead (render_mesh; from
+    geo4d_amd.tsdf.tsdf_scene(scene, voxel, motion="static", mesh=True) with this call's thresholds, True meaning its default voxel;
+    scene.tsdf is reused when it already holds `vertices` - for True whatever its voxel, else for that voxel), with `shade` and
+    `cull_back` as render_mesh takes them. No static point is drawn, the moving points are chosen as persist_static chooses them, and
+    the dict also holds `face`, the winning triangle's row in scene.tsdf["faces"] or -1. Not together with persist_static."""
     if mode not in MODES:
         raise ValueError(f"render_scene: mode must be one of {MODES}, got {mode!r}")
+    if static_mesh is not None and static_mesh is not False and persist_static:
+        raise ValueError("render_scene: static_mesh draws the static part as a mesh and persist_static as points; choose one")
     if scene.imgs is None:
         raise ValueError("render_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs [n, H, W, 3] in [0, 1]")
     scene.require_all_depthmaps("render_scene")
@@ -190,6 +273,22 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
         Kv = Kv.clone()
         Kv[:, 0] *= ow / W
         Kv[:, 1] *= oh / H
+    if static_mesh is not None and static_mesh is not False:
+        # the static part as its TSDF surface, the moving points of each view's source images over it
+        voxel = None if static_mesh is True else float(np.float32(static_mesh))   # as scene.tsdf["voxel"] holds it
+        tsdf = getattr(scene, "tsdf", None)
+        if tsdf is None or "vertices" not in tsdf or (voxel is not None and tsdf["voxel"] != voxel):
+            from .tsdf import tsdf_scene
+            tsdf = tsdf_scene(scene, voxel, motion="static", mesh=True, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf,
+                              is_msk=is_msk, near=near)
+        dyn = getattr(scene, "dynamic_masks", None)
+        if dyn is None:
+            from .motion import segment_motion
+            dyn = segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+        movers = src if sources is not None or mode == "playback" else [[]] * len(src)
+        return render_mesh(tsdf["vertices"], tsdf["faces"], poses, Kv, (oh, ow), colors=tsdf.get("vertex_rgba", tsdf.get("rgba")),
+                           shade=shade, cull_back=cull_back, points=pts3d, point_colors=imgs, mask=dyn if msk is None else msk & dyn,
+                           radius=radius, sources=movers, max_size=max_size, fill=fill, near=near, background=background)
     if not persist_static:
         return render_points(pts3d, imgs, poses, Kv, (oh, ow), mask=msk, radius=radius, sources=src, near=near, max_size=max_size,
                              fill=fill, background=background)

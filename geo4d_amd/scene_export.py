@@ -158,12 +158,13 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
 
 
 def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynamic_masks=False, fuse_static=None, tsdf_static=None,
-               tsdf_mesh_static=None, **glb_kw):
+               tsdf_mesh_static=None, render_kw=None, **glb_kw):
     """test_geo4d.py:513-534: writes <outdir>/<seq>/ with <seq>.glb (called as the script calls it: as_pointcloud=True, is_msk=False,
     cam_size=0.01; `glb_kw` overrides), pred_traj.txt, pred_focal.txt, pred_intrinsics.txt, the depth maps (frame_%04d.npy + colour
     previews), conf_{i}.npy, init_conf_{i}.npy and frame_{i:04d}.png. `imgs` (a clip, see align.rgb_frames) replaces scene.imgs.
     `render`: None, or a mode of geo4d_amd.render.render_scene ("cameras", "playback", "turntable"): also writes <seq>/render/
-    (frame_%04d.png, render.gif) with the glb's threshold and masking. `dynamic_masks=True` also writes dynamic_mask_{i}.png
+    (frame_%04d.png, render.gif) with the glb's threshold and masking; `render_kw`: a dict of further arguments for render_scene, for
+    example dict(static_mesh=True, shade=0.5) (None: none). `dynamic_masks=True` also writes dynamic_mask_{i}.png
     (scene.dynamic_masks, made by geo4d_amd.motion.segment_motion with the glb's threshold and masking when the scene has none) and
     <seq>_static.glb, the glb without the moving points. `fuse_static`: a voxel size, or True for fuse_scene's default, also writes
     <seq>_static_fused.glb, the static points merged into one cloud (get_3D_model_from_scene(motion="static", fuse_voxel=...), always a
@@ -208,6 +209,7 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
         io.save_rgb_imgs(d, scene.imgs.detach().cpu().numpy())
     if render is not None:
         from . import render as _render
-        frames = _render.render_scene(scene, render, min_conf_thr=min_conf_thr, is_msk=is_msk, thr_for_init_conf=thr_init)
+        frames = _render.render_scene(scene, render, min_conf_thr=min_conf_thr, is_msk=is_msk, thr_for_init_conf=thr_init,
+                                      **(render_kw or {}))
         _render.save_render(os.path.join(d, "render"), frames["rgb"])
     return d

@@ -511,6 +511,50 @@ int geo4d_render_fill(int V, int H, int W, int passes, void* workspace, size_t w
 int geo4d_render_resolve(const float* colors, long N, const float* background, int V, int H, int W, unsigned char* rgb, float* depth,
                          int* index, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Triangle meshes in the renderer: an exact raster into the splats' key buffer and a deferred-shading resolve
+ * (geo4d_amd/csrc/render_mesh.hip, geo4d_amd/render.py render_mesh). The rule is this project's own, restated in numpy in
+ * tests/render_mesh_restatement.py; coverage is integer arithmetic, every float operation is + - * / or a correctly rounded conversion
+ * or square root in the written order, no FMA.
+ *   Device arrays: vertices [Nv][3] fp32 world coordinates, faces [T][3] int32, face_mask [T] bytes (NULL: all), views [V][16] as above;
+ *   every view draws the whole mesh. H, W <= 16384. Per (view, triangle t):
+ *   1 drop it when masked out, when an index is outside [0, Nv) (checked on the device, nothing is read out of bounds), or unless every
+ *     vertex has finite camera coordinates (the splat's xc, yc, zc) and zc > near: a triangle that crosses the near plane is dropped,
+ *     there is no clipping;
+ *   2 guard band: with u = fx (xc / zc) + cx, v likewise, drop it unless fabsf(u) < 65536 and fabsf(v) < 65536 at all three vertices,
+ *     decided in float (NaN drops);
+ *   3 snap: X = (long)floorf(u * 256.f + 0.5f), Y likewise (8 sub-pixel bits); pixel (x, y) is sampled at S = (256 x, 256 y);
+ *   4 int64 edge functions edge(A, B, S) = (Bx - Ax)(Sy - Ay) - (By - Ay)(Sx - Ax): E0 = edge(P1, P2, S), E1 = edge(P2, P0, S),
+ *     E2 = edge(P0, P1, S), A = edge(P0, P1, P2); every value stays below 2^51;
+ *   5 A == 0 drops it; with cull_back, A > 0 drops it (a front face is counter-clockwise as seen: A < 0 with y down); if A < 0 negate A
+ *     and every E_k;
+ *   6 candidates x = max(0, (minX + 255) >> 8) .. min(W - 1, maxX >> 8), y likewise; covered iff E0 >= 0 && E1 >= 0 && E2 >= 0: every
+ *     edge inclusive, no top-left rule, two triangles sharing an edge both claim its pixels and the depth test decides;
+ *   7 iz_k = 1.f / zc_k, w_k = (float)((double)E_k / (double)A), q = ((w0 iz0) + (w1 iz1)) + (w2 iz2), zc = 1.f / q (perspective
+ *     correct); the pixel is skipped unless zc > 0;
+ *   8 one unsigned 64-bit atomic minimum of key = float_bits(zc) << 32 | (id_base + t) on the view's pixel, id_base + T < 2^32 - 1:
+ *     with id_base = the point count a point beats a triangle at equal depth, and a lower face a higher one.
+ *   geo4d_render_raster: `workspace` is the key buffer of geo4d_render_workspace; clear = 1 sets it to all ones first (a mesh alone),
+ *     clear = 0 draws into what splat and fill left (fill runs BEFORE the raster: a copied triangle key would have no barycentrics). A
+ *     (view, triangle) whose clipped bounding box holds more than large_area pixels is appended to `list` (geo4d_render_raster_workspace
+ *     (capacity) bytes, 8-byte aligned: an 8-byte count, zeroed here, then capacity int pairs) and drawn by a second launch, one wave per
+ *     entry; when the list is full the appending thread draws the triangle itself. The image depends on none of this.
+ *   geo4d_render_resolve_mesh: a key with id < N is a point (as geo4d_render_resolve; colors may be NULL when N == 0); id >= N + T reads
+ *     nothing and gives background; a triangle key, t = id - N, repeats steps 1 to 7 for its pixel (same integers, same w_k), depth is
+ *     the key's, b_k = (w_k iz_k) zc, colour c = (b0 c0 + b1 c1) + b2 c2 per channel with c_k the vertex colour: vertex_rgba [Nv][4] u8
+ *     as (float)u8 / 255.f (alpha ignored), or vertex_rgb [Nv][3] fp32 as given, or, with both NULL, the HOST array mesh_color [3].
+ *     shade > 0 (at most 1): flat headlight shading with the camera-space edges e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 (nx = e1y e2z -
+ *     e1z e2y and cyclic), len2 = (nx nx + ny ny) + nz nz, lam = len2 > 0 ? fabsf(nz) / sqrtf(len2) : 0 (correctly rounded), g = (1 -
+ *     shade) + shade lam, colour = c g. Outputs as geo4d_render_resolve (rgb quantised the same way) and face [V][H][W] int32 = t or
+ *     -1; index is -1 where a triangle won. Any output may be NULL, not all. */
+size_t geo4d_render_raster_workspace(long capacity);
+int geo4d_render_raster(const float* vertices, long Nv, const int* faces, long T, const unsigned char* face_mask, const float* views,
+                        int V, int H, int W, float near, int cull_back, long id_base, int clear, int large_area, void* workspace,
+                        size_t workspace_bytes, void* list, size_t list_bytes, void* stream);
+int geo4d_render_resolve_mesh(const float* colors, long N, const float* vertices, long Nv, const int* faces, long T,
+                              const unsigned char* vertex_rgba, const float* vertex_rgb, const float* mesh_color, const float* views,
+                              float near, float shade, const float* background, int V, int H, int W, unsigned char* rgb, float* depth,
+                              int* index, int* face, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* Which pixels of the aligned scene moved: geometric votes between the images (geo4d_amd/csrc/motion.hip, geo4d_amd/motion.py). Nothing
  * of the reference is replaced (it fills dynamic_mask_{i}.png from optical flow and SAM2); the rule is this project's own, restated in
  * numpy in tests/motion_restatement.py.
