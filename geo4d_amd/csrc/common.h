@@ -212,6 +212,16 @@ __device__ __forceinline__ float clamp_f16_range(float e) {
 __device__ __forceinline__ u32x2 pack4_f16_sat(const float* e) {
     return u32x2{f32x2_to_f16x2(clamp_f16_range(e[0]), clamp_f16_range(e[1])), f32x2_to_f16x2(clamp_f16_range(e[2]), clamp_f16_range(e[3]))};
 }
+// The same bits from the other side of the conversion (the wide GEMM epilogue, gemm_epilogue.h): the round-to-nearest-even conversion sends
+// exactly the values beyond the range that do not round back into it (|e| >= 65520) to +-inf, so clamping the PACKED f16 pair gives what
+// converting the clamped f32 gives - two instructions per pair (v_pk_minimum3_f16 / v_pk_maximum3_f16, which hand a NaN on as IEEE 754-2019
+// minimum / maximum do) where clamp_f16_range costs four per element (canonicalize, v_med3, compare, select).
+__device__ __forceinline__ unsigned int f32x2_to_f16x2_sat(float lo, float hi) {
+    f32x2 v = {lo, hi};
+    const f16x2_t top = {(_Float16)65504.0f, (_Float16)65504.0f};
+    const f16x2_t h = __builtin_elementwise_maximum(__builtin_elementwise_minimum(__builtin_convertvector(v, f16x2_t), top), -top);
+    return __builtin_bit_cast(unsigned int, h);
+}
 // debug counter of the clamping stores (geo4d_conv_gemm_t.sat_count & co; NULL in production): += the lanes of this wave that hold a value
 // beyond the finite f16 range (|e| > 65504, inf included; NaN is not a saturation). One atomic per wave that saw any. Wave-uniform call sites only.
 __device__ __forceinline__ void count_f16_saturation(unsigned long long* counter, const float* e) {

@@ -3,7 +3,8 @@
 //   * the value math: epi_value (alpha, per-row bias, column bias, row-bias table, SiLU / GELU) and geglu_value, in ONE floating-point
 //     order that every call site had before it was factored out (sites that differ by even a `+ 0.f` keep their own line);
 //   * store policies (element size + pack + store of one lane's 4 consecutive columns) and the register epilogue's fast paths written
-//     once over them: geglu_fast, plain_fast16; the wide f32 plain path (the one that carries gn_colsum and the row biases) is its own.
+//     once over them: geglu_fast, plain_fast16 (8-byte stores of 16-bit rows) and their 16-byte forms geglu_wide16, plain_wide16; the wide
+//     f32 plain path (the one that carries gn_colsum and the row biases) is its own.
 #pragma once
 #include "common.h"
 #include "geo4d_hip.h"
@@ -88,6 +89,10 @@ __device__ __forceinline__ void unpack4_16(const u32x2 r, const bool isbf, float
 // offers an offset beyond the 2 GB window (stores dropped, loads return 0 - no exec-masked branches, so hipcc's waits stay COUNTED), an
 // absent bias / residual is a resource with zero records (its loads return 0 without touching memory).
 constexpr unsigned EPI_OOB = 0x80000000u;
+// debug_ablate bit 6 (A/B runs and the bit tests, ops.EPI_WIDE = 0): 16-bit rows keep the 8-byte epilogue (geglu_fast / plain_fast16);
+// the low six bits keep their meanings (2 = three persistent workgroups, 16 + g = tile order)
+constexpr int EPI_ABLATE_NARROW = 64, EPI_ABLATE_LOW = 63;
+__device__ __forceinline__ bool epi_wide_on(const geo4d_conv_gemm_t& p) { return (p.debug_ablate & EPI_ABLATE_NARROW) == 0; }
 constexpr int EPI_RSRC_FLAGS = 0x00020000;
 __device__ __forceinline__ void* uniform_ptr(const void* q) {
     const unsigned long long v = (unsigned long long)q;
@@ -133,6 +138,10 @@ struct StoreRows16 {               // bf16 / f16 rows of an un-split launch (a s
     static __device__ __forceinline__ bool isbf(const geo4d_conv_gemm_t& p) { return p.out_dtype == GEO4D_BF16; }
     static __device__ __forceinline__ u32x2 pack(const geo4d_conv_gemm_t& p, const float (&e)[4]) { return pack4_16(e, isbf(p)); }
     static __device__ __forceinline__ void store(const u32x2 v, const __amdgpu_buffer_rsrc_t rs, const unsigned off) { __builtin_amdgcn_raw_buffer_store_b64(v, rs, off, 0, 0); }
+    // the 16-byte forms' halves (nothing to count)
+    static __device__ __forceinline__ bool counts(const geo4d_conv_gemm_t&) { return false; }
+    static __device__ __forceinline__ void count(const geo4d_conv_gemm_t&, const float (&)[4]) {}
+    static __device__ __forceinline__ u32x2 pack_half(const geo4d_conv_gemm_t& p, const float (&e)[4]) { return pack4_16(e, isbf(p)); }
 };
 struct StoreF16Sat {               // plain f16 rows clamped to the finite range, NaN kept (common.h pack4_f16_sat); p.sat_count (debug) counts the clamped lanes
     static constexpr unsigned ES = 2;
@@ -141,7 +150,39 @@ struct StoreF16Sat {               // plain f16 rows clamped to the finite range
         return pack4_f16_sat(e);
     }
     static __device__ __forceinline__ void store(const u32x2 v, const __amdgpu_buffer_rsrc_t rs, const unsigned off) { __builtin_amdgcn_raw_buffer_store_b64(v, rs, off, 0, 0); }
+    // the 16-byte forms' halves: the counter's test is made once per wave tile (counts), not per store, and the clamp works on the
+    // packed pair (common.h f32x2_to_f16x2_sat: the same bits)
+    static __device__ __forceinline__ bool counts(const geo4d_conv_gemm_t& p) { return p.sat_count != nullptr; }
+    static __device__ __forceinline__ void count(const geo4d_conv_gemm_t& p, const float (&e)[4]) { count_f16_saturation(p.sat_count, e); }
+    static __device__ __forceinline__ u32x2 pack_half(const geo4d_conv_gemm_t&, const float (&e)[4]) {
+        return u32x2{f32x2_to_f16x2_sat(e[0], e[1]), f32x2_to_f16x2_sat(e[2], e[3])};
+    }
 };
+
+// ---- 16-byte stores of 16-bit rows: two horizontally adjacent 16-column blocks b, b + 1 ---------------------------------------------------
+// A lane holds 8 bytes of each block (its columns 4 lq .. 4 lq + 3). v_permlane16_swap trades the odd 16-lane rows of the first operand for
+// the even rows of the second (as StoreSplit::pack does for hi | lo): an even lq ends with [own x | x of lq + 1] = columns 4 lq .. 4 lq + 7
+// of block b, an odd lq with [y of lq - 1 | own y] = columns 4 (lq - 1) .. 4 lq + 3 of block b + 1 - 12 columns after its own 4 lq of
+// block b (pair_shift16). One 16-byte store where two 8-byte ones stood, a row's run 64 contiguous bytes; every lane of the wave takes part.
+// The exchange is its own inverse: unpair_rows16 turns a 16-byte load at the same offset into the two blocks' halves (the residual).
+__device__ __forceinline__ unsigned pair_shift16(const int lq) { return (lq & 1) ? 24u : 0u; }      // bytes
+__device__ __forceinline__ u32x4 pair_rows16(const u32x2 x, const u32x2 y) {
+    const u32x2 s0 = __builtin_amdgcn_permlane16_swap(x[0], y[0], false, false);
+    const u32x2 s1 = __builtin_amdgcn_permlane16_swap(x[1], y[1], false, false);
+    return u32x4{s0[0], s1[0], s0[1], s1[1]};
+}
+__device__ __forceinline__ void unpair_rows16(const u32x4 r, u32x2& x, u32x2& y) {
+    const u32x2 s0 = __builtin_amdgcn_permlane16_swap(r[0], r[2], false, false);
+    const u32x2 s1 = __builtin_amdgcn_permlane16_swap(r[1], r[3], false, false);
+    x = u32x2{s0[0], s1[0]};
+    y = u32x2{s0[1], s1[1]};
+}
+// whether a wave tile takes the 16-byte forms: the switch, and every one of its NB blocks whole inside N (wave-uniform, in SGPRs: a
+// scalar branch around the whole epilogue, no exec masks; a wave tile cut by N keeps the 8-byte code, which folds the cut into its offsets)
+template <int NB>
+__device__ __forceinline__ bool wide16_tile(const geo4d_conv_gemm_t& p, const int n_w0) {
+    return NB >= 2 && epi_wide_on(p) && __builtin_amdgcn_readfirstlane(n_w0) + 16 * NB <= p.N;
+}
 
 // ---- fast paths of the register epilogue: acc[a][b][j] is out[m_w0 + 16a + lr][n_w0 + 16b + 4lq + j] --------------------------------------
 // `corner`: the element of the output at the wave tile's corner (row m_w0, first stored column), `ldo`: the row pitch in elements.
@@ -176,7 +217,8 @@ __device__ __forceinline__ void geglu_fast(const geo4d_conv_gemm_t& p, const f32
 
 // 16-bit rows, alpha + column bias (+ residual: RES, read through `rcorner` / `ldr` a row block AHEAD of the stores so that its wait
 // stays counted): 8-byte vectors
-template <int MB, int NB, bool RES, typename Store>
+// (B0: the first block - the 16-byte form leaves the last block of an odd NB to this code)
+template <int MB, int NB, bool RES, typename Store, int B0 = 0>
 __device__ __forceinline__ void plain_fast16(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const void* corner, const long ldo,
                                              const void* rcorner, const bool has_res, const int m_w0, const int n_w0, const int lr, const int lq) {
     const __amdgpu_buffer_rsrc_t rsO = tile_rsrc(corner);
@@ -190,7 +232,7 @@ __device__ __forceinline__ void plain_fast16(const geo4d_conv_gemm_t& p, const f
         rowR = (unsigned)p.ldr * 32u;
     }
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
+    for (int b = B0; b < NB; ++b) {
         const bool colok = n_w0 + 16 * b + 4 * lq < p.N;
         const u32x4 bcu = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
         u32x2 ru = {0u, 0u};
@@ -213,6 +255,97 @@ __device__ __forceinline__ void plain_fast16(const geo4d_conv_gemm_t& p, const f
             Store::store(c, rsO, (ok ? offO + a * rowO : EPI_OOB) + 32u * b);
         }
     }
+}
+
+// ---- the 16-byte forms (wide16_tile: every block of the wave tile inside N, so only rows are cut). The same IEEE operations in the same
+// order as the 8-byte forms and the same bytes stored; COUNT: p.sat_count is set (debug) - tested once, by the callers below.
+template <int MB, int NB, typename Store, bool COUNT>
+__device__ __forceinline__ void geglu_wide16_rows(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const void* corner, const long ldo,
+                                                  const int m_w0, const int n_w0, const int lr, const int lq) {
+    if constexpr (NB % 4 == 0) {
+        const __amdgpu_buffer_rsrc_t rsO = tile_rsrc(corner);
+        const __amdgpu_buffer_rsrc_t rsB = bias_rsrc(p, p.bias != nullptr, n_w0);
+        const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 2u + pair_shift16(lq), rowO = (unsigned)ldo * 32u;      // bytes per 16-row block
+#pragma unroll
+        for (int b = 0; b < NB; b += 4) {                  // value blocks b, b + 1 (adjacent in the output), gate blocks b + 2, b + 3
+            u32x4 bu[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bu[i] = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * (b + i), 0, 0);
+#pragma unroll
+            for (int a = 0; a < MB; ++a) {
+                const bool ok = m_w0 + a * 16 + lr < p.M;
+                float e0[4], e1[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    e0[j] = geglu_value(p.alpha, acc[a][b][j], acc[a][b + 2][j], __uint_as_float(bu[0][j]), __uint_as_float(bu[2][j]));
+                    e1[j] = geglu_value(p.alpha, acc[a][b + 1][j], acc[a][b + 3][j], __uint_as_float(bu[1][j]), __uint_as_float(bu[3][j]));
+                }
+                if constexpr (COUNT) { Store::count(p, e0); Store::count(p, e1); }
+                const u32x4 c = pair_rows16(Store::pack_half(p, e0), Store::pack_half(p, e1));
+                __builtin_amdgcn_raw_buffer_store_b128(c, rsO, (ok ? offO + a * rowO : EPI_OOB) + 16u * b, 0, 0);      // 32 output columns per group
+            }
+        }
+    }
+}
+template <int MB, int NB, typename Store>
+__device__ __forceinline__ void geglu_wide16(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const void* corner, const long ldo,
+                                             const int m_w0, const int n_w0, const int lr, const int lq) {
+    if (Store::counts(p)) geglu_wide16_rows<MB, NB, Store, true>(p, acc, corner, ldo, m_w0, n_w0, lr, lq);
+    else geglu_wide16_rows<MB, NB, Store, false>(p, acc, corner, ldo, m_w0, n_w0, lr, lq);
+}
+
+// alpha + column bias (+ residual: one 16-byte load per block pair, at the stores' own offsets and a row block AHEAD of them)
+template <int MB, int NB, bool RES, typename Store, bool COUNT>
+__device__ __forceinline__ void plain_wide16_rows(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const void* corner, const long ldo,
+                                                  const void* rcorner, const bool has_res, const int m_w0, const int n_w0, const int lr, const int lq) {
+    const __amdgpu_buffer_rsrc_t rsO = tile_rsrc(corner);
+    const __amdgpu_buffer_rsrc_t rsB = bias_rsrc(p, p.bias != nullptr, n_w0);
+    const unsigned offO = (unsigned)(lr * (int)ldo + 4 * lq) * 2u + pair_shift16(lq), rowO = (unsigned)ldo * 32u;       // bytes per 16-row block
+    __amdgpu_buffer_rsrc_t rsR = rsO;
+    unsigned offR = 0, rowR = 0;
+    if constexpr (RES) {
+        rsR = tile_rsrc(has_res ? rcorner : p.zeros, has_res);
+        offR = (unsigned)(lr * (int)p.ldr + 4 * lq) * 2u + pair_shift16(lq);
+        rowR = (unsigned)p.ldr * 32u;
+    }
+#pragma unroll
+    for (int b = 0; b + 1 < NB; b += 2) {
+        const u32x4 bc0 = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * b, 0, 0);
+        const u32x4 bc1 = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(4 * lq) * 4u + 64u * (b + 1), 0, 0);
+        u32x4 ru = {0u, 0u, 0u, 0u};
+        if constexpr (RES) ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, (m_w0 + lr < p.M ? offR : EPI_OOB) + 32u * b, 0, 0);
+#pragma unroll
+        for (int a = 0; a < MB; ++a) {
+            const bool ok = m_w0 + a * 16 + lr < p.M;
+            float e0[4], e1[4], rf0[4], rf1[4];
+            if constexpr (RES) {
+                u32x2 r0, r1;
+                unpair_rows16(ru, r0, r1);
+                unpack4_16(r0, Store::isbf(p), rf0);
+                unpack4_16(r1, Store::isbf(p), rf1);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                e0[j] = acc[a][b][j] * p.alpha + __uint_as_float(bc0[j]);
+                e1[j] = acc[a][b + 1][j] * p.alpha + __uint_as_float(bc1[j]);
+                if constexpr (RES) { e0[j] += rf0[j]; e1[j] += rf1[j]; }
+            }
+            if constexpr (COUNT) { Store::count(p, e0); Store::count(p, e1); }
+            const u32x4 c = pair_rows16(Store::pack_half(p, e0), Store::pack_half(p, e1));
+            if constexpr (RES) {
+                if (a + 1 < MB)
+                    ru = __builtin_amdgcn_raw_buffer_load_b128(rsR, (m_w0 + (a + 1) * 16 + lr < p.M ? offR : EPI_OOB) + 32u * b, (a + 1) * rowR, 0);
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(c, rsO, (ok ? offO + a * rowO : EPI_OOB) + 32u * b, 0, 0);
+        }
+    }
+}
+template <int MB, int NB, bool RES, typename Store>
+__device__ __forceinline__ void plain_wide16(const geo4d_conv_gemm_t& p, const f32x4 (&acc)[MB][NB], const void* corner, const long ldo,
+                                             const void* rcorner, const bool has_res, const int m_w0, const int n_w0, const int lr, const int lq) {
+    if (Store::counts(p)) plain_wide16_rows<MB, NB, RES, Store, true>(p, acc, corner, ldo, rcorner, has_res, m_w0, n_w0, lr, lq);
+    else plain_wide16_rows<MB, NB, RES, Store, false>(p, acc, corner, ldo, rcorner, has_res, m_w0, n_w0, lr, lq);
+    if constexpr (NB & 1) plain_fast16<MB, NB, RES, Store, NB - 1>(p, acc, corner, ldo, rcorner, has_res, m_w0, n_w0, lr, lq);      // the odd last block
 }
 
 }  // namespace geo4d_gemm

@@ -85,7 +85,10 @@ __device__ __forceinline__ void tile_of(long t, int tiles_n, int tiles_mn, int g
     tm = first_m + (r - tn * rows);
 }
 // debug_ablate 16 + g (A/B runs, tests): GROUP_M = g; otherwise 1 = column-fastest
-__device__ __forceinline__ int tile_group_m(const geo4d_conv_gemm_t& p) { return (p.debug_ablate >= 16 && p.debug_ablate < 48) ? p.debug_ablate - 16 : 1; }
+__device__ __forceinline__ int tile_group_m(const geo4d_conv_gemm_t& p) {
+    const int low = p.debug_ablate & EPI_ABLATE_LOW;      // (bit 6 is the epilogue's switch, gemm_epilogue.h)
+    return (low >= 16 && low < 48) ? low - 16 : 1;
+}
 
 // The two-pass f16 type's activation panel has 64-byte rows (round 5, "A64"): it multiplies ONE f16 per activation element, and the
 // cost of staging is per 1 KB LDS-DMA request (profiles/r03_gemm_v2_explore_and_ablation.md), so a request covers 16 rows of the 32-k slab
@@ -287,6 +290,14 @@ __device__ __forceinline__ void generic_rows(const geo4d_conv_gemm_t& p, const f
     }
 }
 
+// Whether the 16-bit-row launches of a bf16 tile with MB x NB accumulator blocks per wave take the 16-byte epilogue forms. What decides is
+// the wave tile (it is the accumulators that fill the register file), so that is the key; a NEW tile with one of these wave tiles starts
+// on the 8-byte forms until tools/kernel_resources.py says otherwise. Without room today (profiles/epilogue_wide.md):
+//   4 x 8 - hint 22, 256x256 on 4 x 2 waves: 9 spilled VGPRs would become 26 (scratch 40 -> 108 bytes per lane);
+//   2 x 4 - hint 27, 64x128 on 2 x 2 waves: 163 -> 177 VGPRs, 2 waves per SIMD where its LDS footprint lets 3 run.
+template <int MB, int NB>
+constexpr bool rows16_wide_fits() { return !(MB == 4 && NB == 8) && !(MB == 2 && NB == 4); }
+
 // The dispatcher. T: the element type (4-byte types never take the 16-bit-row fast paths; the two-pass f16 type's OSPLIT output,
 // o_split = 2, is PLAIN f16 rows instead of bf16 hi | lo halves); VECONLY: the host checked the vector-store conditions (no scalar
 // fallback code).
@@ -308,6 +319,12 @@ __device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f
         // o_split = 2 (the two-pass f16 type; round 6): O = PLAIN f16 rows - the A operand of the next dtype-4 launch (GEGLU -> ff-out). The
         // launcher checked: no split-K, no residual / row biases, act 0 or GEGLU, stored columns % 8 == 0, 16-byte aligned rows.
         const unsigned short* corner = (unsigned short*)p.O + e_bz * p.o_bs + (long)m_w0 * p.ldo + (geglu ? (n_w0 >> 1) : n_w0);
+        // wave tiles with every block inside N: 16-byte stores (gemm_epilogue.h; the launcher's alignment checks cover them)
+        if (wide16_tile<NB>(p, n_w0)) {
+            if (geglu) geglu_wide16<MB, NB, StoreF16Sat>(p, acc, corner, p.ldo, m_w0, n_w0, lr, lq);
+            else plain_wide16<MB, NB, false, StoreF16Sat>(p, acc, corner, p.ldo, nullptr, false, m_w0, n_w0, lr, lq);
+            return;
+        }
         if (geglu) geglu_fast<MB, NB, StoreF16Sat>(p, acc, corner, p.ldo, m_w0, n_w0, lr, lq);
         else plain_fast16<MB, NB, false, StoreF16Sat>(p, acc, corner, p.ldo, nullptr, false, m_w0, n_w0, lr, lq);
         return;
@@ -318,6 +335,15 @@ __device__ __forceinline__ void reg_epilogue(const geo4d_conv_gemm_t& p, const f
     if (wide && geglu) return geglu_fast<MB, NB, Wide>(p, acc, (float*)d.O + d.obase + (long)m_w0 * d.ldo + (n_w0 >> 1), d.ldo, m_w0, n_w0, lr, lq);
     if constexpr (!IsX3<T>::value) {      // 16-bit rows (the bf16 / f16 modes): the same structures with 8-byte vectors
         const unsigned short* row0 = (unsigned short*)d.O + d.obase + (long)m_w0 * d.ldo;
+        // 16-byte stores (and residual loads) where the rows are aligned for them and the wave tile lies inside N (gemm_epilogue.h)
+        if constexpr (rows16_wide_fits<MB, NB>()) {
+            if (vec_ok && odt != GEO4D_F32 && wide16_tile<NB>(p, n_w0) && (d.ldo & 7) == 0 && (((uintptr_t)d.O + d.obase * 2) & 15) == 0 &&
+                (!has_res || ((p.ldr & 7) == 0 && (((uintptr_t)p.R + rbase * 2) & 15) == 0))) {
+                if (geglu) return geglu_wide16<MB, NB, StoreRows16>(p, acc, row0 + (n_w0 >> 1), d.ldo, m_w0, n_w0, lr, lq);
+                if (p.act == 0 && !p.rowbias && !(p.bias && p.bias_per_row))
+                    return plain_wide16<MB, NB, true, StoreRows16>(p, acc, row0 + n_w0, d.ldo, (const unsigned short*)p.R + rbase + (long)m_w0 * p.ldr + n_w0, has_res, m_w0, n_w0, lr, lq);
+            }
+        }
         if (vec_ok && odt != GEO4D_F32 && !geglu && p.act == 0 && !p.rowbias && !(p.bias && p.bias_per_row))
             return plain_fast16<MB, NB, true, StoreRows16>(p, acc, row0 + n_w0, d.ldo, (const unsigned short*)p.R + rbase + (long)m_w0 * p.ldr + n_w0, has_res, m_w0, n_w0, lr, lq);
         if (vec_ok && odt != GEO4D_F32 && geglu) return geglu_fast<MB, NB, StoreRows16>(p, acc, row0 + (n_w0 >> 1), d.ldo, m_w0, n_w0, lr, lq);
@@ -595,7 +621,7 @@ int launch_persistent(const geo4d_conv_gemm_t& p, const Plan& plan, hipStream_t 
     const int tiles_mn = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     const long total = (long)tiles_mn * p.batch * plan.splits;
     // debug_ablate = 2 (tests only): 3 workgroups whatever the problem, so that small shapes walk the persistent tile loop
-    const long cap = p.debug_ablate == 2 ? 3 : resident;
+    const long cap = (p.debug_ablate & EPI_ABLATE_LOW) == 2 ? 3 : resident;
     const unsigned grid = (unsigned)(total < cap ? total : cap);
     if constexpr (UP2) hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn, Up2Args{plan.up_w, plan.up_phase});
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, stream, p, plan.splits, tiles_mn);

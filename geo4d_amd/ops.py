@@ -221,6 +221,9 @@ TUNE_EXACT = _env_level("GEO4D_TUNE_EXACT", 0)
 # (key, chosen (tile, split), ms per launch, finalists) of every shape autotuned in this process (tools/tune_gemm.py prints it)
 TUNE_LOG = []
 DEBUG_ABLATE = _env_level("GEO4D_DEBUG_ABLATE", 0)       # tests / A-B runs: 2 = three persistent workgroups; 16 + g = tile order with GROUP_M = g (17 = column-fastest)
+# 0: 16-bit output rows keep the 8-byte epilogue (two stores per pair of 16-column blocks, the f16 clamp in f32, the debug counter tested per
+# store) instead of the 16-byte one - same bits (tests/test_epilogue_wide_gpu.py), A/B: profiles/epilogue_wide.md. Bit 6 of debug_ablate.
+EPI_WIDE = _env_level("GEO4D_EPI_WIDE", 1)
 GEMM_TIMELINE = None   # set to a list to have conv_gemm bracket every launch with HIP events: (flops, start, end, MFMA passes per product)
 ATTN_TIMELINE = None   # the same for the spatial self-attention launches (one key/value set) of ops.attention
 SAT_COUNTER = None     # debug: an int64 [1] device tensor -> every f16-clamping store (GroupNorm / LayerNorm / GEGLU epilogue writing the two-pass
@@ -396,7 +399,7 @@ def conv_gemm_descriptor(a, w, out, *, M, N, K, Cin, lda, ldw, ldo, T=1, Hin=1, 
     p.rowbias_div, p.bias_per_row, p.act = rowbias_div, int(bias_per_row), act
     p.dtype, p.out_dtype, p.out_nchw, p.tile_hint = code, (F32 if code == F16X2 else dt_code(out.dtype)), int(out_nchw), tile_hint
     p.alpha, p.split_k = alpha, split_k
-    p.debug_ablate = DEBUG_ABLATE
+    p.debug_ablate = DEBUG_ABLATE | (0 if EPI_WIDE else 64)
     p.a_split, p.w_split = int(a_split), int(w_split)
     p.o_split = 1 if isinstance(out, SplitAct) else 2 if (code == F16X2 and out.dtype == torch.float16) else 0
     if p.o_split == 1:
