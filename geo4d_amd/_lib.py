@@ -246,6 +246,14 @@ SIGNATURES = {
                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "geo4d_tsdf_mesh_faces": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long,
                                         C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_components_hook": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_components_flatten": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_components_count": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_select_mark": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_select_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1583,6 +1583,90 @@ def tsdf_mesh_extract(keys, f, wt, rgba=None, *, voxel, min_weight=4.0):
     return vertices, col, w, faces
 
 
+def _mesh_faces(faces, mask, what):
+    """(T, mask as contiguous uint8 or None) of faces int32 [T, 3] and a per-face mask [T] (bool or uint8) on the HIP device."""
+    T = _want(faces, "faces", torch.int32, (None, 3)).shape[0]
+    if mask is not None:
+        assert tuple(_dev(mask, what).shape) == (T,) and mask.dtype in (torch.bool, torch.uint8), (what, mask.dtype, tuple(mask.shape))
+        mask = mask.contiguous().view(torch.uint8)                  # a bool's byte is 0 or 1
+    return T, mask
+
+
+def mesh_components(faces, n_vertices, face_mask=None):
+    """(vertex_component int32 [Nv], face_component int32 [T], component_vertices int32 [C], component_faces int32 [C]): the connected
+    pieces of the mesh faces int32 [T, 3] over `n_vertices` vertices (the rule of include/geo4d_hip.h): a face is valid iff `face_mask`
+    ([T] bool or uint8; None: every face) lets it through and its indices lie in [0, Nv); vertices joined by a chain of valid faces
+    sharing a vertex are one component, numbered in ascending order of their smallest vertex; -1 marks a vertex no valid face names and
+    a face that is not valid. A hook (lock-free union-find), a flatten and a count launch with one torch.cumsum between; reads C back
+    (one synchronisation)."""
+    lib = _lib.load()
+    Nv = int(n_vertices)
+    assert 0 <= Nv < 1 << 31, n_vertices
+    T, mask = _mesh_faces(faces, face_mask, "face_mask")
+    dev = faces.device
+    none = torch.empty(0, device=dev, dtype=torch.int32)
+    vertex_component = torch.full((Nv,), -1, device=dev, dtype=torch.int32)
+    face_component = torch.full((T,), -1, device=dev, dtype=torch.int32)
+    if T == 0 or Nv == 0:
+        return vertex_component, face_component, none, none.clone()
+    parent, root = torch.empty(Nv, device=dev, dtype=torch.int32), torch.empty(Nv, device=dev, dtype=torch.int32)
+    touched, is_root = torch.empty(Nv, device=dev, dtype=torch.uint8), torch.empty(Nv, device=dev, dtype=torch.uint8)
+    _lib.check(lib.geo4d_mesh_components_hook(faces.data_ptr(), T, Nv, _ptr(mask), parent.data_ptr(), touched.data_ptr(), _stream()),
+               "geo4d_mesh_components_hook")
+    _lib.check(lib.geo4d_mesh_components_flatten(parent.data_ptr(), touched.data_ptr(), Nv, root.data_ptr(), is_root.data_ptr(), _stream()),
+               "geo4d_mesh_components_flatten")
+    last = torch.cumsum(is_root, 0, dtype=torch.int64)
+    C = int(last[-1])
+    if C == 0:
+        return vertex_component, face_component, none, none.clone()
+    first = (last - is_root).contiguous()
+    component_vertices, component_faces = torch.empty(C, device=dev, dtype=torch.int32), torch.empty(C, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_mesh_components_count(faces.data_ptr(), T, Nv, _ptr(mask), root.data_ptr(), first.data_ptr(), C,
+                                               vertex_component.data_ptr(), face_component.data_ptr(), component_vertices.data_ptr(),
+                                               component_faces.data_ptr(), _stream()), "geo4d_mesh_components_count")
+    return vertex_component, face_component, component_vertices, component_faces
+
+
+def mesh_select(vertices, faces, keep_face, rgba=None, weight=None):
+    """(vertices fp32 [V', 3], rgba uint8 [V', 4] or None, weight fp32 [V'] or None, faces int32 [T', 3], vertex_index int32 [V']): the
+    mesh of the kept faces (the rule of include/geo4d_hip.h): face t is kept iff keep_face[t] ([T] bool or uint8) is set and its indices
+    lie in [0, Nv); a vertex is kept iff a kept face names it; both keep their relative order, faces are rewritten to the new vertex rows
+    and vertex_index is the old row of every new one. A mark launch, two torch.cumsum, a gather launch; reads (V', T') back (one
+    synchronisation)."""
+    lib = _lib.load()
+    Nv = _want(vertices, "vertices", torch.float32, (None, 3)).shape[0]
+    T, keep = _mesh_faces(faces, keep_face, "keep_face")
+    assert keep is not None, "keep_face is required"
+    if rgba is not None:
+        _want(rgba, "rgba", torch.uint8, (Nv, 4))
+    if weight is not None:
+        _want(weight, "weight", torch.float32, (Nv,))
+    dev = vertices.device
+
+    def nothing():
+        return (torch.empty((0, 3), device=dev, dtype=torch.float32), None if rgba is None else torch.empty((0, 4), device=dev, dtype=torch.uint8),
+                None if weight is None else torch.empty(0, device=dev, dtype=torch.float32),
+                torch.empty((0, 3), device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32))
+    if T == 0 or Nv == 0:
+        return nothing()
+    keep_vertex, kept = torch.empty(Nv, device=dev, dtype=torch.uint8), torch.empty(T, device=dev, dtype=torch.uint8)
+    _lib.check(lib.geo4d_mesh_select_mark(faces.data_ptr(), T, Nv, keep.data_ptr(), keep_vertex.data_ptr(), kept.data_ptr(), _stream()),
+               "geo4d_mesh_select_mark")
+    last_vertex, last_face = torch.cumsum(keep_vertex, 0, dtype=torch.int64), torch.cumsum(kept, 0, dtype=torch.int64)
+    V, F = torch.stack([last_vertex[-1], last_face[-1]]).tolist()
+    if F == 0:
+        return nothing()
+    first_vertex, first_face = (last_vertex - keep_vertex).contiguous(), (last_face - kept).contiguous()
+    out = torch.empty((V, 3), device=dev, dtype=torch.float32)
+    col = None if rgba is None else torch.empty((V, 4), device=dev, dtype=torch.uint8)
+    w = None if weight is None else torch.empty(V, device=dev, dtype=torch.float32)
+    new_faces, vertex_index = torch.empty((F, 3), device=dev, dtype=torch.int32), torch.empty(V, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_mesh_select_gather(vertices.data_ptr(), _ptr(rgba), _ptr(weight), faces.data_ptr(), T, Nv, keep_vertex.data_ptr(),
+                                            kept.data_ptr(), first_vertex.data_ptr(), first_face.data_ptr(), V, F, out.data_ptr(), _ptr(col),
+                                            _ptr(w), new_faces.data_ptr(), vertex_index.data_ptr(), _stream()), "geo4d_mesh_select_gather")
+    return out, col, w, new_faces, vertex_index
+
+
 def tsdf_field(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3, capacity=None):
     """The TSDF field of a scene (the rule of include/geo4d_hip.h): (K int64 [M] sorted keys, f fp32 [M], wt fp32 [M], col uint8 [M, 4]
     or None, M, dropped); K, f, wt and col are None when no voxel was marked. Inputs as tsdf_points takes them. Mark, compact and

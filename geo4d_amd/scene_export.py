@@ -67,7 +67,8 @@ def motion_part(scene, msk, motion, **seg_kw):
 
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
                             transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
-                            motion=None, fuse_voxel=None, tsdf_voxel=None, tsdf_mesh=None):
+                            motion=None, fuse_voxel=None, tsdf_voxel=None, tsdf_mesh=None, min_component_faces=None,
+                            min_component_fraction=None):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
@@ -84,7 +85,11 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     `fuse_voxel`. `tsdf_mesh`: None (or False) likewise; a voxel size, or True for tsdf_scene's default, exports the surface of
     tsdf_scene(mesh=True) as one indexed TRIANGLES primitive (one clean surface in place of the n overlapping per-image sheets; same
     masks and thresholds, `motion` None or "static"; also left in scene.tsdf); it needs as_pointcloud=False and excludes `fuse_voxel`
-    and `tsdf_voxel`."""
+    and `tsdf_voxel`. `min_component_faces` / `min_component_fraction`: None (both: the mesh as it is); else the detached pieces of
+    the mesh that is written, the TSDF surface (then tsdf_scene filters it, and scene.tsdf holds the filtered mesh) or the per-image
+    sheets, with fewer faces than that, or than that fraction of the largest piece's, are left out
+    (geo4d_amd.mesh.remove_small_components) and the glb holds only the vertices its faces name; it needs a mesh: as_pointcloud=False
+    and neither `fuse_voxel` nor `tsdf_voxel`."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
     fuse = fuse_voxel is not None and fuse_voxel is not False
@@ -104,6 +109,13 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         raise ValueError("get_3D_model_from_scene: tsdf_mesh writes triangles: it needs as_pointcloud=False (tsdf_voxel gives the points)")
     if surface and motion == "dynamic":
         raise ValueError("get_3D_model_from_scene: tsdf_mesh with motion='dynamic': the moving part has no TSDF")
+    pieces = min_component_faces is not None or min_component_fraction is not None
+    if pieces and (as_pointcloud or fuse or tsdf):
+        raise ValueError("get_3D_model_from_scene: min_component_faces / min_component_fraction remove pieces of a mesh and points have "
+                         "no faces to connect them: they need as_pointcloud=False and neither fuse_voxel nor tsdf_voxel")
+    if pieces:
+        from .mesh import check_keep_args, remove_small_components
+        check_keep_args(min_component_faces, min_component_fraction, who="get_3D_model_from_scene")
     if scene is None:
         return None
     if mask_sky:
@@ -138,7 +150,8 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         elif surface:
             from .tsdf import tsdf_scene
             surf = tsdf_scene(scene, voxel=None if tsdf_mesh is True else tsdf_mesh, motion=motion, min_conf_thr=min_conf_thr,
-                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, mesh=True)
+                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, mesh=True, min_component_faces=min_component_faces,
+                              min_component_fraction=min_component_fraction)
             geometry = [io.mesh_geometry(surf["vertices"].cpu().numpy(), surf["vertex_rgba"].cpu().numpy(), surf["faces"].cpu().numpy())] \
                 if len(surf["faces"]) else []
         elif as_pointcloud:
@@ -149,7 +162,11 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
             pts, rgba, _ = ops.scene_points(pts3d, imgs, None)          # every vertex, as cat_meshes keeps them
             faces, count = ops.scene_mesh_faces(msk, n, H, W, pts3d.device)
             c = int(count.item())
-            geometry = [io.mesh_geometry(pts.cpu().numpy(), rgba.cpu().numpy(), faces[:c].cpu().numpy())] if c else []
+            faces = faces[:c]
+            if pieces and c:
+                kept = remove_small_components(pts, faces, min_faces=min_component_faces, min_fraction=min_component_fraction, rgba=rgba)
+                pts, rgba, faces, c = kept["vertices"], kept["rgba"], kept["faces"], len(kept["faces"])
+            geometry = [io.mesh_geometry(pts.cpu().numpy(), rgba.cpu().numpy(), faces.cpu().numpy())] if c else []
     outfile = os.path.join(outdir, (save_name or "scene") + ".glb")
     if not silent:
         print("(exporting 3D scene to", outfile, ")")
@@ -173,7 +190,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     <seq>_static_tsdf.glb, the surface points of the static part's TSDF (get_3D_model_from_scene(motion="static", tsdf_voxel=...)), and
     nothing else. `tsdf_mesh_static`: a voxel size, or True for tsdf_scene's default, likewise also writes <seq>_static_tsdf_mesh.glb,
     the static part's TSDF surface as a triangle mesh (get_3D_model_from_scene(motion="static", as_pointcloud=False, tsdf_mesh=...)),
-    and nothing else. Returns the directory."""
+    and nothing else; `min_component_faces` / `min_component_fraction` among `glb_kw` filter that mesh alone (see
+    get_3D_model_from_scene): the other files are point clouds unless `glb_kw` says otherwise, and are written as without them. Returns
+    the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -181,6 +200,9 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
         scene.imgs = rgb_frames(imgs, scene.n, scene.H, scene.W).to(scene.dev)
     kw = dict(silent=True, as_pointcloud=True, mask_sky=False, clean_depth=False, transparent_cams=False, cam_size=0.01, is_msk=False)
     kw.update(glb_kw)
+    pieces = {k: kw.pop(k) for k in ("min_component_faces", "min_component_fraction") if k in kw}   # of the meshes only
+    if not kw["as_pointcloud"]:
+        kw.update(pieces)
     is_msk, thr_init = kw["is_msk"], kw.get("thr_for_init_conf", True)
     silent = kw.pop("silent")
     get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
@@ -198,7 +220,7 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
                                 **dict(kw, motion="static", as_pointcloud=True, tsdf_voxel=tsdf_static))
     if tsdf_mesh_static is not None and tsdf_mesh_static is not False:
         get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf_mesh",
-                                **dict(kw, motion="static", as_pointcloud=False, tsdf_mesh=tsdf_mesh_static))
+                                **dict(kw, motion="static", as_pointcloud=False, tsdf_mesh=tsdf_mesh_static, **pieces))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())

@@ -20,7 +20,8 @@ tried them on real predictions.
 (csrc/tsdf_mesh.hip, restated in tests/tsdf_mesh_restatement.py): one vertex per cell of eight live voxels the surface passes through,
 at the mean of the cell's edge crossings, and two triangles per sign change between two neighbouring voxels, front faces toward the
 cameras; ``get_3D_model_from_scene(tsdf_mesh=...)`` and ``save_scene(tsdf_mesh_static=...)`` write it as a glb. On the synthetic scene
-at 2 % depth noise its vertices lie 0.017 RMS from the wall (the points: 0.025).
+at 2 % depth noise its vertices lie 0.017 RMS from the wall (the points: 0.025). ``min_component_faces`` / ``min_component_fraction``
+drop the mesh's small detached pieces, the debris a TSDF of noisy depth leaves in front of and behind the surface (geo4d_amd/mesh.py).
 
 Limits: no normals; the mesh is neither simplified nor smoothed, and where a grid face has four sign changes a mesh edge is shared by
 four triangles (a property of surface nets); one resolution; cell indices must stay below 2^20 in magnitude (samples beyond are refused,
@@ -33,6 +34,7 @@ import math
 import torch
 
 from . import _lib, ops
+from .mesh import check_keep_args, remove_small_components
 from .render import _rgba, _scene_cameras, _views
 
 MOTION = (None, "static")
@@ -77,20 +79,32 @@ def tsdf_points(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, vo
 
 
 @torch.no_grad()
-def tsdf_mesh(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None):
+def tsdf_mesh(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, voxel, trunc=4, min_weight=4.0, near=1e-3, capacity=None,
+              min_component_faces=None, min_component_fraction=None):
     """dict(vertices fp32 [V, 3], rgba uint8 [V, 4] or None, weight fp32 [V], faces int32 [T, 3], voxels, dropped, overflow, voxel): the
     surface of the TSDF as one indexed triangle mesh, on the device: naive surface nets (ops.tsdf_mesh_extract), about one vertex per
     cell the surface passes through, ordered by cell (cx, cy, cz); two triangles per sign change between two neighbouring voxels whose
     four surrounding cells are complete, ordered by voxel and axis, front faces toward the cameras. Inputs, checks and errors are
     tsdf_points'. `weight` of a vertex is the smallest weight of its cell's eight voxels, its colour that of the voxel nearest the
-    surface."""
-    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=False, mesh=True)
+    surface.
+
+    `min_component_faces` / `min_component_fraction` (None: no filter, the dict is what it was): the detached pieces of the extracted mesh
+    with fewer faces than that, or than that fraction of the largest piece's, are removed (mesh.remove_small_components); vertices, faces,
+    colours and weights are the filtered ones, still in their order, and the dict gains `components`, `kept_components` and
+    `removed_faces`."""
+    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=False, mesh=True,
+                 min_component_faces=min_component_faces, min_component_fraction=min_component_fraction)
 
 
-def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, *, points, mesh):
+def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, *, points, mesh,
+          min_component_faces=None, min_component_fraction=None):
     """The checks of tsdf_points, one field (ops.tsdf_field), and what is asked for of its surface: the points (`points`, rgba,
-    weight), the mesh, or both (then the mesh's colours and weights are `vertex_rgba`, `vertex_weight`)."""
+    weight), the mesh, or both (then the mesh's colours and weights are `vertex_rgba`, `vertex_weight`). The mesh goes through
+    mesh.remove_small_components when either component argument is given."""
     v = check_tsdf_args(voxel, trunc, min_weight, near, capacity)
+    filtering = min_component_faces is not None or min_component_fraction is not None
+    if filtering:
+        check_keep_args(min_component_faces, min_component_fraction, who="tsdf_mesh")
     for t, what in ((pts3d, "pts3d"), (depth, "depth")):
         if not t.is_cuda:
             raise _lib.Geo4DNativeError(f"tsdf_points: `{what}` lives on {t.device}; the TSDF runs only on a HIP device (there is no CPU "
@@ -123,15 +137,21 @@ def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_wei
     out.update(voxels=voxels, dropped=0, overflow=0, voxel=v)
     if mesh:
         vertices, vcol, vw, faces = ops.tsdf_mesh_extract(Kv, f, wt, col, voxel=v, min_weight=float(min_weight))
+        if filtering:
+            kept = remove_small_components(vertices, faces, min_faces=min_component_faces, min_fraction=min_component_fraction, rgba=vcol,
+                                           weight=vw)
+            vertices, vcol, vw, faces = kept["vertices"], kept["rgba"], kept["weight"], kept["faces"]
+            out.update(components=kept["components"], kept_components=kept["kept_components"], removed_faces=kept["removed_faces"])
         out.update(vertices=vertices, faces=faces, **(dict(vertex_rgba=vcol, vertex_weight=vw) if points else dict(rgba=vcol, weight=vw)))
     return out
 
 
 @torch.no_grad()
 def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_init_conf=True, is_msk=True, use_conf=False, trunc=4,
-               min_weight=4.0, near=1e-3, capacity=None, mesh=False):
+               min_weight=4.0, near=1e-3, capacity=None, mesh=False, min_component_faces=None, min_component_fraction=None):
     """tsdf_points on a GroupAligner; the result (see tsdf_points) is also stored as scene.tsdf. `mesh=True`: the dict additionally holds
-    the surface as a triangle mesh (see tsdf_mesh) from the same field: `vertices`, `faces`, `vertex_rgba`, `vertex_weight`.
+    the surface as a triangle mesh (see tsdf_mesh) from the same field: `vertices`, `faces`, `vertex_rgba`, `vertex_weight`, without its
+    small detached pieces when `min_component_faces` / `min_component_fraction` say so (see tsdf_mesh; with `mesh=False` either raises).
 
     Points, colours and masks are taken exactly as fusion.fuse_scene and get_3D_model_from_scene take them: scene.get_pts3d(),
     scene.get_depthmaps(), scene.imgs (None: no colours) and scene.get_masks() with `min_conf_thr` / `thr_for_init_conf` set on the scene
@@ -144,6 +164,10 @@ def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_in
     if motion not in MOTION:
         raise ValueError(f"tsdf_scene: motion must be one of {MOTION}, got {motion!r} (the moving part has no TSDF)")
     check_tsdf_args(1.0 if voxel is None else voxel, trunc, min_weight, near, capacity)
+    if min_component_faces is not None or min_component_fraction is not None:
+        if not mesh:
+            raise ValueError("tsdf_scene: min_component_faces / min_component_fraction filter the mesh; pass mesh=True")
+        check_keep_args(min_component_faces, min_component_fraction, who="tsdf_scene")
     scene.require_all_depthmaps("tsdf_scene")
     pts3d = scene.get_pts3d().detach().contiguous()
     depth = scene.get_depthmaps().detach().contiguous()
@@ -159,5 +183,6 @@ def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_in
     c2w, K = _scene_cameras(scene)
     rgb = None if scene.imgs is None else scene.imgs.to(scene.dev).float()
     scene.tsdf = _tsdf(pts3d, depth, msk, c2w, K, rgb, scene.get_conf().detach() if use_conf else None, voxel, trunc, min_weight, near,
-                       capacity, points=True, mesh=bool(mesh))
+                       capacity, points=True, mesh=bool(mesh), min_component_faces=min_component_faces,
+                       min_component_fraction=min_component_fraction)
     return scene.tsdf

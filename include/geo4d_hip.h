@@ -702,6 +702,51 @@ int geo4d_tsdf_mesh_vertices(const long* keys, long M, const float* f, const flo
 int geo4d_tsdf_mesh_faces(const long* keys, long M, const float* f, const unsigned char* complete, const int* counts, const long* first_quad,
                           const long* first_vertex, long Q, long V, int* faces_out, void* stream);
 
+/* The connected pieces of an indexed triangle mesh, and the mesh of a chosen set of its faces (geo4d_amd/csrc/mesh_components.hip,
+ * geo4d_amd/mesh.py): what removes the detached debris a TSDF of noisy depth leaves. The reference has no such step; the rule is this
+ * project's own, restated in numpy in tests/mesh_components_restatement.py. Integer arithmetic throughout: every output is a function of
+ * the inputs alone; permuting the faces permutes face_component and leaves the other outputs equal.
+ *   Inputs: faces int32 [T][3], the vertex count Nv, face_mask u8 [T] (NULL: every face).
+ *   Valid: face t is valid iff face_mask[t] != 0 (or there is no mask) and its three indices lie in [0, Nv), which is decided before
+ *     anything is read or written through them. A valid face may repeat an index: (a, a, b) connects a and b, (a, a, a) touches a alone.
+ *   Connected: two vertices are connected iff a chain of valid faces links them, consecutive faces sharing at least one vertex (vertex
+ *     connectivity, not edge connectivity).
+ *   Labels: a vertex that no valid face names is untouched: vertex_component = -1. Every other vertex belongs to exactly one component;
+ *     the root of a component is its smallest vertex index; components are numbered 0 .. C - 1 in ascending order of root.
+ *     face_component[t] is the component of the face's vertices, -1 for a face that is not valid. component_vertices int32 [C] and
+ *     component_faces int32 [C] count the touched vertices and the valid faces. A component's size is its face count.
+ *   Selection: given keep_face u8 [T], face t is kept iff keep_face[t] != 0 and its indices lie in [0, Nv); a vertex is kept iff a kept
+ *     face names it. Kept vertices and kept faces keep their relative order; faces are rewritten to the new vertex rows; vertex_index
+ *     int32 [V'] is the old row of every new one.
+ *   geo4d_mesh_components_hook: touched u8 [Nv] := 0, parent int32 [Nv] := identity, then one thread per face joins (i0, i1) and (i1, i2)
+ *     in a lock-free union-find (geo4d_amd/csrc/union_find.h: parent[x] <= x always, the larger root is linked under the smaller by a
+ *     compare-and-swap on a root, paths are halved by atomic minimum; every loop turn finishes or moves to a strictly smaller index and
+ *     no thread waits for another) and stores touched = 1 for its vertices. geo4d_mesh_components_flatten, after it: root_out [Nv] = the
+ *     smallest index of v's component, -1 for an untouched v; is_root_out u8 [Nv] = (root_out[v] == v). The caller forms first_component
+ *     = the exclusive prefix sum of is_root_out (int64) and C = its sum. geo4d_mesh_components_count: component_* := 0, then
+ *     vertex_component [Nv], face_component [T] (one writer per row) and the two counts (integer atomic adds).
+ *     geo4d_mesh_select_mark: keep_vertex u8 [Nv] := 0, then 1 for the vertices of kept faces; kept_face u8 [T] = face t is kept. The
+ *     caller forms first_vertex, first_face = the exclusive prefix sums of the two (int64) and V', T' = their sums.
+ *     geo4d_mesh_select_gather writes vertices_out fp32 [V'][3], rgba_out u8 [V'][4] and weight_out fp32 [V'] (each NULL: not wanted),
+ *     faces_out int32 [T'][3] and vertex_index int32 [V']; one writer per row; a row offset outside the output writes nothing.
+ *   T == 0 or Nv == 0 (and C == 0, V' == 0 or T' == 0) launch nothing: every label is then -1 and every output empty, which is the
+ *     caller's to write. Limits: T < 2^31, Nv < 2^31; vertex connectivity only; no areas, no bounding boxes.
+ *   Null pointers (rgba, weight, their outputs and face_mask excepted), T or Nv < 0 or >= 2^31, C > Nv, V' > Nv and T' > T return
+ *   -EINVAL before any device work. */
+int geo4d_mesh_components_hook(const int* faces, long T, long Nv, const unsigned char* face_mask, int* parent, unsigned char* touched,
+                               void* stream);
+int geo4d_mesh_components_flatten(const int* parent, const unsigned char* touched, long Nv, int* root_out, unsigned char* is_root_out,
+                                  void* stream);
+int geo4d_mesh_components_count(const int* faces, long T, long Nv, const unsigned char* face_mask, const int* root,
+                                const long* first_component, long C, int* vertex_component, int* face_component, int* component_vertices,
+                                int* component_faces, void* stream);
+int geo4d_mesh_select_mark(const int* faces, long T, long Nv, const unsigned char* keep_face, unsigned char* keep_vertex,
+                           unsigned char* kept_face, void* stream);
+int geo4d_mesh_select_gather(const float* vertices, const unsigned char* rgba, const float* weight, const int* faces, long T, long Nv,
+                             const unsigned char* keep_vertex, const unsigned char* kept_face, const long* first_vertex,
+                             const long* first_face, long V, long F, float* vertices_out, unsigned char* rgba_out, float* weight_out,
+                             int* faces_out, int* vertex_index, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
