@@ -254,6 +254,15 @@ SIGNATURES = {
     "geo4d_mesh_select_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_adjacency_count": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_adjacency_fill": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "geo4d_mesh_adjacency_sort": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "geo4d_mesh_boundary": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_smooth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                         C.c_float, C.c_void_p, C.c_void_p]),
+    "geo4d_mesh_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                            C.c_void_p]),
     "geo4d_focal_shift_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "geo4d_focal_shift": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -288,7 +288,8 @@ OPENGL = np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]], dt
 
 def _glb_bytes(meshes, transform):
     """Binary glTF 2.0 with one node per primitive. meshes: list of dict(mode, positions f32 [n, 3], colors u8 [n, 4] or None,
-    indices [f, 3] or None: uint32 vertex ids of an indexed primitive).
+    indices [f, 3] or None: uint32 vertex ids of an indexed primitive, normals f32 [n, 3] or None / absent: unit vertex normals, written
+    as NORMAL).
     `transform` (4x4) is applied to every node, as trimesh.Scene.apply_transform does."""
     import json
     import struct
@@ -310,6 +311,11 @@ def _glb_bytes(meshes, transform):
     for m in meshes:
         pos = np.ascontiguousarray(m["positions"], dtype=np.float32)
         attrs = {"POSITION": add(pos, 34962, 5126, "VEC3", minmax=True)}
+        if m.get("normals") is not None:
+            nrm = np.ascontiguousarray(m["normals"], dtype=np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError(f"_glb_bytes: normals must be [n, 3] like positions {pos.shape}, got {nrm.shape}")
+            attrs["NORMAL"] = add(nrm, 34962, 5126, "VEC3")
         if m.get("colors") is not None:
             attrs["COLOR_0"] = add(np.ascontiguousarray(m["colors"], dtype=np.uint8), 34962, 5121, "VEC4", normalized=True)
         prim = {"attributes": attrs, "mode": m["mode"]}
@@ -360,13 +366,17 @@ def save_glb(path, imgs, pts3d, masks, focals, cams2world, cam_size=0.05, show_c
                            cam_color=cam_color)
 
 
-def mesh_geometry(positions, colors, faces):
+def mesh_geometry(positions, colors, faces, normals=None):
     """The indexed TRIANGLES primitive of the mesh export (convert_scene_output_to_glb with as_pointcloud=False): POSITION = every pixel
     of every image as cat_meshes keeps them (f32 [n H W, 3]), COLOR_0 = each vertex's own pixel colour (RGBA u8 [n H W, 4]), uint32
     indices = the kept faces [f, 3]. The reference hands trimesh per-FACE colours (the quad's top-left pixel for its first two faces,
     the bottom-right one for the other two); glTF can attach colours to faces only by un-merging the vertices, so this writer keeps
-    one vertex per pixel and colours by vertex instead, and does not reproduce trimesh's exact file layout."""
-    return dict(mode=4, positions=positions, colors=colors, indices=faces)
+    one vertex per pixel and colours by vertex instead, and does not reproduce trimesh's exact file layout. `normals` (f32 [n, 3] unit
+    vertex normals; None: none, and the primitive is what it was) become the NORMAL attribute."""
+    geometry = dict(mode=4, positions=positions, colors=colors, indices=faces)
+    if normals is not None:
+        geometry["normals"] = normals
+    return geometry
 
 
 def write_scene_glb(path, geometry, focals, cams2world, imsize, cam_size=0.05, show_cam=True, cam_color=None):

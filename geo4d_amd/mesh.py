@@ -1,4 +1,5 @@
-"""Clean-up of indexed triangle meshes on the HIP device (csrc/mesh_components.hip): label the connected pieces, drop the small ones.
+"""Clean-up of indexed triangle meshes on the HIP device: label the connected pieces and drop the small ones (csrc/mesh_components.hip);
+smooth the vertices and give them normals from one corner table (csrc/mesh_smooth.hip).
 
 Every TSDF of noisy depth leaves debris: small detached patches in front of and behind the real surface. ``mesh_components`` labels
 the pieces of any mesh (a lock-free union-find, one thread per face), ``remove_small_components`` keeps the pieces that are large
@@ -11,6 +12,17 @@ function of the mesh alone.
 A piece's size is its number of faces. On a surface-nets mesh every triangle is about half a voxel face, so the count is the area in
 voxel units. Limits: vertex connectivity (two pieces touching in one vertex are one piece); int32 indices; no areas, bounding boxes or
 other float measures; nobody has tried the thresholds on real predictions.
+
+``mesh_adjacency`` builds the corner table: for each vertex, sorted, the corners of the faces around it, and which vertices lie on the
+mesh's boundary. ``smooth_mesh`` runs Taubin (lambda | mu) smoothing on it, which takes the voxel-scale staircase out of a surface-nets
+mesh and all but keeps its size (a noisy unit sphere: 0.8 % after 10 iterations, where lam alone loses 20 %), and
+``vertex_normals`` gives area-weighted unit normals. ``tsdf_mesh``, ``tsdf_scene(mesh=True)``,
+``get_3D_model_from_scene(tsdf_mesh=...)``, ``save_scene`` and ``render_scene(static_mesh=...)`` take ``smooth_iterations`` /
+``smooth_pin_boundary`` (and, but for the renderer, ``normals``). The rule is stated in include/geo4d_hip.h and restated in numpy in
+tests/mesh_smooth_restatement.py. Every float is gathered per vertex in the table's order, so the results are bitwise reproducible;
+they are functions of the mesh as given: another face order sums in another order and may change last bits. Limits: time is linear in
+the largest valence; a normal is zero where the sum of its faces' cross products vanishes; int32 indices and 3 T < 2^31; uniform
+weights per face (no cotangent weights, no feature preservation); nobody has tried the defaults on real predictions.
 """
 from fractions import Fraction
 from numbers import Integral, Real
@@ -79,3 +91,77 @@ def remove_small_components(vertices, faces, *, min_faces=None, min_fraction=Non
     v, col, w, f, vertex_index = ops.mesh_select(vertices, faces, keep_face, rgba, weight)
     return dict(vertices=v, rgba=col, weight=w, faces=f, vertex_index=vertex_index, components=len(keep), kept_components=sum(keep),
                 removed_faces=int(faces.shape[0] - f.shape[0]), removed_vertices=int(vertices.shape[0] - v.shape[0]))
+
+
+def check_smooth_args(iterations=0, lam=0.5, mu=-0.53, who="smooth_mesh"):
+    """ValueError for iterations not an integer >= 0, lam outside (0, 1] or mu outside [-1, 0]."""
+    if isinstance(iterations, bool) or not isinstance(iterations, Integral) or iterations < 0:
+        raise ValueError(f"{who}: iterations must be an integer >= 0, got {iterations!r}")
+    if isinstance(lam, bool) or not isinstance(lam, Real) or not 0 < lam <= 1:
+        raise ValueError(f"{who}: lam must lie in (0, 1], got {lam!r}")
+    if isinstance(mu, bool) or not isinstance(mu, Real) or not -1 <= mu <= 0:
+        raise ValueError(f"{who}: mu must lie in [-1, 0], got {mu!r}")
+
+
+def _table(adjacency, faces, n_vertices, face_mask, who):
+    """The corner table to work on: `adjacency` (a mesh_adjacency dict, whose shapes must fit the mesh) or a fresh one."""
+    if adjacency is None:
+        return mesh_adjacency(faces, n_vertices, face_mask)
+    try:
+        offsets, corners, boundary = adjacency["offsets"], adjacency["corners"], adjacency["boundary"]
+        fits = (tuple(offsets.shape) == (n_vertices + 1,) and tuple(boundary.shape) == (n_vertices,) and corners.dim() == 1
+                and corners.shape[0] == adjacency["entries"] <= 3 * faces.shape[0])
+    except (KeyError, TypeError, AttributeError):
+        fits = False
+    if not fits:
+        raise ValueError(f"{who}: adjacency does not fit a mesh of {n_vertices} vertices and {faces.shape[0]} faces; pass what "
+                         "mesh_adjacency(faces, n_vertices) returns")
+    return adjacency
+
+
+@torch.no_grad()
+def mesh_adjacency(faces, n_vertices, face_mask=None):
+    """dict(offsets int32 [Nv + 1], corners int32 [E], boundary bool [Nv], entries = E) of the mesh faces int32 [T, 3] over n_vertices
+    vertices on the HIP device (ops.mesh_adjacency): the corner table. Entry e = 3 t + k stands for corner k of face t and lies in the row
+    of vertex faces[t][k]; row v is corners[offsets[v]:offsets[v + 1]], ascending, so the table is a function of the mesh alone. A face
+    that is masked out (`face_mask` [T] bool) or has an index outside [0, n_vertices) has no entries. `boundary` marks the vertices with a
+    neighbour that only one face joins them to. Moving vertices leaves the table valid: smooth_mesh and vertex_normals take it as
+    `adjacency`."""
+    offsets, corners, boundary = ops.mesh_adjacency(faces, n_vertices, face_mask)
+    return dict(offsets=offsets, corners=corners, boundary=boundary.view(torch.bool), entries=int(corners.shape[0]))
+
+
+@torch.no_grad()
+def vertex_normals(vertices, faces, *, face_mask=None, adjacency=None):
+    """fp32 [Nv, 3]: area-weighted unit vertex normals of the mesh vertices fp32 [Nv, 3], faces int32 [T, 3] on the HIP device
+    (ops.mesh_vertex_normals): the sum of the faces' cross products (p1 - p0) x (p2 - p0) round the vertex, whose lengths are twice
+    the areas, normalised; (0, 0, 0) where the sum has no finite positive length, as for a vertex no valid face names. `adjacency`: a
+    mesh_adjacency dict of this mesh to reuse (then `face_mask` is not looked at)."""
+    table = _table(adjacency, faces, vertices.shape[0], face_mask, "vertex_normals")
+    return ops.mesh_vertex_normals(vertices, faces, table["offsets"], table["corners"])
+
+
+@torch.no_grad()
+def smooth_mesh(vertices, faces, *, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, face_mask=None, adjacency=None):
+    """fp32 [Nv, 3]: the vertices after `iterations` iterations of Taubin smoothing on the HIP device (ops.mesh_smooth_step). Each
+    iteration moves every vertex by `lam` times the way to the mean of its neighbours and then, unless `mu` is 0, by `mu` (negative:
+    away from it), which undoes the shrinking of the first step. The neighbours of v are the other two vertices of every face round
+    v, so the weights count faces: a neighbour seen from two faces counts twice, and the mean is that of the opposite edges' midpoints;
+    nothing is de-duplicated. `pin_boundary` keeps the boundary vertices (mesh_adjacency) where they are, bit for bit, as every vertex
+    without neighbours stays; non-finite coordinates spread as IEEE arithmetic says. Every step reads one buffer and writes another; the
+    input is never written. `iterations=0` launches nothing and returns `vertices` itself. `adjacency`: a mesh_adjacency dict of this
+    mesh to reuse (then `face_mask` is not looked at): a step moves no vertex between faces, so the table outlives the smoothing."""
+    check_smooth_args(iterations, lam, mu)
+    if adjacency is not None:
+        _table(adjacency, faces, vertices.shape[0], face_mask, "smooth_mesh")
+    if iterations == 0:
+        return vertices
+    table = _table(adjacency, faces, vertices.shape[0], face_mask, "smooth_mesh")
+    pinned = table["boundary"] if pin_boundary else None
+    p, spare = vertices, [torch.empty_like(vertices), torch.empty_like(vertices)]
+    for _ in range(iterations):
+        for s in (lam, mu):
+            if s != 0:
+                p = ops.mesh_smooth_step(p, faces, table["offsets"], table["corners"], s, pinned, out=spare[0])
+                spare.reverse()
+    return p

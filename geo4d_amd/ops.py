@@ -1667,6 +1667,94 @@ def mesh_select(vertices, faces, keep_face, rgba=None, weight=None):
     return out, col, w, new_faces, vertex_index
 
 
+# Rows of the corner table longer than this are sorted, and searched for boundary neighbours, by a whole wave instead of one thread
+# (csrc/mesh_smooth.hip). Both paths give the same table; the value only decides the time. tools/mesh_smooth_bench.py sweeps it: on the
+# TSDF bench mesh (rows of 6 on average, 18 at most) the table takes 0.44 / 0.42 / 0.30 / 0.28 / 0.32 ms at 0 / 4 / 8 / 16 / 32 and above,
+# and with a row of 4000 entries added 119 ms at every value up to 128 against 559 ms by one thread (profiles/mesh_smooth.md).
+MESH_LONG_ROW = 16
+
+
+def _mesh_table(faces, offsets, corners, Nv):
+    """(T, E) of faces int32 [T, 3] with the corner table offsets int32 [Nv + 1], corners int32 [E] on the HIP device."""
+    T = _want(faces, "faces", torch.int32, (None, 3)).shape[0]
+    _want(offsets, "offsets", torch.int32, (Nv + 1,))
+    E = _want(corners, "corners", torch.int32, (None,)).shape[0]
+    assert E <= 3 * T, (E, T)
+    return T, E
+
+
+def mesh_adjacency(faces, n_vertices, face_mask=None, *, long_row=None):
+    """(offsets int32 [Nv + 1], corners int32 [E], boundary uint8 [Nv]): the corner table of the mesh faces int32 [T, 3] over
+    `n_vertices` vertices and its boundary vertices (the rule of include/geo4d_hip.h). An entry e = 3 t + k stands for corner k of the
+    valid face t (`face_mask` [T] bool or uint8 lets it through, indices in [0, Nv)) and lies in the row of vertex faces[t][k]; row v is
+    corners[offsets[v]:offsets[v + 1]], ascending. boundary[v] = 1 iff some neighbour stands exactly once in v's neighbour list. Rows
+    longer than `long_row` (None: MESH_LONG_ROW) are handled by a wave instead of a thread; the result is the same. A count launch, one
+    torch.cumsum, a fill, a sort and a boundary launch; reads E back (one synchronisation)."""
+    lib = _lib.load()
+    Nv = int(n_vertices)
+    assert 0 <= Nv < 1 << 31, n_vertices
+    long_row = MESH_LONG_ROW if long_row is None else int(long_row)
+    assert 0 <= long_row < 1 << 31, long_row
+    T, mask = _mesh_faces(faces, face_mask, "face_mask")
+    dev = faces.device
+    offsets = torch.zeros(Nv + 1, device=dev, dtype=torch.int32)
+    boundary = torch.zeros(Nv, device=dev, dtype=torch.uint8)
+    none = torch.empty(0, device=dev, dtype=torch.int32)
+    if T == 0 or Nv == 0:
+        return offsets, none, boundary
+    degree = torch.zeros(Nv, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_mesh_adjacency_count(faces.data_ptr(), T, Nv, _ptr(mask), degree.data_ptr(), _stream()), "geo4d_mesh_adjacency_count")
+    torch.cumsum(degree, 0, dtype=torch.int32, out=offsets[1:])
+    E = int(offsets[-1])
+    if E == 0:
+        return offsets, none, boundary
+    cursor = degree.zero_()
+    unsorted, corners = torch.empty(E, device=dev, dtype=torch.int32), torch.empty(E, device=dev, dtype=torch.int32)
+    _lib.check(lib.geo4d_mesh_adjacency_fill(faces.data_ptr(), T, Nv, _ptr(mask), offsets.data_ptr(), E, cursor.data_ptr(),
+                                             unsorted.data_ptr(), _stream()), "geo4d_mesh_adjacency_fill")
+    _lib.check(lib.geo4d_mesh_adjacency_sort(offsets.data_ptr(), T, Nv, E, unsorted.data_ptr(), corners.data_ptr(), long_row, _stream()),
+               "geo4d_mesh_adjacency_sort")
+    _lib.check(lib.geo4d_mesh_boundary(faces.data_ptr(), T, Nv, offsets.data_ptr(), corners.data_ptr(), E, long_row, boundary.data_ptr(),
+                                       _stream()), "geo4d_mesh_boundary")
+    return offsets, corners, boundary
+
+
+def mesh_smooth_step(vertices, faces, offsets, corners, s, pinned=None, *, out=None):
+    """fp32 [Nv, 3]: one Jacobi smoothing step with factor `s` (the rule of include/geo4d_hip.h): every vertex moves by s times the way
+    to the mean of its neighbour list (mesh_adjacency's table; a neighbour seen from two faces counts twice); a vertex without
+    neighbours, or with pinned[v] != 0 (`pinned` [Nv] bool or uint8), keeps its bits. One launch into `out` (None: a new tensor),
+    which is never `vertices`."""
+    lib = _lib.load()
+    Nv = _want(vertices, "vertices", torch.float32, (None, 3)).shape[0]
+    T, E = _mesh_table(faces, offsets, corners, Nv)
+    if pinned is not None:
+        assert tuple(_dev(pinned, "pinned").shape) == (Nv,) and pinned.dtype in (torch.bool, torch.uint8), (pinned.dtype, tuple(pinned.shape))
+        pinned = pinned.contiguous().view(torch.uint8)
+    if out is None:
+        out = torch.empty_like(vertices)
+    assert _want(out, "out", torch.float32, (Nv, 3)).data_ptr() != vertices.data_ptr() or Nv == 0, "a step is never in place"
+    if T == 0 or Nv == 0:
+        return out.copy_(vertices)
+    _lib.check(lib.geo4d_mesh_smooth_step(vertices.data_ptr(), faces.data_ptr(), T, Nv, offsets.data_ptr(), corners.data_ptr(), E,
+                                          _ptr(pinned), float(s), out.data_ptr(), _stream()), "geo4d_mesh_smooth_step")
+    return out
+
+
+def mesh_vertex_normals(vertices, faces, offsets, corners):
+    """fp32 [Nv, 3]: area-weighted unit vertex normals (the rule of include/geo4d_hip.h): the sum of the cross products (p1 - p0) x
+    (p2 - p0) of the faces in the vertex's row of mesh_adjacency's table, in the row's order, divided by its length; (0, 0, 0) where
+    that length is not positive and finite (a vertex no valid face names among them). One launch."""
+    lib = _lib.load()
+    Nv = _want(vertices, "vertices", torch.float32, (None, 3)).shape[0]
+    T, E = _mesh_table(faces, offsets, corners, Nv)
+    if T == 0 or Nv == 0:
+        return torch.zeros_like(vertices)
+    out = torch.empty_like(vertices)
+    _lib.check(lib.geo4d_mesh_vertex_normals(vertices.data_ptr(), faces.data_ptr(), T, Nv, offsets.data_ptr(), corners.data_ptr(), E,
+                                             out.data_ptr(), _stream()), "geo4d_mesh_vertex_normals")
+    return out
+
+
 def tsdf_field(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3, capacity=None):
     """The TSDF field of a scene (the rule of include/geo4d_hip.h): (K int64 [M] sorted keys, f fp32 [M], wt fp32 [M], col uint8 [M, 4]
     or None, M, dropped); K, f, wt and col are None when no voxel was marked. Inputs as tsdf_points takes them. Mark, compact and

@@ -211,7 +211,7 @@ def orbit_cameras(center, radius, n, elevation=0.0, up=(0.0, -1.0, 0.0)):
 def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=True, thr_for_init_conf=True, point_size=0, trail=0,
                  path=None, sources=None, n_views=24, elevation=0.3, orbit_radius=None, near=1e-3, max_size=9, fill=0,
                  background=(1, 1, 1), persist_static=False, static_mesh=None, shade=0.0, cull_back=False, min_component_faces=None,
-                 min_component_fraction=None):
+                 min_component_fraction=None, smooth_iterations=None, smooth_pin_boundary=True):
     """Frames of a GroupAligner: dict(rgb, depth, index) as render_points returns them, one view per frame.
 
     Points, colours and masks are those get_3D_model_from_scene exports (get_pts3d, scene.imgs, get_masks with `min_conf_thr` /
@@ -231,13 +231,17 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
     `cull_back` as render_mesh takes them. No static point is drawn, the moving points are chosen as persist_static chooses them, and
     the dict also holds `face`, the winning triangle's row in scene.tsdf["faces"] or -1. Not together with persist_static.
     `min_component_faces` / `min_component_fraction` go to tsdf_scene when this call builds the mesh (its small detached pieces are then
-    not drawn, see geo4d_amd.tsdf.tsdf_mesh); a mesh reused from scene.tsdf is drawn as found, filtered or not. They need static_mesh."""
+    not drawn, see geo4d_amd.tsdf.tsdf_mesh); a mesh reused from scene.tsdf is drawn as found, filtered or not. They need static_mesh.
+    `smooth_iterations` / `smooth_pin_boundary` go to tsdf_scene likewise (Taubin smoothing of the mesh's vertices; scene.tsdf then holds
+    the smoothed mesh) and need static_mesh; the shading stays flat, per triangle."""
     if mode not in MODES:
         raise ValueError(f"render_scene: mode must be one of {MODES}, got {mode!r}")
     if static_mesh is not None and static_mesh is not False and persist_static:
         raise ValueError("render_scene: static_mesh draws the static part as a mesh and persist_static as points; choose one")
     if (min_component_faces is not None or min_component_fraction is not None) and (static_mesh is None or static_mesh is False):
         raise ValueError("render_scene: min_component_faces / min_component_fraction filter the static mesh; pass static_mesh")
+    if (smooth_iterations is not None or smooth_pin_boundary is not True) and (static_mesh is None or static_mesh is False):
+        raise ValueError("render_scene: smooth_iterations / smooth_pin_boundary smooth the static mesh; pass static_mesh")
     if scene.imgs is None:
         raise ValueError("render_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs [n, H, W, 3] in [0, 1]")
     scene.require_all_depthmaps("render_scene")
@@ -286,7 +290,8 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
             from .tsdf import tsdf_scene
             tsdf = tsdf_scene(scene, voxel, motion="static", mesh=True, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf,
                               is_msk=is_msk, near=near, min_component_faces=min_component_faces,
-                              min_component_fraction=min_component_fraction)
+                              min_component_fraction=min_component_fraction, smooth_iterations=smooth_iterations,
+                              smooth_pin_boundary=smooth_pin_boundary)
         dyn = getattr(scene, "dynamic_masks", None)
         if dyn is None:
             from .motion import segment_motion

@@ -68,7 +68,7 @@ def motion_part(scene, msk, motion, **seg_kw):
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
                             transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
                             motion=None, fuse_voxel=None, tsdf_voxel=None, tsdf_mesh=None, min_component_faces=None,
-                            min_component_fraction=None):
+                            min_component_fraction=None, smooth_iterations=None, smooth_pin_boundary=True, normals=False):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
@@ -89,7 +89,10 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     the mesh that is written, the TSDF surface (then tsdf_scene filters it, and scene.tsdf holds the filtered mesh) or the per-image
     sheets, with fewer faces than that, or than that fraction of the largest piece's, are left out
     (geo4d_amd.mesh.remove_small_components) and the glb holds only the vertices its faces name; it needs a mesh: as_pointcloud=False
-    and neither `fuse_voxel` nor `tsdf_voxel`."""
+    and neither `fuse_voxel` nor `tsdf_voxel`. `smooth_iterations` / `smooth_pin_boundary` / `normals`: for the TSDF surface alone
+    (`tsdf_mesh`): tsdf_scene smooths its mesh by that many Taubin iterations (scene.tsdf then holds the smoothed vertices) and, with
+    `normals=True`, the primitive carries the area-weighted unit vertex normals as NORMAL, so that a viewer shades it smoothly. Without
+    `tsdf_mesh` they raise: points have no faces, and the per-image sheets keep unreferenced vertices, whose normal would be zero."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
     fuse = fuse_voxel is not None and fuse_voxel is not False
@@ -116,6 +119,12 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     if pieces:
         from .mesh import check_keep_args, remove_small_components
         check_keep_args(min_component_faces, min_component_fraction, who="get_3D_model_from_scene")
+    if (smooth_iterations is not None or smooth_pin_boundary is not True or normals) and not surface:
+        raise ValueError("get_3D_model_from_scene: smooth_iterations / smooth_pin_boundary / normals are for the TSDF surface mesh alone: "
+                         "they need tsdf_mesh (points have no faces, and the per-image sheets keep vertices that no face names)")
+    if smooth_iterations is not None:
+        from .mesh import check_smooth_args
+        check_smooth_args(smooth_iterations, who="get_3D_model_from_scene")
     if scene is None:
         return None
     if mask_sky:
@@ -151,9 +160,10 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
             from .tsdf import tsdf_scene
             surf = tsdf_scene(scene, voxel=None if tsdf_mesh is True else tsdf_mesh, motion=motion, min_conf_thr=min_conf_thr,
                               thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, mesh=True, min_component_faces=min_component_faces,
-                              min_component_fraction=min_component_fraction)
-            geometry = [io.mesh_geometry(surf["vertices"].cpu().numpy(), surf["vertex_rgba"].cpu().numpy(), surf["faces"].cpu().numpy())] \
-                if len(surf["faces"]) else []
+                              min_component_fraction=min_component_fraction, smooth_iterations=smooth_iterations,
+                              smooth_pin_boundary=smooth_pin_boundary, normals=normals)
+            geometry = [io.mesh_geometry(surf["vertices"].cpu().numpy(), surf["vertex_rgba"].cpu().numpy(), surf["faces"].cpu().numpy(),
+                                         surf["vertex_normals"].cpu().numpy() if normals else None)] if len(surf["faces"]) else []
         elif as_pointcloud:
             pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
             c = int(count.item())
@@ -191,8 +201,8 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     nothing else. `tsdf_mesh_static`: a voxel size, or True for tsdf_scene's default, likewise also writes <seq>_static_tsdf_mesh.glb,
     the static part's TSDF surface as a triangle mesh (get_3D_model_from_scene(motion="static", as_pointcloud=False, tsdf_mesh=...)),
     and nothing else; `min_component_faces` / `min_component_fraction` among `glb_kw` filter that mesh alone (see
-    get_3D_model_from_scene): the other files are point clouds unless `glb_kw` says otherwise, and are written as without them. Returns
-    the directory."""
+    get_3D_model_from_scene): the other files are point clouds unless `glb_kw` says otherwise, and are written as without them;
+    `smooth_iterations` / `smooth_pin_boundary` / `normals` among `glb_kw` likewise reach that mesh alone. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -203,6 +213,7 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     pieces = {k: kw.pop(k) for k in ("min_component_faces", "min_component_fraction") if k in kw}   # of the meshes only
     if not kw["as_pointcloud"]:
         kw.update(pieces)
+    pieces.update({k: kw.pop(k) for k in ("smooth_iterations", "smooth_pin_boundary", "normals") if k in kw})   # of the TSDF mesh only
     is_msk, thr_init = kw["is_msk"], kw.get("thr_for_init_conf", True)
     silent = kw.pop("silent")
     get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)

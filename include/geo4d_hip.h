@@ -747,6 +747,58 @@ int geo4d_mesh_select_gather(const float* vertices, const unsigned char* rgba, c
                              const long* first_face, long V, long F, float* vertices_out, unsigned char* rgba_out, float* weight_out,
                              int* faces_out, int* vertex_index, void* stream);
 
+/* The corner table of an indexed triangle mesh - for each vertex, the corners of the faces around it - and its three consumers:
+ * boundary vertices, the Taubin (lambda | mu) smoothing step and area-weighted vertex normals (geo4d_amd/csrc/mesh_smooth.hip,
+ * geo4d_amd/mesh.py). The reference has no such step; the rule is this project's own, restated in numpy in
+ * tests/mesh_smooth_restatement.py. The table is sorted and therefore a function of the mesh alone; the float outputs are gathered per
+ * vertex by one thread in the table's order (no float atomics), so they are bitwise reproducible.
+ *   Inputs: vertices fp32 [Nv][3], faces int32 [T][3], face_mask u8 [T] (NULL: every face).
+ *   Valid: face t is valid iff face_mask[t] != 0 (or there is no mask) and its three indices lie in [0, Nv), which is decided before
+ *     anything is read or written through them. A valid face may repeat an index.
+ *   Arithmetic: fp32 in the written order, contraction into FMAs off, only + - * / and sqrtf, each correctly rounded.
+ *   1. Corner table: an entry is e = 3 t + k for a valid face t and corner k; it belongs to vertex faces[t][k]. offsets int32 [Nv + 1]
+ *     is the exclusive prefix sum of the entries per vertex; corners int32 [E] holds each vertex's entries ascending in e. A face that
+ *     names v twice appears twice in v's row. 3 T >= 2^31 is refused.
+ *   2. Neighbour list of v: walk v's row in order; for each entry (t, k) take a = faces[t][(k + 1) % 3], then b = faces[t][(k + 2) % 3];
+ *     skip those equal to v. m is the list's length.
+ *   3. Boundary: boundary[v] = 1 iff some id occurs exactly once in v's neighbour list, else 0; an empty list gives 0. A neighbour
+ *     across an edge that three or four triangles share occurs three or four times and does not make v a boundary vertex.
+ *   4. Step with factor s: S = 0; for each w of the list in order S_c = S_c + p[w]_c; then p'[v]_c = p[v]_c + s * (S_c / (float) m -
+ *     p[v]_c). v keeps its position bit for bit if m = 0 or pinned[v] != 0. A step reads one buffer and writes another (Jacobi).
+ *   5. Smoothing (the caller's loop): each iteration runs a step with lam and, if mu != 0, a step with mu. The weights count faces: a
+ *     neighbour seen from two faces counts twice (the mean of the opposite edges' midpoints). Non-finite coordinates propagate as IEEE
+ *     arithmetic says.
+ *   6. Normals: n(t) = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x) with e1 = p1 - p0, e2 = p2 - p0 in the face's own
+ *     vertex order (its length is twice the area: the weighting is by area). N = 0; for each entry of v's row in order N_c = N_c +
+ *     n(t)_c; len2 = (Nx Nx + Ny Ny) + Nz Nz; the result is N_c / sqrtf(len2) if len2 > 0 and finite in float, else (0, 0, 0), which
+ *     a vertex with an empty row gets.
+ *   7. Invariance: offsets, boundary and the multiset of each row are integer functions of the mesh, invariant under a permutation
+ *     of the faces up to the renaming of t. The float outputs are functions of the mesh as given: permuting the faces reorders the
+ *     sums and may change last bits.
+ *   geo4d_mesh_adjacency_count: degree int32 [Nv], zeroed by the caller, += 1 per corner of a valid face (integer atomics). The caller
+ *     forms offsets [Nv + 1] = 0 followed by the inclusive prefix sum of degree, and E = offsets[Nv]. geo4d_mesh_adjacency_fill: cursor
+ *     int32 [Nv], zeroed by the caller; corners [E] receives every entry in its vertex's row, in arbitrary order within the row.
+ *     geo4d_mesh_adjacency_sort: corners_out [E] (another buffer) = every row of corners_in ascending; a row of at most long_row
+ *     entries is sorted by one thread, a longer one by one wave (both give the same table). geo4d_mesh_boundary: boundary u8 [Nv],
+ *     one writer per vertex, the same split by long_row. geo4d_mesh_smooth_step: vertices_out fp32 [Nv][3] (another buffer), pinned
+ *     u8 [Nv] or NULL. geo4d_mesh_vertex_normals: normals_out fp32 [Nv][3]. One thread per vertex walks its row in the last two: time is
+ *     linear in the largest valence. Rows outside [0, E], entries outside [0, 3 T) and indices outside [0, Nv) are skipped.
+ *   T == 0 or Nv == 0 (and E == 0 for fill and sort) launch nothing; the outputs are then the caller's to write.
+ *   Null pointers (face_mask and pinned excepted, and the consumers' corners when E == 0: an empty table has no storage), T or Nv
+ *   < 0 or >= 2^31, 3 T >= 2^31, E < 0 or > 3 T, long_row < 0, an output that is its own input, and s not finite return -EINVAL
+ *   before any device work. */
+int geo4d_mesh_adjacency_count(const int* faces, long T, long Nv, const unsigned char* face_mask, int* degree, void* stream);
+int geo4d_mesh_adjacency_fill(const int* faces, long T, long Nv, const unsigned char* face_mask, const int* offsets, long E, int* cursor,
+                              int* corners, void* stream);
+int geo4d_mesh_adjacency_sort(const int* offsets, long T, long Nv, long E, const int* corners_in, int* corners_out, int long_row,
+                              void* stream);
+int geo4d_mesh_boundary(const int* faces, long T, long Nv, const int* offsets, const int* corners, long E, int long_row,
+                        unsigned char* boundary, void* stream);
+int geo4d_mesh_smooth_step(const float* vertices, const int* faces, long T, long Nv, const int* offsets, const int* corners, long E,
+                           const unsigned char* pinned, float s, float* vertices_out, void* stream);
+int geo4d_mesh_vertex_normals(const float* vertices, const int* faces, long T, long Nv, const int* offsets, const int* corners, long E,
+                              float* normals_out, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
