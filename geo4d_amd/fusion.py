@@ -19,7 +19,8 @@ import math
 import torch
 
 from . import _lib, ops
-from .render import _rgba
+from .motion import segment_motion
+from .scene_view import MOTION, rgba_of, scene_view
 
 REDUCE = tuple(ops.FUSE_REDUCE)
 CELL_LIMIT = 1 << 20
@@ -61,7 +62,7 @@ def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="m
     for t, what in ((weight, "weight"), (mask, "mask")):
         if t is not None and tuple(t.shape) != (N,):
             raise ValueError(f"fuse_points: {what} must be [N] = {(N,)}, got {tuple(t.shape)}")
-    rgba = _rgba(colors, (N,), dev, "fuse_points", "colors", "the fusion", "[N, {}] = ")
+    rgba = rgba_of(colors, (N,), dev, "fuse_points", "colors", "the fusion", "[N, {}] = ")
     pts, rgba, w, count, dropped = ops.fuse_points(points.detach().float().contiguous(), rgba,
                                                    None if weight is None else weight.detach().float().contiguous(),
                                                    None if mask is None else mask.to(dev), voxel=v, reduce=reduce, capacity=capacity)
@@ -75,40 +76,32 @@ def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="m
     return dict(points=pts, rgba=rgba, weight=w, count=count, voxel=v)
 
 
-def default_voxel(depth, focals, mask=None):
+def default_voxel(depth, focals, mask=None, empty=None):
     """2 * median(depth / focal) over the pixels of `mask` (None: all), i.e. twice the median pixel footprint, on the device: depth
-    [n, H, W], focals [n] or [n, 1]; fp32, the lower median (torch.median). None when the mask keeps no pixel."""
+    [n, H, W], focals [n] or [n, 1]; fp32, the lower median (torch.median). `empty` (None) when the mask keeps no pixel."""
     r = depth.float() / focals.float().reshape(-1, 1, 1)
     r = r.reshape(-1) if mask is None else r[mask]
-    return 2.0 * float(torch.median(r)) if r.numel() else None
+    return 2.0 * float(torch.median(r)) if r.numel() else empty
 
 
 @torch.no_grad()
 def fuse_scene(scene, *, voxel=None, motion="static", min_conf_thr=3, thr_for_init_conf=True, is_msk=True, reduce="mean", min_count=1):
     """fuse_points on a GroupAligner; the result (see fuse_points) is also stored as scene.fused.
 
-    Points, colours and masks are taken exactly as get_3D_model_from_scene takes them: scene.get_pts3d(), scene.imgs (None: no colours)
-    and scene.get_masks() with `min_conf_thr` / `thr_for_init_conf` set on the scene (`is_msk=False`: every pixel), restricted by
-    `motion` (None, "static", "dynamic") to scene.dynamic_masks, which segment_motion makes with these thresholds when the scene has
-    none. The weight is the scene's confidence, scene.get_conf(), so a pixel whose confidence is not > 0 takes no part. `voxel=None`
-    means default_voxel: 2 * median(depth / focal) over the exported pixels, twice the median pixel footprint. That default gave 22.6
-    times fewer points on the synthetic scene of tests/motion_restatement.py; nobody has tried it on real predictions."""
-    from .scene_export import MOTION, motion_part
+    Points, colours and masks are taken as get_3D_model_from_scene takes them, through scene_view: scene.imgs (None: no colours), the
+    masks of `min_conf_thr` / `thr_for_init_conf` (`is_msk=False`: every pixel) restricted by `motion` (None, "static", "dynamic") to
+    scene.dynamic_masks, which segment_motion makes with these thresholds when the scene has none. The weight is the scene's
+    confidence, scene.get_conf(), so a pixel whose confidence is not > 0 takes no part. `voxel=None` means default_voxel: 2 *
+    median(depth / focal) over the exported pixels, twice the median pixel footprint. That default gave 22.6 times fewer points on the
+    synthetic scene of tests/motion_restatement.py; nobody has tried it on real predictions."""
     if motion not in MOTION:
         raise ValueError(f"fuse_scene: motion must be one of {MOTION}, got {motion!r}")
     check_fuse_args(1.0 if voxel is None else voxel, reduce, min_count)
-    scene.require_all_depthmaps("fuse_scene")
-    pts3d = scene.get_pts3d().detach().contiguous()
-    scene.min_conf_thr = min_conf_thr
-    scene.thr_for_init_conf = thr_for_init_conf
-    msk = scene.get_masks() if is_msk else None
-    if motion is not None:
-        msk = motion_part(scene, msk, motion, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+    view = scene_view(scene, "fuse_scene", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, motion=motion,
+                      segment=segment_motion)
+    msk = view.mask()
     if voxel is None:
-        voxel = default_voxel(scene.get_depthmaps().detach(), scene.get_focals().detach(), msk)
-        if voxel is None:                                           # nothing to fuse: any voxel gives the empty cloud
-            voxel = 1.0
-    colors = None if scene.imgs is None else scene.imgs.to(scene.dev).float().reshape(-1, 3)
-    scene.fused = fuse_points(pts3d.reshape(-1, 3), colors, scene.get_conf().detach().reshape(-1), None if msk is None else msk.reshape(-1),
-                              voxel=voxel, reduce=reduce, min_count=min_count)
+        voxel = default_voxel(view.depth, view.focals, msk, empty=1.0)   # nothing to fuse: any voxel gives the empty cloud
+    scene.fused = fuse_points(view.pts3d.reshape(-1, 3), None if view.rgb is None else view.rgb.reshape(-1, 3), view.conf.reshape(-1),
+                              None if msk is None else msk.reshape(-1), voxel=voxel, reduce=reduce, min_count=min_count)
     return scene.fused

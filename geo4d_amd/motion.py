@@ -18,7 +18,7 @@ is no spatial clean-up; clips of fewer than three images give empty masks (min_v
 import torch
 
 from . import _lib, ops
-from .render import _scene_cameras, _views
+from .scene_view import scene_view, views_of
 
 
 @torch.no_grad()
@@ -37,7 +37,7 @@ def motion_votes(pts3d, depth, valid, cams2world, K, *, radius=8, tol=0.05, near
         raise ValueError(f"motion_votes: need pts3d [n, H, W, 3] and depth [n, H, W], got {tuple(pts3d.shape)} and {tuple(depth.shape)}")
     if not (1 <= int(radius) <= 127) or not (0 < tol < 1):
         raise ValueError(f"motion_votes: need 1 <= radius <= 127 and 0 < tol < 1, got radius={radius}, tol={tol}")
-    views = _views(cams2world, K)
+    views = views_of(cams2world, K)
     if len(views) != pts3d.shape[0]:
         raise ValueError(f"motion_votes: {len(views)} cameras for {pts3d.shape[0]} images")
     if valid is not None:
@@ -61,12 +61,7 @@ def segment_motion(scene, *, min_conf_thr=3, thr_for_init_conf=True, is_msk=True
     Valid pixels are those get_3D_model_from_scene exports (scene.get_masks() with `min_conf_thr` / `thr_for_init_conf`, set on the
     scene as the export sets them); `is_msk=False` lets every pixel vote and be voted on. The rest is the rule of motion_votes and
     dynamic_mask."""
-    scene.require_all_depthmaps("segment_motion")
-    scene.min_conf_thr = min_conf_thr
-    scene.thr_for_init_conf = thr_for_init_conf
-    valid = scene.get_masks() if is_msk else None
-    c2w, K = _scene_cameras(scene)
-    votes = motion_votes(scene.get_pts3d().detach().contiguous(), scene.get_depthmaps().detach().contiguous(), valid, c2w, K,
-                         radius=radius, tol=tol, near=near)
+    view = scene_view(scene, "segment_motion", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+    votes = motion_votes(view.pts3d, view.depth, view.msk, *view.cameras, radius=radius, tol=tol, near=near)
     scene.dynamic_masks = dynamic_mask(votes, min_votes, ratio)
     return scene.dynamic_masks

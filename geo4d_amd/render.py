@@ -16,60 +16,11 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .motion import segment_motion
+from .scene_view import MeshOptions, rgba_of, scene_view, source_lists, views_of, voxel_option
+from .tsdf import tsdf_scene
 
 MODES = ("cameras", "playback", "turntable")
-
-
-def _views(cams2world, K):
-    """[V, 16] fp32 on the host: rows 0..2 of inv(cams2world) (4x4 algebra in fp64), then fx, fy, cx, cy of K [V, 3, 3]."""
-    c2w = torch.as_tensor(cams2world).detach().double().cpu().numpy().reshape(-1, 4, 4)
-    K = torch.as_tensor(K).detach().double().cpu().numpy().reshape(-1, 3, 3)
-    if len(c2w) != len(K):
-        raise ValueError(f"render: {len(c2w)} camera poses but {len(K)} intrinsics")
-    w2c = np.linalg.inv(c2w)
-    v = np.concatenate([w2c[:, :3, :].reshape(-1, 12), K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3]], 1)
-    return torch.from_numpy(v.astype(np.float32))
-
-
-def _rgba(colors, lead, device, who, arg, step, named=""):
-    """u8 [*lead, 4] of `colors`: a u8 rgba as it is, or float [*lead, 3] in [0, 1] quantised as ops.scene_points does (clip(c * 255 +
-    0.5, 0, 255) truncated, in fp32) with alpha 255. The messages speak as `who` of its argument `arg` and of `step`, the thing that
-    runs; `named` puts a name in front of the shapes they quote ("[N, {}] = ")."""
-    if colors is None:
-        return None
-    if not colors.is_cuda:
-        raise _lib.Geo4DNativeError(f"{who}: `{arg}` lives on {colors.device}; {step} runs only on a HIP device")
-    if colors.dtype == torch.uint8:
-        if tuple(colors.shape) != (*lead, 4):
-            raise ValueError(f"{who}: uint8 colours must be rgba {named.format(4)}{(*lead, 4)}, got {tuple(colors.shape)}")
-        return colors.contiguous()
-    if tuple(colors.shape) != (*lead, 3):
-        raise ValueError(f"{who}: float colours must be {named.format(3)}{(*lead, 3)}, got {tuple(colors.shape)}")
-    rgb = ((colors.float() * 255.0) + 0.5).clamp(0.0, 255.0).to(torch.uint8)
-    return torch.cat([rgb, torch.full((*lead, 1), 255, dtype=torch.uint8, device=device)], -1).contiguous()
-
-
-def _scene_cameras(scene):
-    """(cams2world [n, 4, 4], K [n, 3, 3]) fp64 on the host from a GroupAligner's poses, focals and principal points."""
-    n = scene.n
-    K = torch.zeros((n, 3, 3), dtype=torch.float64)
-    K[:, 0, 0] = K[:, 1, 1] = scene.get_focals().detach().reshape(n).double().cpu()
-    K[:, :2, 2] = scene.get_principal_points().detach().double().cpu()
-    K[:, 2, 2] = 1
-    return scene.get_im_poses_matrix().detach().double().cpu(), K
-
-
-def _csr(sources, V, n_img):
-    """Host CSR (ptr, idx) of the source images per view; None = every image for every view."""
-    if sources is None:
-        sources = [range(n_img)] * V
-    if len(sources) != V:
-        raise ValueError(f"render: {len(sources)} source lists for {V} views")
-    ptr, idx = [0], []
-    for s in sources:
-        idx.extend(int(i) for i in s)
-        ptr.append(len(idx))
-    return ptr, idx
 
 
 @torch.no_grad()
@@ -95,9 +46,9 @@ def render_points(points, colors, cams2world, K, size, *, mask=None, radius=None
     pts = points.reshape(-1, 3).float().contiguous()
     col = colors.reshape(-1, 3).float().contiguous()
     N = pts.shape[0]
-    views = _views(cams2world, K)
+    views = views_of(cams2world, K)
     V = len(views)
-    ptr, idx = _csr(sources, V, n_img)
+    ptr, idx = source_lists(sources, V, n_img)
     flat = lambda t, dt: None if t is None else t.to(pts.device).reshape(-1).to(dt).contiguous()
     mask, radius = flat(mask, torch.bool), flat(radius, torch.float32)
     ws = ops.render_workspace(V, H, W, len(idx), pts.device)
@@ -146,7 +97,7 @@ def render_mesh(vertices, faces, cams2world, K, size, *, colors=None, mesh_color
     Nv, T = vert.shape[0], tri.shape[0]
     vcol = None
     if colors is not None:
-        vcol = _rgba(colors, (Nv,), dev, who, "colors", "rendering", "[Nv, {}] = ") if colors.dtype == torch.uint8 else None
+        vcol = rgba_of(colors, (Nv,), dev, who, "colors", "rendering", "[Nv, {}] = ") if colors.dtype == torch.uint8 else None
         if vcol is None:
             if not colors.is_cuda:
                 raise _lib.Geo4DNativeError(f"{who}: `colors` lives on {colors.device}; rendering runs only on a HIP device")
@@ -155,7 +106,7 @@ def render_mesh(vertices, faces, cams2world, K, size, *, colors=None, mesh_color
             vcol = colors.detach().float().contiguous()
     if face_mask is not None and tuple(face_mask.shape) != (T,):
         raise ValueError(f"{who}: face_mask must be [T] = {(T,)}, got {tuple(face_mask.shape)}")
-    views = _views(cams2world, K)
+    views = views_of(cams2world, K)
     V = len(views)
     dviews = views.to(dev)
     N, col = 0, None
@@ -168,7 +119,7 @@ def render_mesh(vertices, faces, cams2world, K, size, *, colors=None, mesh_color
         col = point_colors.reshape(-1, 3).float().contiguous()
         N = pts.shape[0]
     if N:
-        ptr, idx = _csr(sources, V, n_img)
+        ptr, idx = source_lists(sources, V, n_img)
         flat = lambda t, dt: None if t is None else t.to(dev).reshape(-1).to(dt).contiguous()
         ws = ops.render_workspace(V, H, W, len(idx), dev)
         ops.render_splat(pts, dviews, ptr, idx, (H, W), ws, mask=flat(mask, torch.bool), radius=flat(radius, torch.float32),
@@ -236,26 +187,18 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
     the smoothed mesh) and need static_mesh; the shading stays flat, per triangle."""
     if mode not in MODES:
         raise ValueError(f"render_scene: mode must be one of {MODES}, got {mode!r}")
-    if static_mesh is not None and static_mesh is not False and persist_static:
+    options = MeshOptions(min_component_faces, min_component_fraction, smooth_iterations, smooth_pin_boundary)
+    as_mesh, voxel = voxel_option(static_mesh)
+    if as_mesh and persist_static:
         raise ValueError("render_scene: static_mesh draws the static part as a mesh and persist_static as points; choose one")
-    if (min_component_faces is not None or min_component_fraction is not None) and (static_mesh is None or static_mesh is False):
+    if options.filtering and not as_mesh:
         raise ValueError("render_scene: min_component_faces / min_component_fraction filter the static mesh; pass static_mesh")
-    if (smooth_iterations is not None or smooth_pin_boundary is not True) and (static_mesh is None or static_mesh is False):
+    if options.shaping and not as_mesh:
         raise ValueError("render_scene: smooth_iterations / smooth_pin_boundary smooth the static mesh; pass static_mesh")
-    if scene.imgs is None:
-        raise ValueError("render_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs [n, H, W, 3] in [0, 1]")
-    scene.require_all_depthmaps("render_scene")
-    n, H, W = scene.n, scene.H, scene.W
-    imgs = scene.imgs.to(scene.dev).float().contiguous()
-    pts3d = scene.get_pts3d().detach().contiguous()
-    scene.min_conf_thr = min_conf_thr
-    scene.thr_for_init_conf = thr_for_init_conf
-    msk = scene.get_masks() if is_msk else None
-    focals = scene.get_focals().detach().reshape(n)
-    c2w, K = _scene_cameras(scene)
-    radius = None
-    if point_size:
-        radius = 0.5 * float(point_size) * scene.get_depthmaps().detach() / focals.view(n, 1, 1)
+    view = scene_view(scene, "render_scene", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk,
+                      segment=segment_motion)
+    n, H, W, imgs, pts3d, msk, (c2w, K) = view.n, view.H, view.W, view.imgs, view.pts3d, view.msk, view.cameras
+    radius = 0.5 * float(point_size) * view.depth / view.focals.reshape(n, 1, 1) if point_size else None
     everything = list(range(n))
     if mode == "cameras":
         poses, Kv, src = c2w, K, [everything] * n
@@ -282,38 +225,24 @@ def render_scene(scene, mode="cameras", *, size=None, min_conf_thr=3, is_msk=Tru
         Kv = Kv.clone()
         Kv[:, 0] *= ow / W
         Kv[:, 1] *= oh / H
-    if static_mesh is not None and static_mesh is not False:
-        # the static part as its TSDF surface, the moving points of each view's source images over it
-        voxel = None if static_mesh is True else float(np.float32(static_mesh))   # as scene.tsdf["voxel"] holds it
-        tsdf = getattr(scene, "tsdf", None)
-        if tsdf is None or "vertices" not in tsdf or (voxel is not None and tsdf["voxel"] != voxel):
-            from .tsdf import tsdf_scene
-            tsdf = tsdf_scene(scene, voxel, motion="static", mesh=True, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf,
-                              is_msk=is_msk, near=near, min_component_faces=min_component_faces,
-                              min_component_fraction=min_component_fraction, smooth_iterations=smooth_iterations,
-                              smooth_pin_boundary=smooth_pin_boundary)
-        dyn = getattr(scene, "dynamic_masks", None)
-        if dyn is None:
-            from .motion import segment_motion
-            dyn = segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
-        movers = src if sources is not None or mode == "playback" else [[]] * len(src)
-        return render_mesh(tsdf["vertices"], tsdf["faces"], poses, Kv, (oh, ow), colors=tsdf.get("vertex_rgba", tsdf.get("rgba")),
-                           shade=shade, cull_back=cull_back, points=pts3d, point_colors=imgs, mask=dyn if msk is None else msk & dyn,
-                           radius=radius, sources=movers, max_size=max_size, fill=fill, near=near, background=background)
-    if not persist_static:
+    if not (as_mesh or persist_static):
         return render_points(pts3d, imgs, poses, Kv, (oh, ow), mask=msk, radius=radius, sources=src, near=near, max_size=max_size,
                              fill=fill, background=background)
-    # the images twice, n static-masked copies then n dynamic-masked ones: every view draws all of the former and its own sources of the latter
-    dyn = getattr(scene, "dynamic_masks", None)
-    if dyn is None:
-        from .motion import segment_motion
-        dyn = segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
-    keep = msk if msk is not None else torch.ones_like(dyn)
-    twice = lambda t: None if t is None else torch.cat([t, t])
     movers = src if sources is not None or mode == "playback" else [[]] * len(src)  # "every image" would smear the movers again
-    out = render_points(twice(pts3d), twice(imgs), poses, Kv, (oh, ow), mask=torch.cat([keep & ~dyn, keep & dyn]), radius=twice(radius),
-                        sources=[everything + [n + int(i) for i in s] for s in movers], near=near, max_size=max_size, fill=fill,
-                        background=background)
+    if as_mesh:
+        # the static part as its TSDF surface, the moving points of each view's source images over it
+        voxel = voxel if voxel is None else float(np.float32(voxel))               # as scene.tsdf["voxel"] holds it
+        tsdf = getattr(scene, "tsdf", None)
+        if tsdf is None or "vertices" not in tsdf or (voxel is not None and tsdf["voxel"] != voxel):
+            tsdf = tsdf_scene(scene, voxel, motion="static", mesh=True, near=near, **view.thresholds, **vars(options))
+        return render_mesh(tsdf["vertices"], tsdf["faces"], poses, Kv, (oh, ow), colors=tsdf.get("vertex_rgba", tsdf.get("rgba")),
+                           shade=shade, cull_back=cull_back, points=pts3d, point_colors=imgs, mask=view.mask("dynamic"), radius=radius,
+                           sources=movers, max_size=max_size, fill=fill, near=near, background=background)
+    # the images twice, n static-masked copies then n dynamic-masked ones: every view draws all of the former and its own sources of the latter
+    twice = lambda t: None if t is None else torch.cat([t, t])
+    out = render_points(twice(pts3d), twice(imgs), poses, Kv, (oh, ow), mask=torch.cat([view.mask("static"), view.mask("dynamic")]),
+                        radius=twice(radius), sources=[everything + [n + int(i) for i in s] for s in movers], near=near, max_size=max_size,
+                        fill=fill, background=background)
     idx = out["index"]
     out["index"] = torch.where(idx >= n * H * W, idx - n * H * W, idx)            # rows of the original pts3d.reshape(-1, 3)
     return out

@@ -10,7 +10,13 @@ import os
 
 import torch
 
-from . import io, ops
+from . import _lib, io, ops
+from .fusion import fuse_scene
+from .mesh import remove_small_components
+from .motion import segment_motion
+from .render import render_scene, save_render
+from .scene_view import MOTION, MeshOptions, scene_view, voxel_option
+from .tsdf import tsdf_scene
 
 
 def check_tol(tol):
@@ -34,7 +40,6 @@ def clean_pointcloud(im_confs, K, cams, depthmaps, all_pts3d, tol=0.001, bad_con
     n, H, W = conf.shape
     cams, K = _stack(cams), _stack(K)
     if not (conf.is_cuda and cams.is_cuda and K.is_cuda):
-        from . import _lib
         raise _lib.Geo4DNativeError("clean_pointcloud runs only on a HIP device (there is no CPU fallback)")
     assert len(cams) == len(K) == n, (cams.shape, K.shape, conf.shape)
     mats = torch.cat([cams[:, :3, :].reshape(n, 12), K.reshape(n, 9)], 1).float().contiguous()
@@ -49,20 +54,6 @@ def camera_colors(n):
     import matplotlib
     cmap = matplotlib.colormaps["viridis"]
     return [tuple(255 * c for c in cmap(i / n)[:3]) for i in range(n)]
-
-
-MOTION = (None, "static", "dynamic")
-
-
-def motion_part(scene, msk, motion, **seg_kw):
-    """The export mask [n, H, W] restricted to the "static" or "dynamic" pixels of scene.dynamic_masks (segment_motion(**seg_kw) makes
-    them when the scene has none); msk None = every pixel."""
-    dyn = getattr(scene, "dynamic_masks", None)
-    if dyn is None:
-        from .motion import segment_motion
-        dyn = segment_motion(scene, **seg_kw)
-    part = dyn if motion == "dynamic" else ~dyn
-    return part if msk is None else msk & part
 
 
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
@@ -95,92 +86,66 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     `tsdf_mesh` they raise: points have no faces, and the per-image sheets keep unreferenced vertices, whose normal would be zero."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
-    fuse = fuse_voxel is not None and fuse_voxel is not False
+    options = MeshOptions(min_component_faces, min_component_fraction, smooth_iterations, smooth_pin_boundary, normals)
+    (fuse, fuse_voxel), (tsdf, tsdf_voxel), (surface, tsdf_mesh) = voxel_option(fuse_voxel), voxel_option(tsdf_voxel), voxel_option(tsdf_mesh)
     if fuse and not as_pointcloud:
         raise ValueError("get_3D_model_from_scene: fuse_voxel merges points and has no faces to give: it needs as_pointcloud=True")
-    tsdf = tsdf_voxel is not None and tsdf_voxel is not False
     if tsdf and fuse:
         raise ValueError("get_3D_model_from_scene: fuse_voxel and tsdf_voxel are two different clouds of the same points: give one of them")
     if tsdf and not as_pointcloud:
         raise ValueError("get_3D_model_from_scene: tsdf_voxel gives surface points and has no faces to give: it needs as_pointcloud=True")
     if tsdf and motion == "dynamic":
         raise ValueError("get_3D_model_from_scene: tsdf_voxel with motion='dynamic': the moving part has no TSDF")
-    surface = tsdf_mesh is not None and tsdf_mesh is not False
     if surface and (fuse or tsdf):
         raise ValueError("get_3D_model_from_scene: tsdf_mesh writes triangles, fuse_voxel and tsdf_voxel write points: give one of them")
     if surface and as_pointcloud:
         raise ValueError("get_3D_model_from_scene: tsdf_mesh writes triangles: it needs as_pointcloud=False (tsdf_voxel gives the points)")
     if surface and motion == "dynamic":
         raise ValueError("get_3D_model_from_scene: tsdf_mesh with motion='dynamic': the moving part has no TSDF")
-    pieces = min_component_faces is not None or min_component_fraction is not None
-    if pieces and (as_pointcloud or fuse or tsdf):
+    if options.filtering and (as_pointcloud or fuse or tsdf):
         raise ValueError("get_3D_model_from_scene: min_component_faces / min_component_fraction remove pieces of a mesh and points have "
                          "no faces to connect them: they need as_pointcloud=False and neither fuse_voxel nor tsdf_voxel")
-    if pieces:
-        from .mesh import check_keep_args, remove_small_components
-        check_keep_args(min_component_faces, min_component_fraction, who="get_3D_model_from_scene")
-    if (smooth_iterations is not None or smooth_pin_boundary is not True or normals) and not surface:
+    if options.shaping and not surface:
         raise ValueError("get_3D_model_from_scene: smooth_iterations / smooth_pin_boundary / normals are for the TSDF surface mesh alone: "
                          "they need tsdf_mesh (points have no faces, and the per-image sheets keep vertices that no face names)")
-    if smooth_iterations is not None:
-        from .mesh import check_smooth_args
-        check_smooth_args(smooth_iterations, who="get_3D_model_from_scene")
+    options.check("get_3D_model_from_scene")
     if scene is None:
         return None
     if mask_sky:
         raise NotImplementedError("get_3D_model_from_scene(mask_sky=True): segment_sky needs OpenCV (cv2), which is not available")
     if clean_depth:
         scene = scene.clean_pointcloud()
-    if scene.imgs is None:
-        raise ValueError("get_3D_model_from_scene: the scene has no RGB frames; pass imgs= to post_optimization or set scene.imgs "
-                         "[n, H, W, 3] in [0, 1]")
-    scene.require_all_depthmaps("get_3D_model_from_scene")
     with torch.no_grad():
-        imgs = scene.imgs.to(scene.dev).float().contiguous()
-        focals = scene.get_focals().detach()
-        cams2world = scene.get_im_poses_matrix().detach()
-        pts3d = scene.get_pts3d().contiguous()
-        scene.min_conf_thr = min_conf_thr
-        scene.thr_for_init_conf = thr_for_init_conf
-        msk = scene.get_masks() if is_msk else None
-        if motion is not None:
-            msk = motion_part(scene, msk, motion, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
-        n, H, W, _ = pts3d.shape
+        view = scene_view(scene, "get_3D_model_from_scene", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk,
+                          motion=motion, segment=segment_motion)
+        imgs, n, H, W = view.imgs, view.n, view.H, view.W
+        part = dict(view.thresholds, motion=motion)                 # fuse_scene and tsdf_scene take the scene again, the same way
+        cloud = lambda d: [dict(mode=0, positions=d["points"].cpu().numpy(), colors=d["rgba"].cpu().numpy())] if len(d["points"]) else []
         if fuse:
-            from .fusion import fuse_scene
-            fused = fuse_scene(scene, voxel=None if fuse_voxel is True else fuse_voxel, motion=motion, min_conf_thr=min_conf_thr,
-                               thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
-            geometry = [dict(mode=0, positions=fused["points"].cpu().numpy(), colors=fused["rgba"].cpu().numpy())] if len(fused["points"]) else []
+            geometry = cloud(fuse_scene(scene, voxel=fuse_voxel, **part))
         elif tsdf:
-            from .tsdf import tsdf_scene
-            surf = tsdf_scene(scene, voxel=None if tsdf_voxel is True else tsdf_voxel, motion=motion, min_conf_thr=min_conf_thr,
-                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
-            geometry = [dict(mode=0, positions=surf["points"].cpu().numpy(), colors=surf["rgba"].cpu().numpy())] if len(surf["points"]) else []
+            geometry = cloud(tsdf_scene(scene, voxel=tsdf_voxel, **part))
         elif surface:
-            from .tsdf import tsdf_scene
-            surf = tsdf_scene(scene, voxel=None if tsdf_mesh is True else tsdf_mesh, motion=motion, min_conf_thr=min_conf_thr,
-                              thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, mesh=True, min_component_faces=min_component_faces,
-                              min_component_fraction=min_component_fraction, smooth_iterations=smooth_iterations,
-                              smooth_pin_boundary=smooth_pin_boundary, normals=normals)
+            surf = tsdf_scene(scene, voxel=tsdf_mesh, mesh=True, **part, **vars(options))
             geometry = [io.mesh_geometry(surf["vertices"].cpu().numpy(), surf["vertex_rgba"].cpu().numpy(), surf["faces"].cpu().numpy(),
                                          surf["vertex_normals"].cpu().numpy() if normals else None)] if len(surf["faces"]) else []
         elif as_pointcloud:
-            pts, rgba, count = ops.scene_points(pts3d, imgs, msk)
+            pts, rgba, count = ops.scene_points(view.pts3d, imgs, view.mask())
             c = int(count.item())
             geometry = [dict(mode=0, positions=pts[:c].cpu().numpy(), colors=rgba[:c].cpu().numpy())] if c else []   # e.g. no mover
         else:
-            pts, rgba, _ = ops.scene_points(pts3d, imgs, None)          # every vertex, as cat_meshes keeps them
-            faces, count = ops.scene_mesh_faces(msk, n, H, W, pts3d.device)
+            pts, rgba, _ = ops.scene_points(view.pts3d, imgs, None)     # every vertex, as cat_meshes keeps them
+            faces, count = ops.scene_mesh_faces(view.mask(), n, H, W, view.dev)
             c = int(count.item())
             faces = faces[:c]
-            if pieces and c:
+            if options.filtering and c:
                 kept = remove_small_components(pts, faces, min_faces=min_component_faces, min_fraction=min_component_fraction, rgba=rgba)
                 pts, rgba, faces, c = kept["vertices"], kept["rgba"], kept["faces"], len(kept["faces"])
             geometry = [io.mesh_geometry(pts.cpu().numpy(), rgba.cpu().numpy(), faces.cpu().numpy())] if c else []
     outfile = os.path.join(outdir, (save_name or "scene") + ".glb")
     if not silent:
         print("(exporting 3D scene to", outfile, ")")
-    return io.write_scene_glb(outfile, geometry, focals, cams2world, (W, H), cam_size=cam_size, show_cam=show_cam,
+    return io.write_scene_glb(outfile, geometry, view.focals, view.poses, (W, H), cam_size=cam_size, show_cam=show_cam,
                               cam_color=camera_colors(n))
 
 
@@ -219,19 +184,14 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
     if dynamic_masks:
         if getattr(scene, "dynamic_masks", None) is None:
-            from .motion import segment_motion
             segment_motion(scene, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_init, is_msk=is_msk)
         io.save_dynamic_masks(d, scene.dynamic_masks)
         get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static", **dict(kw, motion="static"))
-    if fuse_static is not None and fuse_static is not False:
-        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_fused",
-                                **dict(kw, motion="static", as_pointcloud=True, fuse_voxel=fuse_static))
-    if tsdf_static is not None and tsdf_static is not False:
-        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf",
-                                **dict(kw, motion="static", as_pointcloud=True, tsdf_voxel=tsdf_static))
-    if tsdf_mesh_static is not None and tsdf_mesh_static is not False:
-        get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq + "_static_tsdf_mesh",
-                                **dict(kw, motion="static", as_pointcloud=False, tsdf_mesh=tsdf_mesh_static, **pieces))
+    for name, arg, voxel, cloud in (("fused", "fuse_voxel", fuse_static, True), ("tsdf", "tsdf_voxel", tsdf_static, True),
+                                    ("tsdf_mesh", "tsdf_mesh", tsdf_mesh_static, False)):
+        if voxel_option(voxel)[0]:                                  # the static part again, as another cloud or as the TSDF mesh
+            get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=f"{seq}_static_{name}",
+                                    **dict(kw, motion="static", as_pointcloud=cloud, **{arg: voxel}, **({} if cloud else pieces)))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())
@@ -241,8 +201,6 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
         io.save_conf_maps(d, scene.get_init_conf(), "init_conf")
         io.save_rgb_imgs(d, scene.imgs.detach().cpu().numpy())
     if render is not None:
-        from . import render as _render
-        frames = _render.render_scene(scene, render, min_conf_thr=min_conf_thr, is_msk=is_msk, thr_for_init_conf=thr_init,
-                                      **(render_kw or {}))
-        _render.save_render(os.path.join(d, "render"), frames["rgb"])
+        frames = render_scene(scene, render, min_conf_thr=min_conf_thr, is_msk=is_msk, thr_for_init_conf=thr_init, **(render_kw or {}))
+        save_render(os.path.join(d, "render"), frames["rgb"])
     return d

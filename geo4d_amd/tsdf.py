@@ -37,8 +37,10 @@ import math
 import torch
 
 from . import _lib, ops
-from .mesh import check_keep_args, check_smooth_args, mesh_adjacency, remove_small_components, smooth_mesh, vertex_normals
-from .render import _rgba, _scene_cameras, _views
+from .fusion import default_voxel
+from .mesh import mesh_adjacency, remove_small_components, smooth_mesh, vertex_normals
+from .motion import segment_motion
+from .scene_view import MeshOptions, rgba_of, scene_view, views_of
 
 MOTION = (None, "static")
 MAX_TRUNC = 8
@@ -78,7 +80,8 @@ def tsdf_points(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, vo
     of voxels marked and integrated. `capacity` overrides the voxel table's size (a power of two; default: >= 4 x the taking-part
     pixels); a table that is too small raises ops.TsdfTableFull naming the capacity to pass. Raises ValueError when a sample's cell
     index floor(x / voxel) reaches 2^20 in magnitude."""
-    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=True, mesh=False)
+    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, MeshOptions(), points=True,
+                 mesh=False)
 
 
 @torch.no_grad()
@@ -100,23 +103,17 @@ def tsdf_mesh(pts3d, depth, valid, cams2world, K, rgb=None, weight=None, *, voxe
     vertices of the (filtered) mesh, the boundary vertices staying where they are unless `smooth_pin_boundary` is False; faces, colours
     and weights are untouched. `normals=True`: the dict gains `normals` fp32 [V, 3], the area-weighted unit vertex normals of the mesh as
     returned (mesh.vertex_normals). The order is extraction, component filter, smoothing, normals."""
-    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, points=False, mesh=True,
-                 min_component_faces=min_component_faces, min_component_fraction=min_component_fraction,
-                 smooth_iterations=smooth_iterations, smooth_pin_boundary=smooth_pin_boundary, normals=normals)
+    opts = MeshOptions(min_component_faces, min_component_fraction, smooth_iterations, smooth_pin_boundary, normals)
+    return _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, opts, points=False, mesh=True)
 
 
-def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, *, points, mesh,
-          min_component_faces=None, min_component_fraction=None, smooth_iterations=None, smooth_pin_boundary=True, normals=False):
+def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_weight, near, capacity, opts, *, points, mesh):
     """The checks of tsdf_points, one field (ops.tsdf_field), and what is asked for of its surface: the points (`points`, rgba,
-    weight), the mesh, or both (then the mesh's colours and weights are `vertex_rgba`, `vertex_weight`). The mesh goes through
-    mesh.remove_small_components when either component argument is given, then through mesh.smooth_mesh when `smooth_iterations` is
-    given, and mesh.vertex_normals adds `normals` (`vertex_normals` beside points) when `normals` is set, all on one corner table."""
+    weight), the mesh, or both (then the mesh's colours and weights are `vertex_rgba`, `vertex_weight`). As `opts` (a MeshOptions)
+    says, the mesh goes through mesh.remove_small_components when either component argument is given, then through mesh.smooth_mesh
+    when `smooth_iterations` is given, and mesh.vertex_normals adds `normals` (`vertex_normals` beside points), all on one corner table."""
     v = check_tsdf_args(voxel, trunc, min_weight, near, capacity)
-    filtering = min_component_faces is not None or min_component_fraction is not None
-    if filtering:
-        check_keep_args(min_component_faces, min_component_fraction, who="tsdf_mesh")
-    if smooth_iterations is not None:
-        check_smooth_args(smooth_iterations, who="tsdf_mesh")
+    opts.check("tsdf_mesh")
     for t, what in ((pts3d, "pts3d"), (depth, "depth")):
         if not t.is_cuda:
             raise _lib.Geo4DNativeError(f"tsdf_points: `{what}` lives on {t.device}; the TSDF runs only on a HIP device (there is no CPU "
@@ -127,11 +124,11 @@ def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_wei
     for t, what in ((valid, "valid"), (weight, "weight")):
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"tsdf_points: {what} must be [n, H, W] = {shape}, got {tuple(t.shape)}")
-    views = _views(cams2world, K)
+    views = views_of(cams2world, K)
     if len(views) != shape[0]:
         raise ValueError(f"tsdf_points: {len(views)} cameras for {shape[0]} images")
     centres = torch.as_tensor(cams2world).detach().double().cpu().reshape(-1, 4, 4)[:, :3, 3].float().contiguous()
-    rgba = _rgba(rgb, shape, dev, "tsdf_points", "rgb", "the TSDF")
+    rgba = rgba_of(rgb, shape, dev, "tsdf_points", "rgb", "the TSDF")
     Kv, f, wt, col, voxels, dropped = ops.tsdf_field(pts3d.detach().float().contiguous(), depth.detach().float().contiguous(),
                                                      None if valid is None else valid.to(dev), views.to(dev), centres.to(dev), rgba,
                                                      None if weight is None else weight.detach().float().contiguous(), voxel=v,
@@ -149,16 +146,17 @@ def _tsdf(pts3d, depth, valid, cams2world, K, rgb, weight, voxel, trunc, min_wei
     out.update(voxels=voxels, dropped=0, overflow=0, voxel=v)
     if mesh:
         vertices, vcol, vw, faces = ops.tsdf_mesh_extract(Kv, f, wt, col, voxel=v, min_weight=float(min_weight))
-        if filtering:
-            kept = remove_small_components(vertices, faces, min_faces=min_component_faces, min_fraction=min_component_fraction, rgba=vcol,
-                                           weight=vw)
+        if opts.filtering:
+            kept = remove_small_components(vertices, faces, min_faces=opts.min_component_faces, min_fraction=opts.min_component_fraction,
+                                           rgba=vcol, weight=vw)
             vertices, vcol, vw, faces = kept["vertices"], kept["rgba"], kept["weight"], kept["faces"]
             out.update(components=kept["components"], kept_components=kept["kept_components"], removed_faces=kept["removed_faces"])
-        if smooth_iterations is not None or normals:
+        if opts.smooth_iterations is not None or opts.normals:
             table = mesh_adjacency(faces, vertices.shape[0])       # one table for both: a smoothing step moves no vertex between faces
-            if smooth_iterations is not None:
-                vertices = smooth_mesh(vertices, faces, iterations=smooth_iterations, pin_boundary=bool(smooth_pin_boundary), adjacency=table)
-            if normals:
+            if opts.smooth_iterations is not None:
+                vertices = smooth_mesh(vertices, faces, adjacency=table, iterations=opts.smooth_iterations,
+                                       pin_boundary=bool(opts.smooth_pin_boundary))
+            if opts.normals:
                 out["vertex_normals" if points else "normals"] = vertex_normals(vertices, faces, adjacency=table)
         out.update(vertices=vertices, faces=faces, **(dict(vertex_rgba=vcol, vertex_weight=vw) if points else dict(rgba=vcol, weight=vw)))
     return out
@@ -174,42 +172,26 @@ def tsdf_scene(scene, voxel=None, motion="static", *, min_conf_thr=3, thr_for_in
     `smooth_iterations` / `smooth_pin_boundary` smooth that mesh and `normals=True` adds `vertex_normals` fp32 [V, 3], as tsdf_mesh does
     (with `mesh=False` any of the three raises); the points are left as they are.
 
-    Points, colours and masks are taken exactly as fusion.fuse_scene and get_3D_model_from_scene take them: scene.get_pts3d(),
-    scene.get_depthmaps(), scene.imgs (None: no colours) and scene.get_masks() with `min_conf_thr` / `thr_for_init_conf` set on the scene
-    (`is_msk=False`: every pixel), restricted by `motion` (None, or "static": not scene.dynamic_masks, which segment_motion makes with
-    these thresholds when the scene has none; a TSDF of moving things is meaningless, so "dynamic" is refused). Every image counts 1;
-    `use_conf=True` weights by scene.get_conf(). `voxel=None` means fusion.default_voxel, 2 * median(depth / focal) over the exported
-    pixels. The defaults were chosen on the synthetic scene of tests/motion_restatement.py; nobody has tried them on real predictions."""
-    from .fusion import default_voxel
-    from .scene_export import motion_part
+    Points, depth, colours and masks are taken as fusion.fuse_scene and get_3D_model_from_scene take them, through scene_view: scene.imgs
+    (None: no colours), the masks of `min_conf_thr` / `thr_for_init_conf` (`is_msk=False`: every pixel) restricted by `motion` (None, or
+    "static": not scene.dynamic_masks, which segment_motion makes with these thresholds when the scene has none; a TSDF of moving
+    things is meaningless, so "dynamic" is refused). Every image counts 1; `use_conf=True` weights by scene.get_conf(). `voxel=None`
+    means fusion.default_voxel, 2 * median(depth / focal) over the exported pixels. The defaults were chosen on the synthetic scene of
+    tests/motion_restatement.py; nobody has tried them on real predictions."""
     if motion not in MOTION:
         raise ValueError(f"tsdf_scene: motion must be one of {MOTION}, got {motion!r} (the moving part has no TSDF)")
     check_tsdf_args(1.0 if voxel is None else voxel, trunc, min_weight, near, capacity)
-    if min_component_faces is not None or min_component_fraction is not None:
-        if not mesh:
-            raise ValueError("tsdf_scene: min_component_faces / min_component_fraction filter the mesh; pass mesh=True")
-        check_keep_args(min_component_faces, min_component_fraction, who="tsdf_scene")
-    if smooth_iterations is not None or smooth_pin_boundary is not True or normals:
-        if not mesh:
-            raise ValueError("tsdf_scene: smooth_iterations / smooth_pin_boundary / normals work on the mesh; pass mesh=True")
-        if smooth_iterations is not None:
-            check_smooth_args(smooth_iterations, who="tsdf_scene")
-    scene.require_all_depthmaps("tsdf_scene")
-    pts3d = scene.get_pts3d().detach().contiguous()
-    depth = scene.get_depthmaps().detach().contiguous()
-    scene.min_conf_thr = min_conf_thr
-    scene.thr_for_init_conf = thr_for_init_conf
-    msk = scene.get_masks() if is_msk else None
-    if motion is not None:
-        msk = motion_part(scene, msk, motion, min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk)
+    opts = MeshOptions(min_component_faces, min_component_fraction, smooth_iterations, smooth_pin_boundary, normals)
+    if opts.filtering and not mesh:
+        raise ValueError("tsdf_scene: min_component_faces / min_component_fraction filter the mesh; pass mesh=True")
+    if opts.shaping and not mesh:
+        raise ValueError("tsdf_scene: smooth_iterations / smooth_pin_boundary / normals work on the mesh; pass mesh=True")
+    opts.check("tsdf_scene")
+    view = scene_view(scene, "tsdf_scene", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, motion=motion,
+                      segment=segment_motion)
+    msk = view.mask()
     if voxel is None:
-        voxel = default_voxel(depth, scene.get_focals().detach(), msk)
-        if voxel is None:                                           # no pixel: any voxel gives the empty cloud
-            voxel = 1.0
-    c2w, K = _scene_cameras(scene)
-    rgb = None if scene.imgs is None else scene.imgs.to(scene.dev).float()
-    scene.tsdf = _tsdf(pts3d, depth, msk, c2w, K, rgb, scene.get_conf().detach() if use_conf else None, voxel, trunc, min_weight, near,
-                       capacity, points=True, mesh=bool(mesh), min_component_faces=min_component_faces,
-                       min_component_fraction=min_component_fraction, smooth_iterations=smooth_iterations,
-                       smooth_pin_boundary=smooth_pin_boundary, normals=normals)
+        voxel = default_voxel(view.depth, view.focals, msk, empty=1.0)   # no pixel: any voxel gives the empty cloud
+    scene.tsdf = _tsdf(view.pts3d, view.depth, msk, *view.cameras, view.rgb, view.conf if use_conf else None, voxel, trunc, min_weight, near,
+                       capacity, opts, points=True, mesh=bool(mesh))
     return scene.tsdf

@@ -8,7 +8,7 @@ DEFAULTS = dict(radius=8, tol=0.05, min_votes=2, ratio=0.25)
 
 
 def views_of(cams2world, K):
-    """[n, 16] float32: rows 0..2 of inv(cams2world) (fp64 4x4 algebra), then fx, fy, cx, cy (geo4d_amd.render._views)."""
+    """[n, 16] float32: rows 0..2 of inv(cams2world) (fp64 4x4 algebra), then fx, fy, cx, cy (geo4d_amd.scene_view.views_of)."""
     w2c = np.linalg.inv(np.asarray(cams2world, dtype=np.float64).reshape(-1, 4, 4))
     K = np.asarray(K, dtype=np.float64).reshape(-1, 3, 3)
     return np.concatenate([w2c[:, :3, :].reshape(-1, 12), K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3]], 1).astype(F)

@@ -13,9 +13,9 @@ import torch
 
 import mesh_components_restatement as mc
 import tsdf_mesh_restatement as tm
+from scene_cases import truth_aligner as _synthetic_aligner
 from test_mesh_components_cpu import (HAND_CASES, INT_MAX, INT_MIN, bad_index_mesh, fan, islands_and_strip, percolation_mesh, random_mesh,
                                       strip)
-from test_tsdf_gpu import _synthetic_aligner
 
 pytestmark = pytest.mark.gpu
 NAMES = ("vertex_component", "face_component", "component_vertices", "component_faces")

@@ -15,9 +15,9 @@ import mesh_components_restatement as mc
 import mesh_smooth_restatement as ms
 import tsdf_mesh_restatement as tm
 import tsdf_restatement as tr
+from scene_cases import truth_aligner as _synthetic_aligner
 from test_mesh_components_cpu import INT_MAX, INT_MIN, bad_index_mesh, fan, percolation_mesh, random_mesh, strip
 from test_mesh_smooth_cpu import HAND_CASES
-from test_tsdf_gpu import _synthetic_aligner
 
 pytestmark = pytest.mark.gpu
 EVERY_ROW_BY_A_WAVE, EVERY_ROW_BY_A_THREAD = 0, 1 << 30

@@ -3,7 +3,6 @@ exact votes on the synthetic scene (clean, noisy, with an invalid band; radius 8
 determinism, and what is built on the masks: segment_motion on an aligned scene, the export's static / dynamic parts, the renderer's
 persist_static and save_scene's PNGs."""
 import json
-import math
 import os
 import struct
 
@@ -12,35 +11,10 @@ import pytest
 import torch
 
 import motion_restatement as mr
+from scene_cases import tiny_aligner as _aligner, truth_aligner as _synthetic_aligner
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SCENES = {"clean": dict(), "noisy": dict(noise=0.02), "banded": dict(band=True)}
-
-
-def _aligner(dev):
-    """The tiny aligned scene of tests/test_render_gpu.py."""
-    from geo4d_amd.align import GroupAligner
-    a_fix = torch.load(os.path.join(G, "align_tiny.pt"), weights_only=False)
-    a = GroupAligner(a_fix["groups"], a_fix["pred"].to(dev), a_fix["conf"].squeeze(-1).to(dev), shared_focal=True,
-                     temporal_smoothing_weight=a_fix["kw"]["temporal_smoothing_weight"], translation_weight=a_fix["kw"]["translation_weight"])
-    for k, v in a_fix["init"].items():
-        a.P[k] = v.clone().to(dev)
-    return a
-
-
-def _synthetic_aligner(dev, s):
-    """A GroupAligner whose parameters are the synthetic scene's truth: its depth maps, cameras and focal."""
-    from geo4d_amd.align import FOCAL_BREAK, GroupAligner, rotmat_to_quat, signed_log1p
-    n, H, W = s["n"], s["H"], s["W"]
-    a = GroupAligner([list(range(n))], torch.zeros((1, n, H, W, 3), device=dev), torch.full((1, n, H, W), 5.0, device=dev))
-    a.P["im_depthmaps"].copy_(torch.from_numpy(s["depth"]).to(dev).reshape(n, -1).log())
-    c2w = torch.from_numpy(s["cams2world"])
-    for k in range(n):
-        a.P["im_poses"][k, :4] = rotmat_to_quat(c2w[k, :3, :3]).float().to(dev)
-        a.P["im_poses"][k, 4:7] = signed_log1p(c2w[k, :3, 3].float()).to(dev)
-    a.P["im_focals"][:] = FOCAL_BREAK * math.log(float(s["K"][0, 0, 0]))
-    return a
 
 
 def _scene_arrays(a):

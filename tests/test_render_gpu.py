@@ -8,20 +8,10 @@ import pytest
 import torch
 
 import render_restatement as rr
+from scene_cases import tiny_aligner_and_fixture as _aligner
 from test_render_cpu import CAM, KMAT, SIZE, check_six_point_case, random_case, six_points
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _aligner(dev):
-    from geo4d_amd.align import GroupAligner
-    a_fix = torch.load(os.path.join(G, "align_tiny.pt"), weights_only=False)
-    a = GroupAligner(a_fix["groups"], a_fix["pred"].to(dev), a_fix["conf"].squeeze(-1).to(dev), shared_focal=True,
-                     temporal_smoothing_weight=a_fix["kw"]["temporal_smoothing_weight"], translation_weight=a_fix["kw"]["translation_weight"])
-    for k, v in a_fix["init"].items():
-        a.P[k] = v.clone().to(dev)
-    return a, a_fix
 
 
 def _gpu(dev, points, colors, cams2world, K, size, **kw):

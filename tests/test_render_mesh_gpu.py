@@ -12,9 +12,9 @@ import motion_restatement as mr
 import render_mesh_restatement as rm
 import render_restatement as rr
 import tsdf_restatement as tr
+from scene_cases import truth_aligner as _synthetic_aligner
 from test_render_cpu import random_case
 from test_render_mesh_cpu import check_hand_cases
-from test_tsdf_gpu import _synthetic_aligner
 
 pytestmark = pytest.mark.gpu
 KEYS = ("rgb", "depth", "index", "face")
@@ -105,8 +105,8 @@ def test_random_case_matches_the_restatement(dev, case, how, fill, colours, shad
 
 
 def _views(dev, c):
-    from geo4d_amd.render import _views
-    return _views(c["cams2world"], c["K"]).to(dev)
+    from geo4d_amd.scene_view import views_of
+    return views_of(c["cams2world"], c["K"]).to(dev)
 
 
 def _raster(dev, case, **kw):
@@ -153,7 +153,7 @@ def test_deterministic_order_free_and_view_by_view(dev, case):
 
 
 def test_raster_leaves_nearer_points_alone_and_render_points_is_unchanged(dev, case):
-    from geo4d_amd import ops, render
+    from geo4d_amd import ops, render, scene_view
     m, (H, W) = case["mesh"], case["size"]
     views = _views(dev, case)
     pts, col = _t(dev, case["points"]), _t(dev, case["colors"])
@@ -161,7 +161,7 @@ def test_raster_leaves_nearer_points_alone_and_render_points_is_unchanged(dev, c
     kw = dict(mask=_t(dev, case["mask"]), sources=case["sources"], fill=1)
     before = render.render_points(pts, col, c2w, K, (H, W), **kw)
     N, n = pts.reshape(-1, 3).shape[0], len(views) * H * W
-    ptr, idx = render._csr(case["sources"], len(views), 3)
+    ptr, idx = scene_view.source_lists(case["sources"], len(views), 3)
     ws = ops.render_workspace(len(views), H, W, len(idx), dev)
     ops.render_splat(pts.reshape(-1, 3).contiguous(), views, ptr, idx, (H, W), ws, mask=kw["mask"].reshape(-1), pts_per_image=N // 3)
     k0 = ws[:n].clone()

@@ -3,7 +3,6 @@ points, colours, weights and voxel counts on the synthetic scenes and on a small
 part, a full table and one that is too small, determinism, the edges, and what is built on it: tsdf_scene on an aligned scene, the
 export's `tsdf_voxel` and save_scene's `tsdf_static`."""
 import json
-import math
 import os
 import struct
 
@@ -13,35 +12,10 @@ import torch
 
 import motion_restatement as mr
 import tsdf_restatement as tr
+from scene_cases import tiny_aligner as _aligner, truth_aligner as _synthetic_aligner
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KEYS = ("points", "rgba", "weight")
-
-
-def _aligner(dev):
-    """The tiny aligned scene of tests/test_render_gpu.py."""
-    from geo4d_amd.align import GroupAligner
-    a_fix = torch.load(os.path.join(G, "align_tiny.pt"), weights_only=False)
-    a = GroupAligner(a_fix["groups"], a_fix["pred"].to(dev), a_fix["conf"].squeeze(-1).to(dev), shared_focal=True,
-                     temporal_smoothing_weight=a_fix["kw"]["temporal_smoothing_weight"], translation_weight=a_fix["kw"]["translation_weight"])
-    for k, v in a_fix["init"].items():
-        a.P[k] = v.clone().to(dev)
-    return a
-
-
-def _synthetic_aligner(dev, s):
-    """A GroupAligner whose parameters are the synthetic scene's truth: its depth maps, cameras and focal (tests/test_fusion_gpu.py's)."""
-    from geo4d_amd.align import FOCAL_BREAK, GroupAligner, rotmat_to_quat, signed_log1p
-    n, H, W = s["n"], s["H"], s["W"]
-    a = GroupAligner([list(range(n))], torch.zeros((1, n, H, W, 3), device=dev), torch.full((1, n, H, W), 5.0, device=dev))
-    a.P["im_depthmaps"].copy_(torch.from_numpy(s["depth"]).to(dev).reshape(n, -1).log())
-    c2w = torch.from_numpy(s["cams2world"])
-    for k in range(n):
-        a.P["im_poses"][k, :4] = rotmat_to_quat(c2w[k, :3, :3]).float().to(dev)
-        a.P["im_poses"][k, 4:7] = signed_log1p(c2w[k, :3, 3].float()).to(dev)
-    a.P["im_focals"][:] = FOCAL_BREAK * math.log(float(s["K"][0, 0, 0]))
-    return a
 
 
 def _points(path):
@@ -215,8 +189,8 @@ def test_one_image_thin_images_and_nothing_valid(dev):
 # ---- 5. the scene level ------------------------------------------------------------------------------------------------------------------
 def _scene_ref(a, msk, voxel, weight=None, **kw):
     """The restatement fed the scene's own arrays."""
-    from geo4d_amd.render import _scene_cameras
-    c2w, K = _scene_cameras(a)
+    from geo4d_amd.scene_view import scene_cameras
+    c2w, K = scene_cameras(a)
     imgs = a.imgs.float().cpu().numpy()
     u8 = np.concatenate([np.clip(imgs * np.float32(255) + np.float32(0.5), 0, 255).astype(np.uint8), np.full((*imgs.shape[:3], 1), 255, np.uint8)], -1)
     valid = np.ones((a.n, a.H, a.W), bool) if msk is None else msk

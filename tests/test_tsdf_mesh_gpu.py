@@ -13,7 +13,8 @@ import torch
 import motion_restatement as mr
 import tsdf_mesh_restatement as tm
 import tsdf_restatement as tr
-from test_tsdf_gpu import _aligner, _compare, _gpu, _synthetic_aligner
+from scene_cases import tiny_aligner as _aligner, truth_aligner as _synthetic_aligner
+from test_tsdf_gpu import _compare, _gpu
 
 pytestmark = pytest.mark.gpu
 KEYS = ("vertices", "rgba", "weight", "faces")
@@ -142,8 +143,8 @@ def _mesh(dev, s, **kw):
 def _field(dev, s):
     """The device's own field of scene dict `s`, as numpy: (K, f, Wt, col)."""
     from geo4d_amd import ops
-    from geo4d_amd.render import _views
-    views = _views(s["cams2world"], s["K"]).to(dev)
+    from geo4d_amd.scene_view import views_of
+    views = views_of(s["cams2world"], s["K"]).to(dev)
     K, f, wt, col, M, dropped = ops.tsdf_field(_t(dev, s["pts3d"]), _t(dev, s["depth"]), _t(dev, s["static"]), views, _t(dev, s["centres"]),
                                                _t(dev, s["rgba"]), voxel=float(np.float32(s["voxel"])))
     assert dropped == 0 and M == len(K)

@@ -22,7 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from geo4d_amd import _lib, fusion, mesh, motion, ops  # noqa: E402
-from geo4d_amd.render import _views  # noqa: E402
+from geo4d_amd.scene_view import views_of  # noqa: E402
 from tools.motion_bench import device_ms  # noqa: E402
 from tools.scene_export_bench import synthetic_scene  # noqa: E402
 
@@ -93,7 +93,7 @@ def main():
     every = torch.ones((n, H, W), dtype=torch.bool, device=dev)
     c2w, Kcam = s["c2w"].double().cpu(), s["K"].double().cpu()
     static = (~motion.dynamic_mask(motion.motion_votes(pts3d, depth, every, c2w, Kcam))).contiguous()
-    views, centres = _views(c2w, Kcam).to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
+    views, centres = views_of(c2w, Kcam).to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
     voxel = torch.tensor(fusion.default_voxel(depth, torch.full((n,), s["f"], device=dev), static), dtype=torch.float32).item()
     K, f, wt, col, M, dropped = ops.tsdf_field(pts3d, depth, static, views, centres, None, None, voxel=voxel, trunc=4, near=1e-3)
     assert dropped == 0 and M > 0

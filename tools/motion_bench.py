@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import motion_restatement as mr  # noqa: E402
-from geo4d_amd import motion, ops, render  # noqa: E402
+from geo4d_amd import motion, ops  # noqa: E402
+from geo4d_amd.scene_view import views_of  # noqa: E402
 from tools.scene_export_bench import synthetic_scene  # noqa: E402
 
 
@@ -54,7 +55,7 @@ def main():
     pts3d, depth = s["pts3d"].contiguous(), s["depth"].contiguous()
     valid = torch.ones((n, H, W), dtype=torch.bool, device=dev)
     c2w, K = s["c2w"].double().cpu(), s["K"].double().cpu()
-    views = render._views(c2w, K).to(dev)
+    views = views_of(c2w, K).to(dev)
     ws = ops.motion_range(depth, valid)
     votes = ops.motion_votes(pts3d, depth, valid, views, radius=radius, ws=ws)
     cast = int(votes.sum(dtype=torch.int64).item())

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import render_restatement as rr  # noqa: E402
-from geo4d_amd import ops, render  # noqa: E402
+from geo4d_amd import ops  # noqa: E402
+from geo4d_amd.scene_view import source_lists, views_of  # noqa: E402
 from tools.scene_export_bench import synthetic_scene  # noqa: E402
 
 
@@ -74,8 +75,8 @@ def main():
     col = torch.rand((n * H * W, 3), device=dev)
     pick = [round(i * (n - 1) / max(V - 1, 1)) for i in range(V)]
     c2w, K = s["c2w"][pick].double().cpu(), s["K"][pick].double().cpu()
-    views = render._views(c2w, K).to(dev)
-    ptr, idx = render._csr(None, V, n)
+    views = views_of(c2w, K).to(dev)
+    ptr, idx = source_lists(None, V, n)
     ws = ops.render_workspace(V, H, W, len(idx), dev)
     out = {"frames": n, "H": H, "W": W, "views": V, "points_M": n * H * W / 1e6, "reps": args.reps, "calls_per_window": args.inner}
     for name, radius, max_size in (("size1", None, 9), ("adaptive", (0.5 * 2.0 * s["depth"] / s["f"]).reshape(-1).contiguous(), 9)):

@@ -23,7 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import render_mesh_restatement as rm  # noqa: E402
-from geo4d_amd import fusion, motion, ops, render  # noqa: E402
+from geo4d_amd import fusion, motion, ops  # noqa: E402
+from geo4d_amd.scene_view import source_lists, views_of  # noqa: E402
 from tools.motion_bench import device_ms  # noqa: E402
 from tools.scene_export_bench import synthetic_scene  # noqa: E402
 
@@ -63,7 +64,7 @@ def main():
     every = torch.ones((n, H, W), dtype=torch.bool, device=dev)
     c2w, Kcam = s["c2w"].double().cpu(), s["K"].double().cpu()
     static = (~motion.dynamic_mask(motion.motion_votes(pts3d, depth, every, c2w, Kcam))).contiguous()
-    all_views, centres = render._views(c2w, Kcam).to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
+    all_views, centres = views_of(c2w, Kcam).to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
     rgba = torch.randint(0, 256, (n, H, W, 4), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).to(dev)
     voxel = torch.tensor(fusion.default_voxel(depth, torch.full((n,), s["f"], device=dev), static), dtype=torch.float32).item()
     Kk, f, wt, col, M, dropped = ops.tsdf_field(pts3d, depth, static, all_views, centres, rgba, None, voxel=voxel, trunc=4, near=1e-3)
@@ -88,7 +89,7 @@ def main():
     r["covered_frac"] = float((face >= 0).float().mean())
     r["box_pixels_per_view_M"] = float(sum(box_areas(vert, faces, v, (H, W)).sum() for v in views)) / V / 1e6
     pts, pcol = pts3d.reshape(-1, 3).contiguous(), torch.rand((n * H * W, 3), device=dev)
-    ptr, idx = render._csr(None, V, n)
+    ptr, idx = source_lists(None, V, n)
     splat = lambda: ops.render_splat(pts, views, ptr, idx, (H, W), ws, pts_per_image=H * W)
     r["point_splat_ms_per_view"], r["point_splat_ms_per_view_best"] = (t / V for t in device_ms(splat, args.reps, args.inner))
     r["point_resolve_ms_per_view"] = device_ms(lambda: ops.render_resolve(ws, pcol, V, (H, W)), args.reps, args.inner)[0] / V
@@ -114,7 +115,7 @@ def main():
     for dist in args.close:
         pose = c2w[mid].clone()
         pose[:3, 3] += pose[:3, 2] * (wall - dist)                                # forward along the camera's own z
-        view = render._views(pose[None], Kcam[mid:mid + 1]).to(dev)
+        view = views_of(pose[None], Kcam[mid:mid + 1]).to(dev)
         areas = box_areas(vert, faces, view[0], (H, W))
         c = {"wall_distance": dist, "triangles_with_a_box": int((areas > 0).sum()), "box_pixels_M": float(areas.sum()) / 1e6,
              "largest_box": int(areas.max()), "ms": {}, "boxes_over": {}}

@@ -19,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from geo4d_amd import fusion, motion, ops  # noqa: E402
-from geo4d_amd.render import _views  # noqa: E402
+from geo4d_amd.scene_view import views_of  # noqa: E402
 from tools.motion_bench import device_ms  # noqa: E402
 from tools.scene_export_bench import synthetic_scene  # noqa: E402
 
@@ -106,7 +106,7 @@ def main():
     every = torch.ones((n, H, W), dtype=torch.bool, device=dev)
     c2w, K = s["c2w"].double().cpu(), s["K"].double().cpu()
     static = (~motion.dynamic_mask(motion.motion_votes(pts3d, depth, every, c2w, K))).contiguous()
-    views_host = _views(c2w, K)
+    views_host = views_of(c2w, K)
     views, centres = views_host.to(dev), c2w[:, :3, 3].float().contiguous().to(dev)
     rgba = torch.randint(0, 256, (n, H, W, 4), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).to(dev)
     voxel = torch.tensor(fusion.default_voxel(depth, torch.full((n,), s["f"], device=dev), static), dtype=torch.float32).item()
