@@ -9,6 +9,9 @@
 * ``eval_metrics`` = ``dust3r/utils/vo_eval.py eval_metrics`` (:174-258): ATE and RPE under evo's sim(3) alignment, restated in fp64
   numpy (evo is not a dependency).
 * ``evaluate_scene`` / ``average_depth_metrics``: the glue of infer_geo4d.py around them.
+* ``cloud_metrics`` / ``scene_cloud_metrics``: accuracy, completeness, Chamfer distance and precision / recall / F-score of a point
+  cloud against a ground-truth cloud, on the nearest-neighbour search of csrc/nearest.hip (``geo4d_amd.nearest``). The reference has
+  no such step; the rule is this project's own (include/geo4d_hip.h, tests/nearest_restatement.py).
 """
 import math
 import os
@@ -18,6 +21,10 @@ import torch
 
 from . import _lib, io, ops
 from .align import relative_pose_errors, rigid_points_registration, rotation_angle_deg
+from .fusion import fuse_points
+from .motion import segment_motion
+from .nearest import _cloud, check_cloud, check_radius, nearest_points
+from .scene_view import MOTION, scene_view
 
 DEPTH_KEYS = ("Abs Rel", "Sq Rel", "RMSE", "Log RMSE", "δ < 1.25", "δ < 1.25^2", "δ < 1.25^3")
 
@@ -131,18 +138,43 @@ def _associate(ref_t, est_t, max_diff=0.01):
     return (i_short, i_long) if est_longer else (i_long, i_short)
 
 
-def _sim3_align(est, ref):
-    """evo PosePath3D.align(correct_scale=True): Umeyama sim(3) of the estimated positions onto the reference ones (unit weights), applied
-    to the whole estimated poses."""
+def _sim3_fit(est, ref):
+    """(s, R, T) fp64 of the Umeyama sim(3) that takes the estimated positions onto the reference ones (unit weights): x -> s R x + T."""
     x, y = torch.from_numpy(est[:, :3, 3]), torch.from_numpy(ref[:, :3, 3])
     cov = ((y - y.mean(0)).T @ (x - x.mean(0))).numpy() / len(x)
     if np.count_nonzero(np.linalg.svd(cov, compute_uv=False) > np.finfo(np.float64).eps) < 2:     # evo's GeometryException
         raise ValueError("eval_metrics: degenerate covariance rank, Umeyama alignment is not possible")
-    s, R, T = (v.numpy() for v in rigid_points_registration(x, y, torch.ones(len(x), dtype=torch.float64), fp64=True))
+    return tuple(v.numpy() for v in rigid_points_registration(x, y, torch.ones(len(x), dtype=torch.float64), fp64=True))
+
+
+def _sim3_align(est, ref):
+    """evo PosePath3D.align(correct_scale=True): Umeyama sim(3) of the estimated positions onto the reference ones (unit weights), applied
+    to the whole estimated poses."""
+    s, R, T = _sim3_fit(est, ref)
     out = est.copy()
     out[:, :3, :3] = R @ est[:, :3, :3]
     out[:, :3, 3] = s * est[:, :3, 3] @ R.T + T
     return out
+
+
+def _matched_poses(pred_traj, gt_traj, sample_stride=1):
+    """(reference poses, estimated poses) as [N, 4, 4] fp64, matched by timestamp as eval_metrics matches them."""
+    ep, et = np.asarray(pred_traj[0], dtype=np.float64)[::sample_stride], np.asarray(pred_traj[1], dtype=np.float64).reshape(-1)[::sample_stride]
+    rp, rt = np.asarray(gt_traj[0], dtype=np.float64)[::sample_stride], np.asarray(gt_traj[1], dtype=np.float64).reshape(-1)[::sample_stride]
+    if len(et) == len(rt):
+        et = rt
+    i_ref, i_est = _associate(rt, et)
+    return _tum_to_mats(rp[i_ref]), _tum_to_mats(ep[i_est])
+
+
+def trajectory_sim3(pred_traj, gt_traj, sample_stride=1):
+    """The 4 x 4 fp64 matrix [[s R, T], [0, 1]] of the sim(3) eval_metrics fits between the trajectories (Umeyama, estimated positions
+    onto the reference's): what takes the estimate's world into the ground truth's. A degenerate trajectory raises ValueError."""
+    ref, est = _matched_poses(pred_traj, gt_traj, sample_stride)
+    s, R, T = _sim3_fit(est, ref)
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = s * R, T
+    return M
 
 
 def eval_metrics(pred_traj, gt_traj, seq="", filename="", sample_stride=1):
@@ -154,12 +186,7 @@ def eval_metrics(pred_traj, gt_traj, seq="", filename="", sample_stride=1):
     then the RMSE of the position errors; RPE = evo ``rpe(delta=1 frame, all_pairs=True, align=True, correct_scale=True)``: the same
     sim(3), then the RMSE over consecutive pairs of the translation norm and the rotation angle of (Q_i^-1 Q_{i+1})^-1 (P_i^-1 P_{i+1}).
     ``filename`` (when given) receives a short plain-text summary, not evo's printed report. A degenerate trajectory raises ValueError."""
-    ep, et = np.asarray(pred_traj[0], dtype=np.float64)[::sample_stride], np.asarray(pred_traj[1], dtype=np.float64).reshape(-1)[::sample_stride]
-    rp, rt = np.asarray(gt_traj[0], dtype=np.float64)[::sample_stride], np.asarray(gt_traj[1], dtype=np.float64).reshape(-1)[::sample_stride]
-    if len(et) == len(rt):
-        et = rt
-    i_ref, i_est = _associate(rt, et)
-    ref, est = _tum_to_mats(rp[i_ref]), _tum_to_mats(ep[i_est])
+    ref, est = _matched_poses(pred_traj, gt_traj, sample_stride)
     al = _sim3_align(est, ref)
     ate = float(np.sqrt(np.mean(np.sum((al[:, :3, 3] - ref[:, :3, 3]) ** 2, -1))))
     E = relative_pose_errors(al, ref)
@@ -222,4 +249,120 @@ def evaluate_scene(scene, gt_depth, *, dataset, gt_traj=None, seq="", out_dir=No
             with open(os.path.join(out_dir, seq, "_error_log.txt"), "a") as f:
                 f.write(f"{dataset}-{seq: <16} | ATE: {ate:.5f}, RPE trans: {rpe_trans:.5f}, RPE rot: {rpe_rot:.5f}\n")
                 f.write(f"{ate:.5f}\n{rpe_trans:.5f}\n{rpe_rot:.5f}\n")
+    return out
+
+
+# ---- the 3D result ------------------------------------------------------------------------------------------------------------------
+def _thresholds(thresholds, max_dist):
+    """The thresholds as floats (None: (max_dist,)); ValueError unless 0 < t <= max_dist for each."""
+    ts = (max_dist,) if thresholds is None else tuple(thresholds)
+    try:
+        ts = tuple(float(t) for t in ts)
+    except (TypeError, ValueError):
+        raise ValueError(f"cloud_metrics: thresholds must be numbers, got {thresholds!r}") from None
+    if not ts or not all(0 < t <= max_dist for t in ts):
+        raise ValueError(f"cloud_metrics: thresholds must be a non-empty sequence with 0 < t <= max_dist = {max_dist:g}, got {thresholds!r}")
+    return ts
+
+
+@torch.no_grad()
+def cloud_metrics(pred, gt, *, max_dist, thresholds=None, voxel=None, pred_mask=None, gt_mask=None):
+    """Accuracy, completeness, Chamfer distance and precision / recall / F-score of a predicted cloud against a ground-truth cloud, on the
+    HIP device (geo4d_amd.nearest; the rule of include/geo4d_hip.h). The clouds must already be in one frame: the figures are only as
+    meaningful as the alignment handed in.
+
+    pred [Np, 3], gt [Ng, 3], the masks [N] bool (None: all). A point takes part when its mask is set and its coordinates are finite
+    (`n_pred`, `n_gt`). One nearest-neighbour query runs in each direction with the radius `max_dist`. Per point, d = sqrt(dist2) in
+    fp32 when a neighbour was found within `max_dist`, else `max_dist`: the truncated distance. `accuracy` is the float64 mean of d
+    over the predicted points (pred -> gt), `completeness` over the ground truth's (gt -> pred), `chamfer` their half-sum. Per threshold
+    t of `thresholds` (None: (max_dist,); 0 < t <= max_dist): `within_pred[k]` / `within_gt[k]` count the points with a neighbour at
+    dist2 <= t * t (fp32), `precision[k]` = within_pred / n_pred, `recall[k]` = within_gt / n_gt, `fscore[k]` = 2 P R / (P + R), 0 when
+    P + R = 0. `unmatched_pred` / `unmatched_gt` count the points without a neighbour within `max_dist`. `pred_dist` / `gt_dist` fp32
+    per input row hold d (NaN where the row took no part), for colouring a cloud by its error. `voxel`: both clouds are first reduced
+    with fuse_points(reduce="mean") at that voxel (evaluating downsampled clouds is standard practice, and it keeps the cells small:
+    the time grows with the points per cell); the per-row outputs then belong to the reduced clouds, returned as `pred_points` /
+    `gt_points`. The thresholds' default is untried on real predictions. Either side without a taking-part point raises ValueError,
+    and so do points outside the cell grid (|x| >= 2^20 max_dist)."""
+    who = "cloud_metrics"
+    r = check_radius(max_dist, who, "max_dist")
+    ts = _thresholds(thresholds, r)
+    check_cloud(pred, pred_mask, who, "pred"), check_cloud(gt, gt_mask, who, "gt")
+    pred, pred_mask = _cloud(pred, pred_mask, who, "pred")
+    gt, gt_mask = _cloud(gt, gt_mask, who, "gt")
+    if voxel is not None:
+        pred, pred_mask = fuse_points(pred, mask=pred_mask, voxel=voxel)["points"], None
+        gt, gt_mask = fuse_points(gt, mask=gt_mask, voxel=voxel)["points"], None
+    sides = {}
+    for name, q, qm, ref, rm in (("pred", pred, pred_mask, gt, gt_mask), ("gt", gt, gt_mask, pred, pred_mask)):
+        took = torch.isfinite(q).all(1) if qm is None else torch.isfinite(q).all(1) & qm.to(torch.bool)
+        nn = nearest_points(q, ref, radius=r, query_mask=qm, reference_mask=rm)
+        matched = nn["index"] >= 0
+        # sqrt in fp64 rounded to fp32 is the correctly rounded fp32 square root whatever the device's fp32 sqrt does
+        d = torch.where(matched, nn["dist2"].double().sqrt().float(), torch.full_like(nn["dist2"], r))
+        t2 = [(torch.tensor(t, dtype=torch.float32) * torch.tensor(t, dtype=torch.float32)).item() for t in ts]
+        within = [(matched & (nn["dist2"] <= x)).sum() for x in t2]
+        sides[name] = (took, matched, d, within)
+    host = torch.stack([x.double() for name in ("pred", "gt") for x in
+                        (sides[name][0].sum(), (sides[name][0] & ~sides[name][1]).sum(),
+                         torch.where(sides[name][0], sides[name][2], torch.zeros_like(sides[name][2])).double().sum(), *sides[name][3])]).tolist()
+    K = len(ts)
+    (n_pred, un_pred, sum_pred, *w_pred), (n_gt, un_gt, sum_gt, *w_gt) = host[:3 + K], host[3 + K:]
+    n_pred, n_gt = int(n_pred), int(n_gt)
+    if n_pred == 0 or n_gt == 0:
+        raise ValueError(f"cloud_metrics: no point takes part on the {'predicted' if n_pred == 0 else 'ground-truth'} side (mask set and "
+                         "finite coordinates)")
+    acc, comp = sum_pred / n_pred, sum_gt / n_gt
+    P, R = [int(w) / n_pred for w in w_pred], [int(w) / n_gt for w in w_gt]
+    out = dict(max_dist=r, thresholds=list(ts), n_pred=n_pred, n_gt=n_gt, accuracy=acc, completeness=comp, chamfer=0.5 * (acc + comp),
+               within_pred=[int(w) for w in w_pred], within_gt=[int(w) for w in w_gt], precision=P, recall=R,
+               fscore=[2 * p * q / (p + q) if p + q > 0 else 0.0 for p, q in zip(P, R)], unmatched_pred=int(un_pred), unmatched_gt=int(un_gt))
+    nan = float("nan")
+    out["pred_dist"] = torch.where(sides["pred"][0], sides["pred"][2], torch.full_like(sides["pred"][2], nan))
+    out["gt_dist"] = torch.where(sides["gt"][0], sides["gt"][2], torch.full_like(sides["gt"][2], nan))
+    if voxel is not None:
+        out["pred_points"], out["gt_points"] = pred, gt
+    return out
+
+
+@torch.no_grad()
+def scene_cloud_metrics(scene, gt_points, *, max_dist, thresholds=None, transform=None, gt_traj=None, voxel=None, motion=None, min_conf_thr=3,
+                        thr_for_init_conf=True, is_msk=True, out_dir=None, seq=""):
+    """cloud_metrics of an aligned GroupAligner's points against a ground-truth cloud gt_points [Ng, 3].
+
+    The scene's points and mask are taken as fuse_scene takes them, through scene_view (`min_conf_thr` / `thr_for_init_conf` /
+    `is_msk`, restricted by `motion`). They are moved by `transform` (4 x 4, [[s R, T], [0, 1]]: scale folded in) when given; else,
+    with `gt_traj` ([poses, timestamps] as eval_metrics takes them), by the sim(3) eval_metrics fits between the scene's trajectory and
+    that one (trajectory_sim3); with neither they are not moved. The move is pts @ (s R).T + T in fp32 with torch on the device.
+    With `out_dir`, writes {out_dir}/{seq}_cloud_metric.txt. Returns cloud_metrics' dict plus `transform` (the 4 x 4 fp64 array used,
+    or None)."""
+    if motion not in MOTION:
+        raise ValueError(f"scene_cloud_metrics: motion must be one of {MOTION}, got {motion!r}")
+    if transform is not None and gt_traj is not None:
+        raise ValueError("scene_cloud_metrics: give `transform` or `gt_traj`, not both")
+    if transform is not None:
+        transform = np.asarray(torch.as_tensor(transform).detach().cpu().numpy(), dtype=np.float64)
+        if transform.shape != (4, 4) or not np.isfinite(transform).all():
+            raise ValueError(f"scene_cloud_metrics: transform must be a finite 4 x 4 matrix, got shape {transform.shape}")
+    view = scene_view(scene, "scene_cloud_metrics", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk,
+                      motion=motion, segment=segment_motion)
+    msk = view.mask()
+    if transform is None and gt_traj is not None:
+        transform = trajectory_sim3(io.get_tum_poses(view.poses), gt_traj)
+    pts = view.pts3d.reshape(-1, 3).float()
+    if transform is not None:
+        M = torch.from_numpy(transform).to(view.dev).float()
+        pts = pts @ M[:3, :3].T + M[:3, 3]
+    gt = _as_tensor(gt_points)
+    out = cloud_metrics(pts, gt.to(view.dev) if torch.is_tensor(gt) and gt.dim() == 2 else gt, max_dist=max_dist, thresholds=thresholds,
+                        voxel=voxel, pred_mask=None if msk is None else msk.reshape(-1))
+    out["transform"] = transform
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, f"{seq}_cloud_metric.txt"), "w") as f:
+            f.write(f"Seq: {seq} \n\n")
+            f.write(f"Cloud metrics, truncated at max_dist = {out['max_dist']:g}; {out['n_pred']} predicted and {out['n_gt']} ground-truth points\n")
+            f.write(f"    accuracy\t{out['accuracy']}\n    completeness\t{out['completeness']}\n    chamfer\t{out['chamfer']}\n")
+            f.write(f"    unmatched\t{out['unmatched_pred']} predicted, {out['unmatched_gt']} ground truth\n")
+            for k, t in enumerate(out["thresholds"]):
+                f.write(f"    at {t:g}:\tprecision {out['precision'][k]}\trecall {out['recall'][k]}\tfscore {out['fscore'][k]}\n")
     return out

@@ -10,9 +10,11 @@ per-voxel sums are integers, so the result does not depend on the order of the p
 out sorted by voxel (cx, cy, cz).
 
 This removes duplicates, not noise: points are binned by their noisy positions, so every voxel keeps its bias (at 2 % depth noise the
-fused points of the synthetic scene are no closer to the wall than the raw ones). Limits: cell indices must stay below 2^20 in
-magnitude on every axis (points beyond are refused, not clipped); offsets inside a voxel are kept to 1 / 65536 of its side and weights
-to 1 / 128 within [1 / 128, 256); a surface that crosses a voxel obliquely still leaves one point per voxel it touches.
+fused points of the synthetic scene are no closer to the wall than the raw ones). The one kind of noise it can name is the isolated
+point: ``min_neighbours`` leaves out fused points with too few other fused points near them (csrc/nearest.hip). Limits: cell indices
+must stay below 2^20 in magnitude on every axis (points beyond are refused, not clipped); offsets inside a voxel are kept to 1 / 65536
+of its side and weights to 1 / 128 within [1 / 128, 256); a surface that crosses a voxel obliquely still leaves one point per voxel it
+touches.
 """
 import math
 
@@ -24,6 +26,14 @@ from .scene_view import MOTION, rgba_of, scene_view
 
 REDUCE = tuple(ops.FUSE_REDUCE)
 CELL_LIMIT = 1 << 20
+
+
+def check_neighbour_args(who, min_neighbours, neighbour_radius):
+    """ValueError for a min_neighbours that is not an integer >= 0 or a neighbour_radius (None: the default) that is not finite and
+    > 0 in fp32."""
+    ops.check_min_neighbours(min_neighbours, who)
+    if neighbour_radius is not None:
+        ops.check_nn_radius(neighbour_radius, who, "neighbour_radius")
 
 
 def check_fuse_args(voxel, reduce, min_count):
@@ -42,7 +52,8 @@ def check_fuse_args(voxel, reduce, min_count):
 
 
 @torch.no_grad()
-def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="mean", min_count=1, capacity=None):
+def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="mean", min_count=1, capacity=None, min_neighbours=0,
+                neighbour_radius=None):
     """dict(points fp32 [M, 3], rgba uint8 [M, 4] or None, weight fp32 [M], count int32 [M], voxel): one row per occupied voxel, in
     (cx, cy, cz) order, on the device.
 
@@ -51,8 +62,12 @@ def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="m
     finite and its weight is finite and > 0. reduce "mean": the weighted mean position and colour and the mean weight of the voxel's
     points; "best": the voxel's point of highest weight (the lowest row on ties), copied bit for bit. `count` is the number of points
     in the voxel; voxels with fewer than `min_count` are left out. `capacity` overrides the hash table's size (a power of two >= N).
+    `min_neighbours` > 0: after the reduction and `min_count`, fused points with fewer than that many OTHER fused points within
+    `neighbour_radius` are left out as well (geo4d_amd.nearest.radius_outliers: what removes an isolated floating point);
+    `neighbour_radius=None` means 2 * voxel, a default nobody has tried on real predictions. `min_neighbours=0` launches nothing new.
     Raises ValueError when a point's cell index floor(x / voxel) reaches 2^20 in magnitude."""
     v = check_fuse_args(voxel, reduce, min_count)
+    check_neighbour_args("fuse_points", min_neighbours, neighbour_radius)
     if not points.is_cuda:
         raise _lib.Geo4DNativeError(f"fuse_points: `points` lives on {points.device}; the fusion runs only on a HIP device (there is no "
                                     "CPU fallback)")
@@ -73,6 +88,14 @@ def fuse_points(points, colors=None, weight=None, mask=None, *, voxel, reduce="m
     if min_count > 1:
         keep = count >= int(min_count)
         pts, w, count, rgba = pts[keep], w[keep], count[keep], None if rgba is None else rgba[keep]
+    if min_neighbours > 0:
+        r = ops.check_nn_radius(2 * v if neighbour_radius is None else neighbour_radius, "fuse_points", "neighbour_radius")
+        grid = ops.nn_grid(pts, radius=r)                           # geo4d_amd.nearest.radius_outliers, from below it in the scene layer
+        if grid.dropped:
+            raise ValueError(f"fuse_points: {grid.dropped} fused point(s) lie outside the neighbour search's cell grid: at neighbour_radius "
+                             f"= {r:g} it needs |x| < {CELL_LIMIT * r:g} on every axis; use a larger neighbour_radius")
+        keep = ops.nn_query(grid, pts, exclude_same_row=True)[2] >= min_neighbours
+        pts, w, count, rgba = pts[keep], w[keep], count[keep], None if rgba is None else rgba[keep]
     return dict(points=pts, rgba=rgba, weight=w, count=count, voxel=v)
 
 
@@ -85,7 +108,8 @@ def default_voxel(depth, focals, mask=None, empty=None):
 
 
 @torch.no_grad()
-def fuse_scene(scene, *, voxel=None, motion="static", min_conf_thr=3, thr_for_init_conf=True, is_msk=True, reduce="mean", min_count=1):
+def fuse_scene(scene, *, voxel=None, motion="static", min_conf_thr=3, thr_for_init_conf=True, is_msk=True, reduce="mean", min_count=1,
+               min_neighbours=0, neighbour_radius=None):
     """fuse_points on a GroupAligner; the result (see fuse_points) is also stored as scene.fused.
 
     Points, colours and masks are taken as get_3D_model_from_scene takes them, through scene_view: scene.imgs (None: no colours), the
@@ -93,15 +117,18 @@ def fuse_scene(scene, *, voxel=None, motion="static", min_conf_thr=3, thr_for_in
     scene.dynamic_masks, which segment_motion makes with these thresholds when the scene has none. The weight is the scene's
     confidence, scene.get_conf(), so a pixel whose confidence is not > 0 takes no part. `voxel=None` means default_voxel: 2 *
     median(depth / focal) over the exported pixels, twice the median pixel footprint. That default gave 22.6 times fewer points on the
-    synthetic scene of tests/motion_restatement.py; nobody has tried it on real predictions."""
+    synthetic scene of tests/motion_restatement.py; nobody has tried it on real predictions. `min_neighbours` / `neighbour_radius`
+    are fuse_points': isolated fused points are left out."""
     if motion not in MOTION:
         raise ValueError(f"fuse_scene: motion must be one of {MOTION}, got {motion!r}")
     check_fuse_args(1.0 if voxel is None else voxel, reduce, min_count)
+    check_neighbour_args("fuse_scene", min_neighbours, neighbour_radius)
     view = scene_view(scene, "fuse_scene", min_conf_thr=min_conf_thr, thr_for_init_conf=thr_for_init_conf, is_msk=is_msk, motion=motion,
                       segment=segment_motion)
     msk = view.mask()
     if voxel is None:
         voxel = default_voxel(view.depth, view.focals, msk, empty=1.0)   # nothing to fuse: any voxel gives the empty cloud
     scene.fused = fuse_points(view.pts3d.reshape(-1, 3), None if view.rgb is None else view.rgb.reshape(-1, 3), view.conf.reshape(-1),
-                              None if msk is None else msk.reshape(-1), voxel=voxel, reduce=reduce, min_count=min_count)
+                              None if msk is None else msk.reshape(-1), voxel=voxel, reduce=reduce, min_count=min_count,
+                              min_neighbours=min_neighbours, neighbour_radius=neighbour_radius)
     return scene.fused

@@ -1755,6 +1755,103 @@ def mesh_vertex_normals(vertices, faces, offsets, corners):
     return out
 
 
+class NNGrid:
+    """The cell grid of one reference set (the rule of include/geo4d_hip.h): `radius` (the cell side), cell_keys int64 [M] sorted and
+    unique, cell_start int32 [M + 1], ref_sorted fp32 [Nt, 3] and ref_row int32 [Nt] (the taking-part points in (key, row) order and
+    their original rows), n_reference = Nr, n_taking = Nt, and `dropped`, the reference points outside the grid (an int)."""
+
+    def __init__(self, radius, cell_keys, cell_start, ref_sorted, ref_row, n_reference, n_taking, dropped, device):
+        self.radius, self.cell_keys, self.cell_start, self.ref_sorted, self.ref_row = radius, cell_keys, cell_start, ref_sorted, ref_row
+        self.n_reference, self.n_taking, self.dropped, self.device = n_reference, n_taking, dropped, device
+
+
+def check_nn_radius(radius, who="nearest_points", what="radius"):
+    """The fp32 radius; ValueError unless it is finite and > 0 in fp32 and so is its square."""
+    try:
+        r = torch.tensor(float(radius), dtype=torch.float32)
+        r, r2 = r.item(), (r * r).item()
+    except (TypeError, ValueError):
+        r = r2 = float("nan")
+    if not (r > 0 and r2 < float("inf")):
+        raise ValueError(f"{who}: {what} must be finite and > 0 in fp32, and so must its square, got {radius!r}")
+    return r
+
+
+def check_min_neighbours(min_neighbours, who="radius_outliers"):
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, int) or min_neighbours < 0:
+        raise ValueError(f"{who}: min_neighbours must be an integer >= 0, got {min_neighbours!r}")
+    return min_neighbours
+
+
+def _nn_mask(mask, N):
+    if mask is None:
+        return None
+    assert tuple(_dev(mask, "mask").shape) == (N,), mask.shape
+    return mask.to(torch.bool).contiguous()
+
+
+def _nn_sorted_rows(points, mask, radius):
+    """(order int64 [N], taking, dropped, sorted keys int64 [taking]): the rows of points fp32 [N, 3] (N > 0), the `taking` taking-part
+    ones first in (key, row) order. One launch (geo4d_nn_keys), one stable torch.sort, and one synchronisation for the two counts. A
+    point that takes no part has the key -1 (all ones), which the signed sort puts first: the order is rolled so that they come last."""
+    N, dev = points.shape[0], points.device
+    keys, dropped = torch.empty(N, device=dev, dtype=torch.int64), torch.empty(1, device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().geo4d_nn_keys(points.data_ptr(), _ptr(mask), N, radius, keys.data_ptr(), dropped.data_ptr(), _stream()),
+               "geo4d_nn_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    taking, n_dropped = torch.cat([(keys >= 0).sum().reshape(1), dropped]).tolist()
+    out = N - taking
+    return torch.cat([order[out:], order[:out]]).contiguous(), taking, n_dropped, skeys[out:]
+
+
+def nn_grid(reference, *, radius, mask=None):
+    """The NNGrid of reference fp32 [Nr, 3] (mask bool [Nr] or None) for cells of side `radius`, on the HIP device. geo4d_nn_keys and
+    geo4d_nn_gather are HIP launches; between them torch.sort (stable) orders the keys, torch.unique_consecutive and torch.cumsum make
+    cell_keys and cell_start. Reads Nt and the dropped count back in one synchronisation. Reusable for any number of nn_query calls."""
+    Nr, dev = _want(reference, "reference", torch.float32, (None, 3)).shape[0], reference.device
+    mask = _nn_mask(mask, Nr)
+    radius = float(radius)
+    empty = lambda dt, *shape: torch.empty(shape, device=dev, dtype=dt)
+    if Nr == 0:
+        return NNGrid(radius, empty(torch.int64, 0), torch.zeros(1, device=dev, dtype=torch.int32), empty(torch.float32, 0, 3),
+                      empty(torch.int32, 0), 0, 0, 0, dev)
+    assert Nr < 1 << 31, Nr
+    order, Nt, dropped, skeys = _nn_sorted_rows(reference, mask, radius)
+    cell_keys, counts = torch.unique_consecutive(skeys, return_counts=True)
+    cell_start = torch.zeros(cell_keys.shape[0] + 1, device=dev, dtype=torch.int32)
+    torch.cumsum(counts, 0, dtype=torch.int32, out=cell_start[1:])
+    ref_sorted, ref_row = empty(torch.float32, Nt, 3), empty(torch.int32, Nt)
+    if Nt:
+        _lib.check(_lib.load().geo4d_nn_gather(reference.data_ptr(), order.data_ptr(), Nt, Nr, ref_sorted.data_ptr(), ref_row.data_ptr(),
+                                               _stream()), "geo4d_nn_gather")
+    return NNGrid(radius, cell_keys.contiguous(), cell_start, ref_sorted, ref_row, Nr, Nt, dropped, dev)
+
+
+def nn_query(grid, query, *, mask=None, exclude_same_row=False):
+    """(index int32 [Nq], dist2 fp32 [Nq], count int32 [Nq], dropped int) of query fp32 [Nq, 3] (mask bool [Nq] or None) against an
+    NNGrid (the rule of include/geo4d_hip.h): the nearest reference row within grid.radius (-1: none), its squared distance (+inf) and
+    the number of reference points within; `dropped` counts the queries outside the grid, which get (-1, +inf, 0) like every query
+    that takes no part. geo4d_nn_keys, a stable torch.sort of the queries' keys, then geo4d_nn_query; one synchronisation. No query, or
+    a grid without points, launches nothing."""
+    Nq, dev = _want(query, "query", torch.float32, (None, 3)).shape[0], query.device
+    assert grid.device == dev, (grid.device, dev)
+    mask = _nn_mask(mask, Nq)
+    index = torch.full((Nq,), -1, device=dev, dtype=torch.int32)
+    dist2 = torch.full((Nq,), float("inf"), device=dev, dtype=torch.float32)
+    count = torch.zeros(Nq, device=dev, dtype=torch.int32)
+    if Nq == 0:
+        return index, dist2, count, 0
+    assert Nq < 1 << 31, Nq
+    order, taking, dropped, _ = _nn_sorted_rows(query, mask, grid.radius)
+    if grid.n_taking == 0 or taking == 0:
+        return index, dist2, count, dropped
+    _lib.check(_lib.load().geo4d_nn_query(query.data_ptr(), order.data_ptr(), taking, Nq, grid.cell_keys.data_ptr(), grid.cell_start.data_ptr(),
+                                          grid.cell_keys.shape[0], grid.ref_sorted.data_ptr(), grid.ref_row.data_ptr(), grid.n_taking,
+                                          grid.n_reference, grid.radius, int(bool(exclude_same_row)), index.data_ptr(), dist2.data_ptr(),
+                                          count.data_ptr(), _stream()), "geo4d_nn_query")
+    return index, dist2, count, dropped
+
+
 def tsdf_field(pts3d, depth, valid, views, centres, rgba=None, weight=None, *, voxel, trunc=4, near=1e-3, capacity=None):
     """The TSDF field of a scene (the rule of include/geo4d_hip.h): (K int64 [M] sorted keys, f fp32 [M], wt fp32 [M], col uint8 [M, 4]
     or None, M, dropped); K, f, wt and col are None when no voxel was marked. Inputs as tsdf_points takes them. Mark, compact and

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib, io, ops
-from .fusion import fuse_scene
+from .fusion import check_neighbour_args, fuse_scene
 from .mesh import remove_small_components
 from .motion import segment_motion
 from .render import render_scene, save_render
@@ -59,7 +59,8 @@ def camera_colors(n):
 def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud=False, mask_sky=False, clean_depth=False,
                             transparent_cams=False, cam_size=0.05, show_cam=True, save_name=None, thr_for_init_conf=True, is_msk=True,
                             motion=None, fuse_voxel=None, tsdf_voxel=None, tsdf_mesh=None, min_component_faces=None,
-                            min_component_fraction=None, smooth_iterations=None, smooth_pin_boundary=True, normals=False):
+                            min_component_fraction=None, smooth_iterations=None, smooth_pin_boundary=True, normals=False,
+                            fuse_min_neighbours=0, fuse_neighbour_radius=None):
     """dust3r/demo.py:56-86 on a GroupAligner; returns the path of <outdir>/<save_name or 'scene'>.glb (None when scene is None).
 
     Sets scene.min_conf_thr / thr_for_init_conf as the demo does; `is_msk=False` keeps every pixel. The point cloud is byte-identical
@@ -83,11 +84,17 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
     and neither `fuse_voxel` nor `tsdf_voxel`. `smooth_iterations` / `smooth_pin_boundary` / `normals`: for the TSDF surface alone
     (`tsdf_mesh`): tsdf_scene smooths its mesh by that many Taubin iterations (scene.tsdf then holds the smoothed vertices) and, with
     `normals=True`, the primitive carries the area-weighted unit vertex normals as NORMAL, so that a viewer shades it smoothly. Without
-    `tsdf_mesh` they raise: points have no faces, and the per-image sheets keep unreferenced vertices, whose normal would be zero."""
+    `tsdf_mesh` they raise: points have no faces, and the per-image sheets keep unreferenced vertices, whose normal would be zero.
+    `fuse_min_neighbours` / `fuse_neighbour_radius`: fuse_scene's `min_neighbours` / `neighbour_radius` for the fused cloud alone
+    (fused points with fewer other fused points within the radius are left out); without `fuse_voxel` they raise."""
     if motion not in MOTION:
         raise ValueError(f"get_3D_model_from_scene: motion must be one of {MOTION}, got {motion!r}")
+    check_neighbour_args("get_3D_model_from_scene", fuse_min_neighbours, fuse_neighbour_radius)
     options = MeshOptions(min_component_faces, min_component_fraction, smooth_iterations, smooth_pin_boundary, normals)
     (fuse, fuse_voxel), (tsdf, tsdf_voxel), (surface, tsdf_mesh) = voxel_option(fuse_voxel), voxel_option(tsdf_voxel), voxel_option(tsdf_mesh)
+    if (fuse_min_neighbours or fuse_neighbour_radius is not None) and not fuse:
+        raise ValueError("get_3D_model_from_scene: fuse_min_neighbours / fuse_neighbour_radius thin out the fused cloud alone: they need "
+                         "fuse_voxel")
     if fuse and not as_pointcloud:
         raise ValueError("get_3D_model_from_scene: fuse_voxel merges points and has no faces to give: it needs as_pointcloud=True")
     if tsdf and fuse:
@@ -122,7 +129,8 @@ def get_3D_model_from_scene(outdir, silent, scene, min_conf_thr=3, as_pointcloud
         part = dict(view.thresholds, motion=motion)                 # fuse_scene and tsdf_scene take the scene again, the same way
         cloud = lambda d: [dict(mode=0, positions=d["points"].cpu().numpy(), colors=d["rgba"].cpu().numpy())] if len(d["points"]) else []
         if fuse:
-            geometry = cloud(fuse_scene(scene, voxel=fuse_voxel, **part))
+            geometry = cloud(fuse_scene(scene, voxel=fuse_voxel, min_neighbours=fuse_min_neighbours, neighbour_radius=fuse_neighbour_radius,
+                                        **part))
         elif tsdf:
             geometry = cloud(tsdf_scene(scene, voxel=tsdf_voxel, **part))
         elif surface:
@@ -167,7 +175,8 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     the static part's TSDF surface as a triangle mesh (get_3D_model_from_scene(motion="static", as_pointcloud=False, tsdf_mesh=...)),
     and nothing else; `min_component_faces` / `min_component_fraction` among `glb_kw` filter that mesh alone (see
     get_3D_model_from_scene): the other files are point clouds unless `glb_kw` says otherwise, and are written as without them;
-    `smooth_iterations` / `smooth_pin_boundary` / `normals` among `glb_kw` likewise reach that mesh alone. Returns the directory."""
+    `smooth_iterations` / `smooth_pin_boundary` / `normals` among `glb_kw` likewise reach that mesh alone; `fuse_min_neighbours` /
+    `fuse_neighbour_radius` among `glb_kw` reach <seq>_static_fused.glb alone and raise without `fuse_static`. Returns the directory."""
     from .align import rgb_frames
     d = os.path.join(outdir, seq)
     os.makedirs(d, exist_ok=True)
@@ -179,6 +188,10 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
     if not kw["as_pointcloud"]:
         kw.update(pieces)
     pieces.update({k: kw.pop(k) for k in ("smooth_iterations", "smooth_pin_boundary", "normals") if k in kw})   # of the TSDF mesh only
+    near = {k: kw.pop(k) for k in ("fuse_min_neighbours", "fuse_neighbour_radius") if k in kw}   # of the fused static cloud only
+    check_neighbour_args("save_scene", near.get("fuse_min_neighbours", 0), near.get("fuse_neighbour_radius"))
+    if (near.get("fuse_min_neighbours") or near.get("fuse_neighbour_radius") is not None) and not voxel_option(fuse_static)[0]:
+        raise ValueError("save_scene: fuse_min_neighbours / fuse_neighbour_radius thin out the fused static cloud alone: they need fuse_static")
     is_msk, thr_init = kw["is_msk"], kw.get("thr_for_init_conf", True)
     silent = kw.pop("silent")
     get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=seq, **kw)
@@ -191,7 +204,8 @@ def save_scene(scene, outdir, seq, imgs=None, min_conf_thr=2, render=None, dynam
                                     ("tsdf_mesh", "tsdf_mesh", tsdf_mesh_static, False)):
         if voxel_option(voxel)[0]:                                  # the static part again, as another cloud or as the TSDF mesh
             get_3D_model_from_scene(d, silent, scene, min_conf_thr=min_conf_thr, save_name=f"{seq}_static_{name}",
-                                    **dict(kw, motion="static", as_pointcloud=cloud, **{arg: voxel}, **({} if cloud else pieces)))
+                                    **dict(kw, motion="static", as_pointcloud=cloud, **{arg: voxel}, **({} if cloud else pieces),
+                                           **(near if name == "fused" else {})))
     with torch.no_grad():
         io.save_tum_poses(os.path.join(d, "pred_traj.txt"), scene.get_im_poses_matrix().detach())
         io.save_focals(os.path.join(d, "pred_focal.txt"), scene.get_focals().detach())

@@ -799,6 +799,51 @@ int geo4d_mesh_smooth_step(const float* vertices, const int* faces, long T, long
 int geo4d_mesh_vertex_normals(const float* vertices, const int* faces, long T, long Nv, const int* offsets, const int* corners, long E,
                               float* normals_out, void* stream);
 
+/* For every query point, the nearest reference point within a radius and the number of reference points within it, on a grid of cells
+ * of side radius (geo4d_amd/csrc/nearest.hip, geo4d_amd/nearest.py): what the cloud metrics of geo4d_amd/evaluation.py and the radius
+ * outlier removal of geo4d_amd/fusion.py stand on. The reference has no such step; the rule is this project's own, restated in numpy in
+ * tests/nearest_restatement.py. Arithmetic: fp32 in the written order, contraction into FMAs off, only + - * / and floorf, each
+ * correctly rounded, so no comparison with the restatement has a tolerance.
+ *   Inputs: reference fp32 [Nr][3] with reference_mask u8 [Nr] (NULL: every row), query fp32 [Nq][3] with query_mask likewise, the
+ *     radius r > 0 with r2 = r * r finite in fp32, exclude_same_row (0 / 1); Nr, Nq < 2^31.
+ *   1. Cells: the cell side is r; a point's cell is c_a = floorf(X_a / r); the cell takes part iff fabsf(c_a) < 2^20 on every axis and
+ *     its key is (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20), as for the fusion: unsigned key order is (cx, cy, cz) order.
+ *   2. Who takes part: a point (reference or query) takes part iff its mask is set, its coordinates are finite and its cell takes part.
+ *     A point that fails only the last condition is counted in `dropped`; the others are skipped silently. A query that takes no part
+ *     gets index = -1, dist2 = +inf, count = 0.
+ *   3. Candidates of query i: the taking-part reference rows j whose integer cell differs from the query's by at most 1 on every axis,
+ *     without j = i when exclude_same_row. Cells outside the grid (|c| >= 2^20) do not exist and are skipped; they are never reached
+ *     through a carry between the fields of a key.
+ *   4. Distance: dx = Qx - Rx, likewise dy, dz; d2 = (dx dx + dy dy) + dz dz; j is within iff d2 <= r2.
+ *   5. Per query: count int32 = the number of candidates within; index int32 = the within candidate with the smallest (d2, j) in
+ *     lexicographic order (the lowest original row wins on ties), or -1; dist2 fp32 = its d2, or +inf.
+ *   6. Every output is a minimum or an integer count over a set, so it depends neither on the order the candidates are visited in nor
+ *     on the run: two runs are equal bit for bit. Permuting the reference rows leaves dist2 and count unchanged.
+ *   7. Against "every taking-part reference with d2 <= r2" the restriction to neighbouring cells changes nothing in exact arithmetic;
+ *     floorf(X / r) rounds, so a query can differ only where a reference lies within rounding of r from it (measured: none of 3 000
+ *     queries, six inputs, tests/test_nearest_cpu.py).
+ *   geo4d_nn_keys: keys_out int64 [N] = the key of a taking-part point, all ones for any other (after every real key in unsigned
+ *     order; first in a signed sort); dropped int64 [1] := the count of rule 2 (zeroed by the call; one integer atomic add per
+ *     workgroup). The caller sorts the keys stably and forms the grid of the reference: cell_keys int64 [M] sorted and unique,
+ *     cell_start int32 [M + 1] = the exclusive prefix sum of the points per cell, Nt = cell_start[M] the taking-part points.
+ *     geo4d_nn_gather: for k < Nt, sorted_out fp32 [Nt][3] = points[order[k]] and row_out int32 [Nt] = order[k], where order int64
+ *     [Nt] lists the taking-part rows in (key, row) order; an entry outside [0, N) gives row -1 and NaN coordinates.
+ *     geo4d_nn_query: query_order int64 [Nq] lists the query rows, the Nq_taking taking-part ones first and sorted by their own key
+ *     (so that a wave's lanes share cells); one thread per entry writes the three outputs of its row: the rule above for the first
+ *     Nq_taking, (-1, +inf, 0) for the others. Nine lower-bound searches of cell_keys per query (the three cells of a column are
+ *     consecutive in key order), each followed by a walk over the column's contiguous range of ref_sorted. Every loop is counted: 3 x 3
+ *     columns, at most 32 halvings, at most 3 cells, at most Nt points; no thread waits for another. A cell_start outside [0, Nt] and
+ *     a ref_row outside [0, Nr) are skipped and never dereferenced; a query_order entry outside [0, Nq) writes nothing.
+ *   N = 0, Nt = 0 and Nq = 0 launch nothing. Limits: one nearest neighbour, int32 indices; time grows with the points per cell.
+ *   Null pointers (the masks excepted, and what an extent of 0 leaves without storage), sizes < 0 or >= 2^31, Nt > N, Nq_taking > Nq,
+ *   M > Nt, Nt > Nr, a radius that is not finite and > 0 or whose square is not finite in fp32, exclude_same_row other than 0 / 1 and
+ *   an output that is an input or another output return -EINVAL before any device work. */
+int geo4d_nn_keys(const float* points, const unsigned char* mask, long N, float radius, long* keys_out, long* dropped, void* stream);
+int geo4d_nn_gather(const float* points, const long* order, long Nt, long N, float* sorted_out, int* row_out, void* stream);
+int geo4d_nn_query(const float* query, const long* query_order, long Nq_taking, long Nq, const long* cell_keys, const int* cell_start,
+                   long M, const float* ref_sorted, const int* ref_row, long Nt, long Nr, float radius, int exclude_same_row,
+                   int* index_out, float* dist2_out, int* count_out, void* stream);
+
 /* z-shift and focal of point maps from the maps alone (geo4d_amd/csrc/focal_shift.hip). replaces utils.geometry.point_map_to_depth ->
  * solve_optimal_shift_focal(..., ransac_iters=None) (utils/geometry.py:162-270: nearest down-sampling, then scipy least_squares from
  * shift 0 per map on the host), as init_im_poses.align_group_prefix (:244-271) calls it. Per map b, over the selected pixels:
